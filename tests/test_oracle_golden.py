@@ -1,11 +1,11 @@
 """The oracle restatement vs the golden vectors the UNMODIFIED reference produced
-(oracle/make_golden.py), and - where /root/reference exists - vs the live reference."""
+(oracle/make_golden.py)."""
 import os
 
 import pytest
 import torch
 
-from oracle.cases import CASES, build_case, default_shapes, input_checksum, with_grad
+from oracle.cases import CASES, build_case, input_checksum, with_grad
 from oracle.transfusion_oracle import forward_train, naive_mask
 
 GOLDEN = os.path.join(os.path.dirname(__file__), 'golden')
@@ -88,14 +88,14 @@ def test_packed_layout_known_answers():
     assert P.positions[0][:3] == [(0, 29, 4), (1, 62, 2), (0, 93, 4)]
 
 
-@pytest.mark.reference
 @pytest.mark.parametrize('name', ['tiny1'])
 def test_oracle_matches_live_reference(name):
-    from oracle import ref_runner
-    if not ref_runner.reference_available():
-        pytest.skip('/root/reference not present (GPU box)')
+    """the reference's complete outputs of a small case - every logit and every gradient, as oracle/make_golden.py stored them from
+    `ref_runner.reference_forward_backward` - held to the tolerances of a same-process comparison with the live reference"""
+    ref = load_golden(name)
+    assert ref['row_step'] == 1 and 'grads' in ref, 'needs the full logits and gradients of the case'
     cfg, sd, batch, times, noise = build_case(name)
-    ref, _ = ref_runner.reference_forward_backward(cfg, sd, batch, times, noise, modality_default_shape=default_shapes(cfg))
+    assert abs(input_checksum(sd, batch, times, noise) - ref['input_checksum']) <= 1e-6 * abs(ref['input_checksum'])
     sdg = with_grad(sd)
     out = forward_train(sdg, cfg, batch, times, noise, return_all=True)
     out['loss'].backward()

@@ -7,7 +7,7 @@ O=$R/gpurun_out/step_ab.txt
 for round in 1 2; do
   for spec in "$@"; do
     tag=${spec%%:*}; envs=${spec#*:}
-    env $envs python bench.py --steps ${STEPS:-12} --warmup 4 --no-cpu-baseline --no-sample --no-other-configs --no-parity --ragged-steps 0 > /tmp/ab_$tag.json 2>/tmp/ab_$tag.err || tail -3 /tmp/ab_$tag.err >> $O
+    env $envs python bench.py --full --steps ${STEPS:-12} --warmup 4 --no-cpu-baseline --no-sample --no-other-configs --no-parity --ragged-steps 0 > /tmp/ab_$tag.json 2>/tmp/ab_$tag.err || tail -3 /tmp/ab_$tag.err >> $O
     python - "$tag" /tmp/ab_$tag.json >> $O <<'PY'
 import json, sys
 tag, path = sys.argv[1], sys.argv[2]
