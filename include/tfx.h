@@ -171,6 +171,12 @@ typedef struct {
   const int32_t* nr_rot_pos; const float* nr_cos; const float* nr_sin;
   float nr_q_scale, nr_norm_scale;
   float* nr_dgamma_q; float* nr_dgamma_k;
+  /* LASER attention (reference T:979-983, T:1019-1022; Transformer(attn_laser=True)), forward, decode and backward.  0 = off: every kernel computes what it
+   * computed before the field existed, bit for bit.  1: `v` holds v' = exp(c tanh(v / c)) (tfx_laser_v_fwd) and the forward writes og = sigmoid(gate) log(P v')
+   * instead of sigmoid(gate) P v'; `lse` is unchanged.  The backward prep then takes L = og / sigmoid(gate) and hands the dK/dV and dQ kernels
+   * do_eff = dout sigmoid(gate) exp(-L), delta = sum_d dout sigmoid(gate) (= do_eff . P v' exactly), dgate = sum_d dout og (1 - sigmoid(gate)); their dv is
+   * d v', which tfx_laser_v_bwd turns into d v. */
+  int32_t laser;
 } tfx_attn_args;
 int tfx_attn_fwd(const tfx_attn_args* a, void* stream);
 int tfx_attn_bwd(const tfx_attn_args* a, void* stream);   /* prep + dK/dV kernel + dQ kernel */
@@ -179,6 +185,24 @@ int tfx_attn_bwd(const tfx_attn_args* a, void* stream);   /* prep + dK/dV kernel
  * sample, keys / values in a per-sample buffer of `n_kv` > 0 rows, kv_end[t] = visible cache length of query row t (own prefix + the block
  * being decoded).  Fails with -10 when n_kv == 0. */
 int tfx_decode_attn(const tfx_attn_args* a, void* stream);
+
+/* LASER value transform (reference T:979-983: softclamp T:280-281, then exp): token-wise over T rows of H heads x 64 columns.
+ *   forward:  vl[rowmap[t]] = bf16(exp(c tanh(v[t] / c))), computed in fp32 and rounded once; rowmap NULL = row t, rowmap[t] < 0 = skip
+ *             (decode steps: this step's rows into a side cache of v', the rows the KV-cache append writes raw v to)
+ *   backward: dv[t] = dvl[t] exp(c tanh(v[t] / c)) (1 - tanh(v[t] / c)^2), the factor recomputed in fp32 from the raw v; dv may alias dvl
+ *             (in place over the d v' the attention backward wrote).  rowmap is ignored.
+ * All leading dimensions % 8 == 0, 16-byte aligned bases; c > 0.  |c tanh| <= c, so v' needs no max-subtraction: [exp(-c), exp(c)]. */
+typedef struct {
+  int32_t T, H;
+  const tfx_bf16* v; int32_t ld_v;            /* raw values */
+  tfx_bf16* vl; int32_t ld_vl;                /* forward: v' out */
+  const int32_t* rowmap;                      /* forward, optional: output row of input row t (< 0 = skip) */
+  float c;                                    /* laser_softclamp_value (reference default 15, T:866) */
+  const tfx_bf16* dvl; int32_t ld_dvl;        /* backward: d v' in */
+  tfx_bf16* dv; int32_t ld_dv;                /* backward: d v out */
+} tfx_laser_v_args;
+int tfx_laser_v_fwd(const tfx_laser_v_args* a, void* stream);
+int tfx_laser_v_bwd(const tfx_laser_v_args* a, void* stream);
 
 /* ---- token-wise kernels ---------------------------------------------------------------------- */
 typedef struct {
@@ -471,7 +495,7 @@ enum { TFX_OP_GEMM_NT = 0, TFX_OP_GEMM_TN = 1, TFX_OP_ATTN_FWD = 2, TFX_OP_ATTN_
        TFX_OP_ADALN_POST_FWD = 6, TFX_OP_ADALN_POST_BWD = 7, TFX_OP_QK_NORM_ROPE_FWD = 8, TFX_OP_QK_NORM_ROPE_BWD = 9, TFX_OP_ATTNRES_FWD = 10,
        TFX_OP_ATTNRES_BWD = 11, TFX_OP_RMSNORM_FWD = 12, TFX_OP_RMSNORM_BWD = 13, TFX_OP_EMBED_FWD = 14, TFX_OP_EMBED_BWD = 15,
        TFX_OP_NOISE_MIX = 16, TFX_OP_FOURIER = 17, TFX_OP_CE_FWD_BWD = 18, TFX_OP_MSE_FWD_BWD = 19, TFX_OP_CAST_ROWS = 20, TFX_OP_CAST_ROWS_T = 21,
-       TFX_OP_ADAM_STEP = 22, TFX_OP_DECODE_ATTN = 23,
+       TFX_OP_ADAM_STEP = 22, TFX_OP_DECODE_ATTN = 23, TFX_OP_LASER_V_FWD = 24, TFX_OP_LASER_V_BWD = 25,
        /* positional entry points (args = tfx_raw_args) */
        TFX_OP_OUTPUT_TO_FLOW = 32, TFX_OP_GATHER_F32 = 33, TFX_OP_ONEHOT_BF16 = 34, TFX_OP_SCATTER_ROWS_BF16 = 35, TFX_OP_F32_TO_BF16 = 36,
        TFX_OP_SILU_BWD = 37, TFX_OP_COLSUM_BF16 = 38, TFX_OP_COLSUM_F32 = 39, TFX_OP_ADD_BF16 = 40, TFX_OP_SCALE_BF16_DEV = 41, TFX_OP_CAST_BLOCK_BF16 = 42, TFX_OP_SCALE_BF16_COPY = 43, TFX_OP_ADALN_POST_PRE_FWD = 44, TFX_OP_LAYER_END_FWD = 45,

@@ -578,14 +578,24 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_pipe_kernel(tfx_attn_args p) 
   ls += __shfl_xor(ls, 32, 64);
   {
     const float g = sigmoidf_(bf2f(p.gate[(tok0 + qc) * p.ld_gate + h]));
-    const float sc = g * __builtin_amdgcn_rcpf(ls);
     bf16x4 ov[2][4];
+    if (p.laser) {                                              // (kernel argument: wave-uniform) LASER: og = g log(P v'), T:1019-1022
+      const float rl = __builtin_amdgcn_rcpf(ls);
 #pragma unroll
-    for (int db = 0; db < 2; db++)
+      for (int db = 0; db < 2; db++)
 #pragma unroll
-      for (int rg = 0; rg < 4; rg++)
+        for (int rg = 0; rg < 4; rg++)
 #pragma unroll
-        for (int e = 0; e < 4; e++) ov[db][rg][e] = f2bf(o[db][rg * 4 + e] * sc);
+          for (int e = 0; e < 4; e++) ov[db][rg][e] = f2bf(g * __logf(o[db][rg * 4 + e] * rl));
+    } else {
+      const float sc = g * __builtin_amdgcn_rcpf(ls);
+#pragma unroll
+      for (int db = 0; db < 2; db++)
+#pragma unroll
+        for (int rg = 0; rg < 4; rg++)
+#pragma unroll
+          for (int e = 0; e < 4; e++) ov[db][rg][e] = f2bf(o[db][rg * 4 + e] * sc);
+    }
     __syncthreads();                                            // every wave is through with the K / V tiles: their LDS becomes the staging area
     wave_block_store(&Ks[0][0] + w * 2048, ov, p.out + (tok0 + q0 + w * 32) * p.ld_out + h * DH, p.ld_out, n - (q0 + w * 32));
     if (qrow < n && hi == 0) p.lse[((size_t)b * p.h + h) * p.n + qrow] = __log2f(ls) * LN2;
@@ -606,6 +616,25 @@ __global__ __launch_bounds__(256) void attn_bwd_prep_kernel(tfx_attn_args p) {
   const bf16x8 d8 = *(const bf16x8*)(p.dout + (size_t)t * p.ld_dout + h * DH + sub * 8);
   const bf16x8 o8 = *(const bf16x8*)(p.out + (size_t)t * p.ld_out + h * DH + sub * 8);
   const float g = sigmoidf_(bf2f(p.gate[(size_t)t * p.ld_gate + h]));
+  if (p.laser) {
+    // LASER: og = g L with L = log O, O = P v'.  do_eff = dout g / O = dout g exp(-L); delta = do_eff . O = sum dout g (exact); dgate as below
+    const float rg = __builtin_amdgcn_rcpf(fmaxf(g, 1e-30f));
+    float dg = 0.f, ds = 0.f; bf16x8 e8;
+#pragma unroll
+    for (int e = 0; e < 8; e++) {
+      const float d = bf2f(d8[e]), og = bf2f(o8[e]);
+      dg += d * og; ds += d;
+      e8[e] = f2bf(d * g * __expf(-og * rg));
+    }
+    *(bf16x8*)(p.do_eff + (size_t)t * p.ld_do + h * DH + sub * 8) = e8;
+    dg = group8_sum(dg); ds = group8_sum(ds);
+    if (sub == 0) {
+      const unsigned bb = t / (unsigned)p.n, i = t - bb * p.n;
+      p.delta[((size_t)bb * p.h + h) * p.n + i] = ds * g;
+      p.dgate[(size_t)t * p.ld_dgate + h] = f2bf(dg * (1.f - g));
+    }
+    return;
+  }
   float dl = 0.f; bf16x8 e8;
 #pragma unroll
   for (int e = 0; e < 8; e++) { float d = bf2f(d8[e]); dl += d * bf2f(o8[e]); e8[e] = f2bf(d * g); }

@@ -187,10 +187,16 @@ __global__ __launch_bounds__(256) void decode_attn_rows_k(tfx_attn_args p) {
       lt += red[r][gg][s2][8];
     }
     const float gate = bf2f(p.gate[(size_t)t * p.ld_gate + h]);
-    const float sc = __builtin_amdgcn_rcpf(1.f + __expf(-gate)) / lt;
     bf16x8 ov;
+    if (p.laser) {                                         // LASER (T:1019-1022): `v` is the side cache of v' = exp(softclamp(v)); og = g log(o / l)
+      const float gs = __builtin_amdgcn_rcpf(1.f + __expf(-gate)), rl = 1.f / lt;
 #pragma unroll
-    for (int e = 0; e < 8; e++) ov[e] = f2bf(o[e] * sc);
+      for (int e = 0; e < 8; e++) ov[e] = f2bf(gs * __logf(o[e] * rl));
+    } else {
+      const float sc = __builtin_amdgcn_rcpf(1.f + __expf(-gate)) / lt;
+#pragma unroll
+      for (int e = 0; e < 8; e++) ov[e] = f2bf(o[e] * sc);
+    }
     *(bf16x8*)(p.out + (size_t)t * p.ld_out + h * 64 + s2 * 8) = ov;
     if (p.lse && s2 == 0) p.lse[((size_t)b * p.h + h) * p.n + r] = __logf(lt);
   }

@@ -2013,6 +2013,45 @@ __global__ __launch_bounds__(256) void ema_k(float* ema, const float* online, lo
   }
 }
 
+// LASER value transform (reference T:979-983): v' = exp(c tanh(v / c)) and its backward.  One lane per 8 contiguous columns (16-byte accesses),
+// the T x H*64 matrix flattened row-major over 8-column chunks; 32-bit index math (the launcher checks the chunk count)
+TFX_DEV float laser_factor(float x, float c, float ic, float* th_out) {
+  const float th = tanhf(x * ic);
+  *th_out = th;
+  return expf(c * th);
+}
+__global__ __launch_bounds__(256) void laser_v_fwd_k(tfx_laser_v_args p, unsigned nch) {
+  const unsigned gid = blockIdx.x * blockDim.x + threadIdx.x;
+  const unsigned cpr = (unsigned)p.H * 8;                             // 8-column chunks per row
+  if (gid >= nch) return;
+  const unsigned t = gid / cpr, c8 = gid - t * cpr;
+  const int dst = p.rowmap ? p.rowmap[t] : (int)t;
+  if (dst < 0) return;
+  const bf16x8 x = *(const bf16x8*)(p.v + (size_t)t * p.ld_v + c8 * 8);
+  const float ic = 1.f / p.c;
+  bf16x8 y;
+#pragma unroll
+  for (int e = 0; e < 8; e++) { float th; y[e] = f2bf(laser_factor(bf2f(x[e]), p.c, ic, &th)); }
+  *(bf16x8*)(p.vl + (size_t)dst * p.ld_vl + c8 * 8) = y;
+}
+__global__ __launch_bounds__(256) void laser_v_bwd_k(tfx_laser_v_args p, unsigned nch) {
+  const unsigned gid = blockIdx.x * blockDim.x + threadIdx.x;
+  const unsigned cpr = (unsigned)p.H * 8;
+  if (gid >= nch) return;
+  const unsigned t = gid / cpr, c8 = gid - t * cpr;
+  const bf16x8 x = *(const bf16x8*)(p.v + (size_t)t * p.ld_v + c8 * 8);
+  const bf16x8 g = *(const bf16x8*)(p.dvl + (size_t)t * p.ld_dvl + c8 * 8);
+  const float ic = 1.f / p.c;
+  bf16x8 y;
+#pragma unroll
+  for (int e = 0; e < 8; e++) {
+    float th;
+    const float f = laser_factor(bf2f(x[e]), p.c, ic, &th);
+    y[e] = f2bf(bf2f(g[e]) * f * (1.f - th * th));
+  }
+  *(bf16x8*)(p.dv + (size_t)t * p.ld_dv + c8 * 8) = y;
+}
+
 }  // namespace tfx
 
 // ------------------------------------------------------------------------------------------------
@@ -2293,6 +2332,23 @@ int tfx_mfma_peak_probe(const void* ops, float* out, int32_t iters, int32_t bloc
   if (!ops || !out || iters <= 0 || blocks <= 0) return -1;
   hipLaunchKernelGGL(mfma_peak_k, dim3(blocks), dim3(256), 0, ST(s), (const bf16x8*)ops, out, iters); RET();
 }
-const char* tfx_version(void) { return "tfx-hip gfx950 r1"; }
+int tfx_laser_v_fwd(const tfx_laser_v_args* a, void* s) {
+  if (!a || a->T < 0 || a->H <= 0 || !(a->c > 0.f)) return -1;
+  if (a->T == 0) return 0;
+  if (!a->v || !a->vl || ((a->ld_v | a->ld_vl) & 7) || a->ld_v < a->H * 64 || a->ld_vl < a->H * 64 || (((uintptr_t)a->v | (uintptr_t)a->vl) & 15)) return -2;
+  const long long nch = (long long)a->T * a->H * 8;
+  if (nch >= (1ll << 31)) return -4;
+  hipLaunchKernelGGL(laser_v_fwd_k, dim3((unsigned)((nch + 255) / 256)), dim3(256), 0, ST(s), *a, (unsigned)nch); RET();
+}
+int tfx_laser_v_bwd(const tfx_laser_v_args* a, void* s) {
+  if (!a || a->T < 0 || a->H <= 0 || !(a->c > 0.f)) return -1;
+  if (a->T == 0) return 0;
+  if (!a->v || !a->dvl || !a->dv || ((a->ld_v | a->ld_dvl | a->ld_dv) & 7) || a->ld_v < a->H * 64 || a->ld_dvl < a->H * 64 || a->ld_dv < a->H * 64 ||
+      (((uintptr_t)a->v | (uintptr_t)a->dvl | (uintptr_t)a->dv) & 15)) return -2;
+  const long long nch = (long long)a->T * a->H * 8;
+  if (nch >= (1ll << 31)) return -4;
+  hipLaunchKernelGGL(laser_v_bwd_k, dim3((unsigned)((nch + 255) / 256)), dim3(256), 0, ST(s), *a, (unsigned)nch); RET();
+}
+const char* tfx_version(void) { return "tfx-hip gfx950 r2-laser"; }
 
 }  // extern "C"

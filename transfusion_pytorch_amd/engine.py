@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import weakref
 
 import torch
 
@@ -282,6 +283,23 @@ class Plan:
         # per layer: the soft-cap plan tfx_qk_norm_rope_fwd derives from the layer's QK-RMSNorm gains (tfx.h) and its attention kernels - forward
         # and, later, backward - read: polynomial degree and coefficients from the BOUND on the scores, no look at the data.  TFX_SC_PLAN=0: decide from the scores
         self.sc_plan = z(D, 8, dtype=torch.float32)
+        # LASER attention (md.laser = its softclamp value; T:979-983): the attention reads v' = exp(c tanh(v / c)), written by tfx_laser_v_fwd behind the
+        # projection.  Training plans keep v' per layer ([T, heads 64] bf16: 64 MiB per layer at 65 536 tokens x 512), so the backward reads the forward's
+        # v' instead of recomputing it; inference plans without a cache share one buffer across layers (`li`).  Decode plans keep a side cache of v' beside
+        # the KV cache (which holds raw v, T:977), shared by the plans over the same cache buffer and freed with the last of them (weak references); every
+        # step re-derives it for ALL cache rows after the append, so a cache filled, grown, copied or handed in by any route is covered.  Laser off: no
+        # buffer, no launch.
+        self.vl = self.vlc = None
+        if md.laser:
+            if cache is None:
+                self.vl = e(nl, T, hd)
+            else:
+                side = ps.__dict__.setdefault('_laser_side', weakref.WeakValueDictionary())
+                key = (cache.data_ptr(), tuple(cache.shape), tuple(cache.stride()))
+                self.vlc = side.get(key)
+                if self.vlc is None:
+                    self.vlc = e(D, cache.shape[1] * cache.shape[2], hd)          # counted in the plan that creates it
+                    side[key] = self.vlc
         self.fwd, self.bwd = LaunchList(), LaunchList()
         self.noise_args = {}
         self.loaded_structure = None
@@ -463,6 +481,7 @@ class Plan:
                          **({'qk_plan': plan_kw['sc_plan'], 'qk_softcap': 50.0} if plan_kw else {}),
                          **(dict(qk_cache=self.cache[i], qk_ld_cache=2 * hd, qk_cache_pos=self.cache_pos) if self.cache is not None else {}))
                 self._rope_nt_args = getattr(self, '_rope_nt_args', []) + [L[-1][1]]
+                self._laser_fwd(L, i)
                 self._k(L, 'tfx_attn_fwd' if (self.cache is None or self.tile_attn) else 'tfx_decode_attn', 'tfx_attn_args', **self._attn_kw(i))
             else:
                 self._nt(L, algo_n=md.nq, A=self.ua[li], lda=d, B=S[f'qkvg{i}'], ldb=d, M=T, N=md.nqk, K=d, epi=E['TFX_EPI_BF16'], C=self.qkvg[lkv], ldc=ldq)
@@ -591,7 +610,26 @@ class Plan:
         self._rope_args = getattr(self, '_rope_args', []) + [L[-1][1]]
         L.meta = L.meta or {}
         L.meta[len(L) - 1] = ('hbm', 2 * 2 * T * hd * 2)                # q, k in; q~, k~ out
+        self._laser_fwd(L, i)
         self._k(L, 'tfx_attn_fwd' if (self.cache is None or self.tile_attn) else 'tfx_decode_attn', 'tfx_attn_args', **self._attn_kw(i))
+
+    def _laser_fwd(self, L, i):
+        """LASER (T:979-983): v' = exp(c tanh(v / c)) of layer i's values for its attention - the plan's own rows, or in a decode plan every row of the
+        layer's KV cache after this step's append (into the side cache)"""
+        md, hd = self.md, self.md.hdk
+        if not md.laser:
+            return
+        if self.cache is None:
+            self._k(L, 'tfx_laser_v_fwd', 'tfx_laser_v_args', T=self.T, H=md.heads, v=_p(self.qkvg, self._lkv(i)) + 2 * 2 * hd, ld_v=md.ldq,
+                    vl=self.vl[self._li(i)], ld_vl=hd, c=md.laser)
+            rows = self.T
+        else:
+            ck = self.cache[i]
+            rows = int(ck.shape[0]) * int(ck.shape[1])
+            self._k(L, 'tfx_laser_v_fwd', 'tfx_laser_v_args', T=rows, H=md.heads, v=ck.data_ptr() + 2 * hd, ld_v=2 * hd,      # raw v at column hd (byte 2 hd)
+                    vl=self.vlc[i], ld_vl=hd, c=md.laser)
+        L.meta = L.meta or {}
+        L.meta[len(L) - 1] = ('hbm', 2 * rows * hd * 2)                  # v in, v' out
 
     def _clean_q(self, L, t, r):
         """q = W proj of `_clean_flow`: one GEMM over the type's projected token rows"""
@@ -637,6 +675,8 @@ class Plan:
         if self.cache is not None:
             ck = self.cache[i]
             kw.update(k=ck.data_ptr(), v=ck.data_ptr() + 2 * hd, ld_k=2 * hd, ld_v=2 * hd, n_kv=int(ck.shape[1]))
+        if md.laser:
+            kw.update(v=self.vl[li] if self.cache is None else self.vlc[i], ld_v=hd, laser=1)
         if bwd:
             dqkvg = self.dqkvg_p[i % len(self.dqkvg_p)]
             kw.update(dout=self.dog, ld_dout=hd, do_eff=self.do_eff, ld_do=hd, delta=self.delta,
@@ -856,6 +896,12 @@ class Plan:
                 self._rope_args = getattr(self, '_rope_args', []) + [L[-1][1]]
                 L.meta = L.meta or {}
                 L.meta[len(L) - 1] = ('hbm', 3 * 2 * T * hd * 2)                # q, k (raw) in; d q~, d k~ in; d q, d k out
+            if md.laser:                # d v' -> d v in place, before the dX and weight-gradient GEMMs read the [dq | dk | dv | dgate] rows (T:979-983 backwards)
+                dv = dqkvg.data_ptr() + 2 * 2 * hd
+                self._k(L, 'tfx_laser_v_bwd', 'tfx_laser_v_args', T=T, H=H, v=_p(self.qkvg, i) + 2 * 2 * hd, ld_v=ldq, c=md.laser,
+                        dvl=dv, ld_dvl=ldq, dv=dv, ld_dv=ldq)
+                L.meta = L.meta or {}
+                L.meta[len(L) - 1] = ('hbm', 3 * T * hd * 2)                  # v, d v' in; d v out
             self._nt(L, algo_k=md.nq, A=dqkvg, lda=ldq, B=S[f'qkvg_t{i}'], ldb=ldq, M=T, N=d, K=ldq, epi=E['TFX_EPI_BF16'], C=self.du, ldc=d)
             # (pull form: the gradient a U-Net skip hands to this layer's input joins here, so that G ends up as the TOTAL gradient of xres[i])
             self._k(L, 'tfx_adaln_pre_bwd', 'tfx_adaln_pre_args', T=T, d=d, x=x_a, tok_inst=self.tok_inst, table=ta, ld_table=nt3,

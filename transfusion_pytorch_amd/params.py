@@ -39,6 +39,7 @@ class ModelDims:
     pos_types: tuple = ()                 # modality types whose tokens get an additive axial positional embedding (T:1384-1403): rows computed by the host MLP
     ext_types: tuple = ()                 # modality types whose latent <-> model maps are user modules (`pre_post_transformer_enc_dec`, T:1451-1494):
                                           # their token rows come in from / their embedding rows go out to PyTorch; no projection parameters here
+    laser: float = 0.                     # LASER attention (Transformer(attn_laser=True), T:979-983, T:1019-1022): the softclamp value c of v' = exp(c tanh(v / c)); 0 = off
 
     @property
     def num_modalities(self): return len(self.dim_latents)

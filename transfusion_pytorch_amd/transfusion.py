@@ -151,11 +151,17 @@ class Transformer:
     def __init__(self, dim, *, depth, dim_head=64, heads=8, dropout=0., ff_expansion_factor=4, attn_kwargs: dict = dict(),
                  ff_kwargs: dict = dict(), attn_laser=False, unet_skips=True, use_flex_attn=False, qk_rmsnorm=True, use_value_residual=False):
         # use_flex_attn only selects the reference's attention BACKEND (same scores, same mask, T:998-1027): accepted, the native kernel runs
-        unsupported = dict(dropout=dropout != 0., attn_kwargs=bool(attn_kwargs), ff_kwargs=bool(ff_kwargs), attn_laser=attn_laser,
+        # attn_laser (T:979-983, T:1019-1022) runs natively; of the attention's keyword arguments only its softclamp value (T:866) is taken
+        attn_kwargs = dict(attn_kwargs)
+        laser_c = attn_kwargs.pop('laser_softclamp_value', 15.)
+        unsupported = dict(dropout=dropout != 0., attn_kwargs=bool(attn_kwargs), ff_kwargs=bool(ff_kwargs),
                            unet_skips=not unet_skips, qk_rmsnorm=not qk_rmsnorm, use_value_residual=use_value_residual)
         bad = [k for k, v in unsupported.items() if v]
         if bad:
             raise NotImplementedError(f'Transformer options not supported by the native MI355X path: {bad}')
+        if not (isinstance(laser_c, (int, float)) and laser_c > 0):
+            raise ValueError(f'laser_softclamp_value must be a positive number, got {laser_c!r}')
+        self.attn_laser, self.laser_softclamp_value = bool(attn_laser), float(laser_c)
         if dim_head > 64 or dim_head % 2 or dim_head < 2:
             raise NotImplementedError('the native attention kernels hold 64 columns per head: dim_head must be even and <= 64 '
                                       '(smaller heads run zero-padded)')
@@ -301,6 +307,7 @@ class Transfusion(nn.Module):
 
         self.md = ModelDims(num_text_tokens=num_text_tokens, dim=dim, depth=transformer.depth, heads=transformer.heads,
                             dim_head=transformer.dim_head, dim_latents=tuple(self.dim_latents), ff_expansion_factor=transformer.ff_expansion_factor, model_output_clean=bool(model_output_clean), clean_eps=float(eps),
+                            laser=transformer.laser_softclamp_value if transformer.attn_laser else 0.,
                             pos_types=tuple(t for t, f in enumerate(self.add_pos_emb) if f), ext_types=tuple(sorted(ext_modules)))
         self.store = ParamStore(self.md, self)
         if ext_modules:       # the reference's attribute names: latent_to_model_projs[t] / model_to_latent_projs[t] ARE the user's modules (T:1493-1494)
