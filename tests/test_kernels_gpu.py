@@ -612,7 +612,22 @@ def test_attention_softcap_plan_from_qk_norm_bound(gscale, want_mode):
 def test_attention_fwd_against_kv_cache(b, h, lq, n_kv, entry):
     """decode-time call (engine.Plan(cache=...)): `lq` new query rows per sample against keys / values that live in a LONGER per-sample
     cache buffer (`n_kv` > n rows, token-major [b, n_kv, 2 * h * 64] = k~ | v), each query row with its own visible length `kv_end`
-    (own prefix + the block being decoded; rows of finished samples see a short prefix).  Reference: masked softmax in fp32."""
+    (own prefix + the block being decoded; rows of finished samples see a short prefix).  Reference: masked softmax in fp32; global and
+    per-row error (tests/_attn_cases.py row_err)."""
+    _attn_fwd_vs_cache(b, h, lq, n_kv, entry)
+
+
+# flow-decode steps of 7 x 7 / 14 x 14 / 300-token blocks (tfx_decode_attn hands n > 2 rows to the same forward kernel: tfx_attn_fwd only), a long cache
+@pytest.mark.parametrize('entry,b,h,lq,n_kv', [('tfx_attn_fwd', 3, 2, 49, 1100), ('tfx_attn_fwd', 3, 2, 196, 2100), ('tfx_attn_fwd', 3, 1, 300, 4100),
+                                               ('tfx_attn_fwd', 3, 2, 2, 4100), ('tfx_decode_attn', 3, 2, 2, 4100)])
+def test_attention_fwd_against_kv_cache_long_blocks(entry, b, h, lq, n_kv):
+    """test_attention_fwd_against_kv_cache with block-sized query steps: sample 1's largest kv_end sits on an inner row of each query tile (a text
+    row next to the block), not on the tile's last row"""
+    _attn_fwd_vs_cache(b, h, lq, n_kv, entry)
+
+
+def _attn_fwd_vs_cache(b, h, lq, n_kv, entry):
+    from _attn_cases import ROW_TOL, row_err
     torch.manual_seed(11)
     HD = h * 64
     T = b * lq
@@ -624,6 +639,9 @@ def test_attention_fwd_against_kv_cache(b, h, lq, n_kv, entry):
     kv_end = torch.stack([torch.randint(1, n_kv + 1, (1,), generator=g).expand(lq) for _ in range(b)]).clone()
     if b > 2:                                                     # rows of one sample with DIFFERENT visible lengths (a text row next to a block, mixed decode steps)
         kv_end[1] = torch.randint(1, n_kv + 1, (lq,), generator=g)
+    if lq >= 49:                                                  # a block's rows see prefix + block; inner rows of every query tile see 61 keys more
+        kv_end[1] = n_kv // 2
+        kv_end[1, 7::128] = n_kv // 2 + 61
     kv_end[0] = n_kv                                              # a full cache
     kv_end[-1] = 1                                                # a single visible key
     kv_end = kv_end.to(torch.int32).to(DEV)
@@ -644,6 +662,9 @@ def test_attention_fwd_against_kv_cache(b, h, lq, n_kv, entry):
     check(f'attn fwd vs cache b{b} h{h} lq{lq} n_kv{n_kv}', out.float().reshape(b, lq, h, 64).transpose(1, 2), ref, 8e-3)
     ref_lse = torch.logsumexp(sim, dim=-1)
     assert (lse - ref_lse).abs().max() <= 2e-2
+    er = row_err(out.float().reshape(b, lq, h, 64).transpose(1, 2), ref).max().item()
+    print(f'  worst row: rel err {er:.3e} (tol {ROW_TOL["out"]})')
+    assert er <= ROW_TOL['out']
 
 
 # ---------------------------------------------------------------------------------------------- token-wise
