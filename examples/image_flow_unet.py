@@ -5,6 +5,7 @@ for the velocity-consistency term, `generate_modality_only` for samples.  There 
 strokes per image); everything else is the reference script with the import changed.
 
     python examples/image_flow_unet.py --steps 300
+    python examples/image_flow_unet.py --steps 300 --muon      # train_image_only.py:90: Muon over model.muon_parameters(), Adam over the rest
 """
 from __future__ import annotations
 
@@ -47,7 +48,7 @@ def synthetic_digits(n, seed=0):
     return img[:, None]
 
 
-def main(steps=300, batch_size=32, log=print):
+def main(steps=300, batch_size=32, log=print, muon=False):
     torch.manual_seed(0)
     model = Transfusion(
         num_text_tokens=10, dim_latent=4, channel_first_latent=True, modality_default_shape=(14, 14),
@@ -57,13 +58,20 @@ def main(steps=300, batch_size=32, log=print):
         transformer=dict(dim=64, depth=4, dim_head=32, heads=8)).cuda()
     ema_model = model.create_ema()
     data = synthetic_digits(2048).cuda()
-    opt = torch.optim.Adam(model.parameters(), lr=8e-4)
+    if muon:
+        # one object for both rules: Muon (torch.optim.Muon's arithmetic, grouped HIP kernels) over the attention / feed-forward matrices, the fused
+        # Adam over the rest of the flat buffer, a stock Adam over the conv pair and the positional MLP - all under one global clip at 0.5
+        from transfusion_pytorch_amd.optim import FusedMuon
+        opt = FusedMuon(model, lr=8e-4, muon_lr=5e-3, max_grad_norm=0.5)
+    else:
+        opt = torch.optim.Adam(model.parameters(), lr=8e-4)
     losses = []
     for step in range(1, steps + 1):
         batch = data[torch.randint(0, data.shape[0], (batch_size,), device=data.device)]
         loss = model(batch, velocity_consistency_ema_model=ema_model)
         loss.backward()
-        torch.nn.utils.clip_grad_norm_(model.parameters(), 0.5)
+        if not muon:
+            torch.nn.utils.clip_grad_norm_(model.parameters(), 0.5)
         opt.step()
         opt.zero_grad()
         ema_model.update()
@@ -77,6 +85,7 @@ def main(steps=300, batch_size=32, log=print):
 if __name__ == '__main__':
     ap = argparse.ArgumentParser()
     ap.add_argument('--steps', type=int, default=300)
+    ap.add_argument('--muon', action='store_true', help='optim.FusedMuon instead of torch.optim.Adam')
     a = ap.parse_args()
-    losses, images = main(steps=a.steps)
+    losses, images = main(steps=a.steps, muon=a.muon)
     print('generated', tuple(images.shape), 'range', float(images.min()), float(images.max()))

@@ -23,6 +23,8 @@
  *   tfx_fourier                  RandomFourierEmbed T:617-635
  *   tfx_ce_* / tfx_mse_*         loss block T:3320-3376
  *   tfx_adam_*                   train_toy.py:55-57 (clip_grad_norm_ + Adam)
+ *   tfx_muon_* / tfx_sumsq_det   the optimizer over Transfusion.muon_parameters() T:1657-1672 (train_image_only.py:90); the rule is
+ *                                torch.optim.Muon's: torch/optim/_muon.py:24-92 (Newton-Schulz, lr adjustment), 258-293 (momentum, update)
  */
 #ifndef TFX_H
 #define TFX_H
@@ -469,8 +471,73 @@ typedef struct {
   float* p; const float* g; float* m; float* v; int64_t n;
   float lr, beta1, beta2, eps, weight_decay, max_norm, grad_scale;
   int32_t step; const float* sumsq;
+  /* grown at the end (zero / NULL = the behaviour before): DEVICE table of `nskip` sorted, disjoint [start, end) element ranges (2 nskip int64) the
+   * kernel leaves untouched - p, m and v of the matrices another rule updates (tfx_muon_*).  Starts and ends are multiples of 4, the elements of one
+   * thread (the flat buffer's segments are padded to 4): a group is skipped whole or not at all, and the arithmetic of every other element is the
+   * kernel's own.  sumsq still covers the whole buffer. */
+  const int64_t* skip; int32_t nskip;
 } tfx_adam_args;
 int tfx_adam_step(const tfx_adam_args* a, void* stream);
+
+/* ---- Muon (torch/optim/_muon.py) ---------------------------------------------------------------
+ * One optimizer step over ALL matrices of Transfusion.muon_parameters() (T:1657-1672) in a number of launches that does not depend on their count:
+ *   tfx_sumsq_det (2 launches) -> tfx_muon_prep -> tfx_muon_norm -> ns_steps x { gram, poly, update: tfx_muon_gemm } -> tfx_muon_apply -> tfx_adam_step(skip)
+ * No atomics, no sum whose order varies: the path is run-to-run bit-deterministic.
+ *
+ * Orientation and padding (_muon.py:50-52): a rows x cols parameter is iterated as X, m x n with m = min, n = max (transposed when rows > cols).  The bf16
+ * workspace keeps X (m_pad x n_pad) AND X^T (n_pad x m_pad), zero-padded to multiples of the 128 x 128 tile; zero rows / columns stay zero under the
+ * iteration.  The "straight" copy has the parameter's own orientation (X when rows <= cols, else X^T), the "transposed" copy the other one. */
+enum { TFX_SUMSQ_DET_PARTIALS = 1024 };
+/* sumsq[0] = sum of g[i]^2 (overwritten, not accumulated) in a fixed order; partials: TFX_SUMSQ_DET_PARTIALS floats of scratch.  The clip norm of the Muon step
+ * (clip_grad_norm_, train_toy.py:55): tfx_sumsq's atomic sum changes in the last bits from run to run */
+int tfx_sumsq_det(const float* g, int64_t n, float* partials, float* sumsq, void* stream);
+/* host only: what a rows x cols parameter becomes - flip (rows > cols), m <= n, their padded sizes, output tiles of its gram / poly product (m_pad x m_pad)
+ * and of its update product (n_pad x m_pad), 64 x 64 blocks of tfx_muon_prep / _apply.  Any output pointer may be NULL. */
+int tfx_muon_plan(int32_t rows, int32_t cols, int32_t* flip, int32_t* m, int32_t* n, int32_t* m_pad, int32_t* n_pad, int32_t* gram_tiles,
+                  int32_t* update_tiles, int32_t* prep_blocks);
+/* host only: kernel launches of one optimizer step (the chain above) for ns_steps iterations over nmat matrices - the same for every nmat >= 1 */
+int tfx_muon_step_launches(int32_t ns_steps, int32_t nmat);
+typedef struct {
+  int64_t off;                 /* element offset of the rows x cols fp32 matrix in the flat buffers (parameters, gradients, momentum) */
+  int64_t s_off, t_off;        /* element offsets in the bf16 workspace of the straight copy (rows x ld_s) and the transposed copy (cols x ld_t) */
+  int32_t rows, cols, ld_s, ld_t;
+  int32_t blk0;                /* first 64 x 64 block of this matrix in the prep / apply grid (= its first entry in `partials`) */
+  float lr_ratio;              /* _adjust_lr's ratio for this shape (_muon.py:65-77) */
+} tfx_muon_mat;
+/* momentum, Nesterov mix, bf16 X0 in both orientations, per-block sums of squares (_muon.py:280-282): block b works on matrix blk_mat[b].
+ * g is scaled by grad_scale x the clip coefficient of tfx_adam_step (sumsq, max_norm) before it enters the momentum.  X0 is stored UNNORMALISED; tfx_muon_norm
+ * turns the partials into 1 / max(|u|, eps) and its square per matrix, which the first gram product and the first update carry (scale_acc / scale_z).
+ * Supported magnitudes: the first gram product sums u_i u_j in fp32 BEFORE 1 / |u|^2 is applied, so the products square the range: elements of u
+ * below about 1e-19 in magnitude underflow there (contribute zero) and elements above about 1e19 overflow, where torch - which divides first - is
+ * exact.  eps bounds 1 / |u|^2 (1e14 at the default 1e-7), so small inputs give zeros, never inf / NaN.  Gradients behind a global clip are far
+ * inside the range. */
+typedef struct {
+  const tfx_muon_mat* mats; const int32_t* blk_mat; int32_t nmat, nblk;
+  const float* g; float* buf; tfx_bf16* ws; float* partials;
+  const float* sumsq; float max_norm, grad_scale, momentum; int32_t nesterov;
+} tfx_muon_prep_args;
+int tfx_muon_prep(const tfx_muon_prep_args* a, void* stream);
+/* inv[2 i] = 1 / max(sqrt(sum of matrix i's partials), eps), inv[2 i + 1] = its square   (_muon.py:54) */
+int tfx_muon_norm(const tfx_muon_mat* mats, int32_t nmat, const float* partials, float eps, float* inv, void* stream);
+/* one problem of a grouped launch: C (M x N) = alpha scale_z Z + beta scale_acc P . Q^T, P: M x K, Q: N x K, all bf16, row-major, K contiguous, fp32
+ * accumulation, one rounding of the result; Ct (optional) also receives the transposed result (N x M).  M, N multiples of 128, K of 64, leading dimensions of 8,
+ * pointers 16-byte aligned: the kernel has no bounds predicate.  Z, Ct, scale_z, scale_acc may be NULL (no addend / no second copy / 1); the scales are DEVICE floats.
+ * The three Newton-Schulz products (_muon.py:56-62): gram P = Q = X; poly P = Q = Z = A (A symmetric: A . A^T = A @ A); update P = Z = X^T, Q = B. */
+typedef struct {
+  const tfx_bf16* P; const tfx_bf16* Q; const tfx_bf16* Z; tfx_bf16* C; tfx_bf16* Ct;
+  const float* scale_z; const float* scale_acc;
+  int32_t M, N, K, ldp, ldq, ldz, ldc, ldct;
+  int32_t tile0;               /* first tile of this problem in the launch's grid; its (M / 128) x (N / 128) tiles follow row-major */
+  int32_t reserved;
+} tfx_muon_gemm_problem;
+/* table, tile_prob (problem index of every tile): DEVICE arrays; alpha, beta apply to every problem of the launch */
+int tfx_muon_gemm(const tfx_muon_gemm_problem* table, const int32_t* tile_prob, int32_t ntiles, float alpha, float beta, void* stream);
+/* p = p decay - lr lr_ratio O   (_muon.py:288-289; decay = 1 - lr weight_decay), O = the straight copy of the final iterate in `ws` */
+typedef struct {
+  const tfx_muon_mat* mats; const int32_t* blk_mat; int32_t nmat, nblk;
+  float* p; const tfx_bf16* ws; float lr, decay;
+} tfx_muon_apply_args;
+int tfx_muon_apply(const tfx_muon_apply_args* a, void* stream);
 /* exponential moving average of a flat parameter buffer: ema = decay * ema + (1 - decay) * online   (ema_pytorch EMA.update, used by
  * Transfusion.create_ema T:1681-1699) */
 int tfx_ema_update(float* ema, const float* online, int64_t n, float decay, void* stream);

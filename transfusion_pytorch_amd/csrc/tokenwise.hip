@@ -1961,6 +1961,11 @@ __global__ __launch_bounds__(256) void adam_k(tfx_adam_args p, float step_size, 
   // 4 parameters per thread (16-B accesses); bias corrections are computed once on the host side of the launch
   const long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
   if (i >= p.n) return;
+  if (p.nskip > 0) {                                     // ranges another rule updates (tfx.h): whole groups of 4, so a thread's elements are all in or all out
+    int lo = 0, hi = p.nskip;                            // first range that ends behind i
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (p.skip[2 * mid + 1] > i) hi = mid; else lo = mid + 1; }
+    if (lo < p.nskip && p.skip[2 * lo] <= i) return;
+  }
   float coef = p.grad_scale;
   if (p.max_norm > 0.f) {
     float norm = sqrtf(p.sumsq[0]) * p.grad_scale;
@@ -2307,6 +2312,7 @@ int tfx_sumsq(const float* g, int64_t n, float* out, void* s) {
 int tfx_adam_step(const tfx_adam_args* a, void* s) {
   if (a->n == 0) return 0;
   if (((uintptr_t)a->p | (uintptr_t)a->g | (uintptr_t)a->m | (uintptr_t)a->v) & 15) return -1;
+  if (a->nskip < 0 || (a->nskip > 0 && !a->skip)) return -1;
   const double bc1 = 1.0 - pow((double)a->beta1, (double)a->step), bc2 = 1.0 - pow((double)a->beta2, (double)a->step);
   const long long nthr = (a->n + 3) / 4;
   hipLaunchKernelGGL(adam_k, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, ST(s), *a, (float)(a->lr / bc1), (float)(1.0 / sqrt(bc2))); RET();
@@ -2349,6 +2355,6 @@ int tfx_laser_v_bwd(const tfx_laser_v_args* a, void* s) {
   if (nch >= (1ll << 31)) return -4;
   hipLaunchKernelGGL(laser_v_bwd_k, dim3((unsigned)((nch + 255) / 256)), dim3(256), 0, ST(s), *a, (unsigned)nch); RET();
 }
-const char* tfx_version(void) { return "tfx-hip gfx950 r2-laser"; }
+const char* tfx_version(void) { return "tfx-hip gfx950 r3-laser-muon"; }
 
 }  // extern "C"

@@ -139,6 +139,15 @@ class GradReducer:
 
 
 class FusedAdam:
+    """global-norm clip + Adam over the flat fp32 buffer as one launch (train_toy.py:55-57), the data-parallel gradient exchange in front of it, a stock
+    Adam under the same clip coefficient for `model.external_parameters()`.  Every scalar (`lr`, `betas`, ...) is re-read at each step.
+
+    `deterministic_norm` (class default False, True in FusedMuon; may be set on an instance): take the clip norm as a fixed-order sum (`tfx_sumsq_det`)
+    instead of `tfx_sumsq`'s atomic one, whose last bits - and with them the clip coefficient of every element - change from run to run.  False is the
+    step FusedAdam always took."""
+
+    deterministic_norm = False
+
     def __init__(self, model, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0., max_grad_norm=None, process_group=None,
                  average_grads=True):
         self.model, self.lr, self.betas, self.eps, self.weight_decay = model, lr, betas, eps, weight_decay
@@ -150,6 +159,7 @@ class FusedAdam:
         self.time_exchange = False      # bench.py: bracket the exchange section of every step with events on the compute stream (`exchange_ms`)
         self._xev = []
         self.m = self.v = self.sumsq = None
+        self._sumsq_partials = None     # scratch of the fixed-order clip norm (`deterministic_norm`)
         self.reducer = None             # set by `overlap_grad_sync`: the exchange then runs in layer groups during the backward
         # parameters that live OUTSIDE the flat buffer: the positional-embedding MLPs and the user's pre / post transformer encoder-decoder
         # modules (PyTorch modules with autograd gradients).  They are few and small: a stock Adam steps them, under the SAME global clip
@@ -240,8 +250,13 @@ class FusedAdam:
         gscale = (1.0 / world) if (self.average and world > 1) else 1.0
         ext_grads = [p.grad for p in self.ext_params if p.grad is not None]
         if max_norm > 0:
-            self.sumsq.zero_()
-            capi.check(capi.lib().tfx_sumsq(ps.grad.data_ptr(), ps.numel, self.sumsq.data_ptr(), stream), 'tfx_sumsq')
+            if self.deterministic_norm:
+                if self._sumsq_partials is None or self._sumsq_partials.device != ps.flat.device:
+                    self._sumsq_partials = torch.zeros(capi.ENUMS['TFX_SUMSQ_DET_PARTIALS'], device=ps.flat.device)
+                capi.check(capi.lib().tfx_sumsq_det(ps.grad.data_ptr(), ps.numel, self._sumsq_partials.data_ptr(), self.sumsq.data_ptr(), stream), 'tfx_sumsq_det')
+            else:
+                self.sumsq.zero_()
+                capi.check(capi.lib().tfx_sumsq(ps.grad.data_ptr(), ps.numel, self.sumsq.data_ptr(), stream), 'tfx_sumsq')
             if ext_grads:
                 self.sumsq += torch.stack([g.float().pow(2).sum() for g in ext_grads]).sum()
         if ext_grads:                                       # same scaling as adam_k: grad_scale * min(1, max_norm / (|g| grad_scale + 1e-6)), on the device
@@ -253,12 +268,18 @@ class FusedAdam:
             for grp in self.ext_opt.param_groups:          # a schedule that sets `opt.lr = ...` (re-read by the fused kernel every step) reaches these too
                 grp['lr'], grp['betas'], grp['eps'], grp['weight_decay'] = self.lr, tuple(self.betas), self.eps, self.weight_decay
             self.ext_opt.step()
+        skip, nskip = self._step_other_rules(ps, stream, max_norm, gscale)
         a = capi.make_args('tfx_adam_args', p=ps.flat, g=ps.grad, m=self.m, v=self.v, n=ps.numel, lr=self.lr, beta1=self.betas[0],
                            beta2=self.betas[1], eps=self.eps, weight_decay=self.weight_decay, max_norm=max_norm,
-                           grad_scale=gscale, step=self.step_count, sumsq=self.sumsq)
+                           grad_scale=gscale, step=self.step_count, sumsq=self.sumsq, skip=skip, nskip=nskip)
         capi.call('tfx_adam_step', a, stream)
         # the master changed behind autograd's back: new weights epoch (shadows rebuilt, kept decode plans dropped)
         ps.mark_dirty()
+
+    def _step_other_rules(self, ps, stream, max_norm, gscale):
+        """hook of subclasses that update part of the flat buffer by another rule, between the clip norm and the Adam launch: returns the device
+        table of element ranges Adam then leaves alone and its length (tfx_adam_args.skip / nskip)"""
+        return None, 0
 
     def zero_grad(self, set_to_none: bool = True):
         ps = self.model.store
@@ -269,3 +290,242 @@ class FusedAdam:
                 p.grad = None
         elif ps.grad is not None:
             ps.grad.zero_()
+
+
+class _MuonTables:
+    """device tables of one FusedMuon over one flat buffer: matrix descriptors, the bf16 workspace, the problem tables of the grouped products"""
+
+
+def _muon_host_tables(segs, adjust_lr_fn=None):
+    """the step's tables as host data (no device needed): matrix descriptors and the problems of the grouped products, with workspace OFFSETS
+    (elements) where the device tables carry pointers.  `segs`: sorted (offset, rows, cols) of the matrices in the flat buffers."""
+    mats, blk_mat, sq_prob, up_prob = [], [], [], []
+    xw = abw = blk = sq_t = up_t = 0
+    for i, (off, rows, cols) in enumerate(segs):
+        pl = FusedMuon.plan(rows, cols)
+        mp, np_ = pl['m_pad'], pl['n_pad']
+        x_off, xt_off = xw, xw + mp * np_
+        xw += 2 * mp * np_
+        a_off, b_off = abw, abw + mp * mp
+        abw += 2 * mp * mp
+        flip = pl['flip']
+        mats.append(dict(off=off, s_off=xt_off if flip else x_off, t_off=x_off if flip else xt_off, rows=rows, cols=cols,
+                         ld_s=mp if flip else np_, ld_t=np_ if flip else mp, blk0=blk, lr_ratio=FusedMuon._lr_ratio(adjust_lr_fn, rows, cols),
+                         x_off=x_off, xt_off=xt_off, a_off=a_off, b_off=b_off, sq_tile0=sq_t, up_tile0=up_t, **pl))
+        blk_mat += [i] * pl['prep_blocks']; blk += pl['prep_blocks']
+        sq_prob += [i] * pl['gram_tiles']; sq_t += pl['gram_tiles']
+        up_prob += [i] * pl['update_tiles']; up_t += pl['update_tiles']
+    return dict(mats=mats, blk_mat=blk_mat, sq_prob=sq_prob, up_prob=up_prob, x_elems=xw, ab_elems=abw)
+
+
+def _muon_device_tables(H, dev):
+    T = _MuonTables()
+    T.H, T.nmat, T.nblk = H, len(H['mats']), len(H['blk_mat'])
+    T.sq_tiles, T.up_tiles = len(H['sq_prob']), len(H['up_prob'])
+    i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=dev)
+    T.blk_mat, T.sq_prob, T.up_prob = i32(H['blk_mat']), i32(H['sq_prob']), i32(H['up_prob'])
+    # zero-filled ONCE: the kernels write zeros (products of zeros) or nothing into the padding
+    T.wsx = [torch.zeros(H['x_elems'], dtype=torch.bfloat16, device=dev) for _ in range(2)]
+    T.wsab = torch.zeros(H['ab_elems'], dtype=torch.bfloat16, device=dev)
+    T.partials = torch.zeros(T.nblk, device=dev)
+    T.inv = torch.zeros(2 * T.nmat, device=dev)
+
+    def upload(struct, rows):
+        S = capi.STRUCTS[struct]
+        names = {f for f, _ in capi.STRUCT_FIELDS[struct]}
+        arr = (S * len(rows))()
+        for a, r in zip(arr, rows):
+            for k, v in r.items():
+                if k in names:
+                    setattr(a, k, v)
+        return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
+
+    T.mats = upload('tfx_muon_mat', H['mats'])
+    x = [w.data_ptr() for w in T.wsx]
+    ab, inv = T.wsab.data_ptr(), T.inv.data_ptr()
+
+    def gram(cur, first):
+        return upload('tfx_muon_gemm_problem', [dict(P=x[cur] + 2 * m['x_off'], Q=x[cur] + 2 * m['x_off'], C=ab + 2 * m['a_off'],
+                                                     scale_acc=inv + 4 * (2 * i + 1) if first else None, M=m['m_pad'], N=m['m_pad'], K=m['n_pad'],
+                                                     ldp=m['n_pad'], ldq=m['n_pad'], ldc=m['m_pad'], tile0=m['sq_tile0']) for i, m in enumerate(H['mats'])])
+
+    def update(cur, first):
+        s = lambda i: inv + 4 * (2 * i) if first else None
+        return upload('tfx_muon_gemm_problem', [dict(P=x[cur] + 2 * m['xt_off'], Z=x[cur] + 2 * m['xt_off'], Q=ab + 2 * m['b_off'],
+                                                     C=x[cur ^ 1] + 2 * m['xt_off'], Ct=x[cur ^ 1] + 2 * m['x_off'], scale_z=s(i), scale_acc=s(i),
+                                                     M=m['n_pad'], N=m['m_pad'], K=m['m_pad'], ldp=m['m_pad'], ldz=m['m_pad'], ldq=m['m_pad'],
+                                                     ldc=m['m_pad'], ldct=m['n_pad'], tile0=m['up_tile0']) for i, m in enumerate(H['mats'])])
+
+    T.gram_first, T.gram = gram(0, True), [gram(0, False), gram(1, False)]
+    T.update_first, T.update = update(0, True), [update(0, False), update(1, False)]
+    T.poly = upload('tfx_muon_gemm_problem', [dict(P=ab + 2 * m['a_off'], Q=ab + 2 * m['a_off'], Z=ab + 2 * m['a_off'], C=ab + 2 * m['b_off'],
+                                                   M=m['m_pad'], N=m['m_pad'], K=m['m_pad'], ldp=m['m_pad'], ldq=m['m_pad'], ldz=m['m_pad'],
+                                                   ldc=m['m_pad'], tile0=m['sq_tile0']) for m in H['mats']])
+    return T
+
+
+def _muon_orthogonalize(T, g, buf, sumsq, max_norm, gscale, momentum, nesterov, eps, coefficients, ns, stream):
+    """momentum + norms + ns Newton-Schulz iterations over all matrices of the tables `T`: 2 + 3 ns launches.  The final iterate is in T.wsx[ns & 1]."""
+    if not 1 <= ns < 100:
+        raise ValueError('ns_steps must be in 1 ... 99')
+    a, b, c = (float(x) for x in coefficients)
+    L = capi.lib()
+    prep = capi.make_args('tfx_muon_prep_args', mats=T.mats, blk_mat=T.blk_mat, nmat=T.nmat, nblk=T.nblk, g=g, buf=buf, ws=T.wsx[0],
+                          partials=T.partials, sumsq=sumsq, max_norm=max_norm, grad_scale=gscale, momentum=float(momentum), nesterov=int(bool(nesterov)))
+    capi.call('tfx_muon_prep', prep, stream)
+    capi.check(L.tfx_muon_norm(T.mats.data_ptr(), T.nmat, T.partials.data_ptr(), float(eps), T.inv.data_ptr(), stream), 'tfx_muon_norm')
+    gemm = lambda tab, prob, tiles, al, be: capi.check(L.tfx_muon_gemm(tab.data_ptr(), prob.data_ptr(), tiles, al, be, stream), 'tfx_muon_gemm')
+    for t in range(ns):
+        cur = t & 1
+        gemm(T.gram_first if t == 0 else T.gram[cur], T.sq_prob, T.sq_tiles, 0., 1.)
+        gemm(T.poly, T.sq_prob, T.sq_tiles, b, c)
+        gemm(T.update_first if t == 0 else T.update[cur], T.up_prob, T.up_tiles, a, 1.)
+
+
+def newton_schulz(mats, ns_coefficients=(3.4445, -4.775, 2.0315), ns_steps=5, eps=1e-7):
+    """`torch.optim._muon._zeropower_via_newtonschulz` (_muon.py:24-62) of a LIST of 2-D fp32 tensors on the MI355X through the grouped kernels of
+    FusedMuon - all matrices per launch.  Returns the bf16 results in the inputs' own orientation."""
+    dev = mats[0].device
+    segs, off = [], 0
+    for m in mats:
+        if m.ndim != 2 or m.device != dev or not m.is_cuda:
+            raise ValueError('newton_schulz takes 2-D tensors on one GPU')
+        segs.append((off, m.shape[0], m.shape[1])); off += -(-m.numel() // 4) * 4
+    g = torch.zeros(off, device=dev)
+    for (o, r, c), m in zip(segs, mats):
+        g[o:o + r * c].copy_(m.reshape(-1))
+    T = _muon_device_tables(_muon_host_tables(segs), dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    # momentum 0 without the Nesterov mix: u = g
+    _muon_orthogonalize(T, g, torch.zeros_like(g), None, 0., 1., 0., False, eps, ns_coefficients, int(ns_steps), stream)
+    ws = T.wsx[int(ns_steps) & 1]
+    return [ws[d['s_off']:d['s_off'] + d['rows'] * d['ld_s']].view(d['rows'], d['ld_s'])[:, :d['cols']].clone() for d in T.H['mats']]
+
+
+class FusedMuon(FusedAdam):
+    """Muon over `model.muon_parameters()` (train_image_only.py:90: `MuonAdamAtan2(model.muon_parameters(), model.parameters(), ...)`), the fused
+    Adam over everything else - one optimizer object, one `step()`.  Gradient exchange, `no_sync`, `overlap_grad_sync`, external parameters, the
+    device-side global clip and `zero_grad` are FusedAdam's; the clip coefficient is the same for both shares.
+
+    The Muon rule is `torch.optim.Muon`'s (torch/optim/_muon.py), with its keyword names and defaults - prefixed `muon_` where Adam has the name:
+        buf = lerp(buf, g, 1 - momentum);  u = lerp(g, buf, momentum) if nesterov else buf
+        X = u / max(|u|_F, muon_eps), transposed if rows > cols;  ns_steps x { A = X X^T; B = b A + c A A; X = a X + B X }  (bf16 operands, fp32 sums)
+        p = p (1 - muon_lr muon_weight_decay) - adjust_lr(muon_lr, shape) X
+    All matrices go through every stage together (csrc/muon.hip): the number of launches of a step does not depend on the depth, and nothing in
+    the path is an atomic or an order-varying sum, so replicas that orthogonalise the same all-reduced gradient stay bit-identical.
+    The momentum of a matrix lives in the Adam first-moment buffer at the matrix's own range (`momentum_buffer(p)`); Adam skips those ranges.
+    Every scalar (`lr`, `muon_lr`, `momentum`, ...) is re-read at each step."""
+
+    deterministic_norm = True
+
+    def __init__(self, model, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0., max_grad_norm=None, process_group=None, average_grads=True, *,
+                 muon_params=None, muon_lr=1e-3, muon_weight_decay=0.1, momentum=0.95, nesterov=True, ns_coefficients=(3.4445, -4.775, 2.0315),
+                 ns_steps=5, muon_eps=1e-7, adjust_lr_fn=None):
+        super().__init__(model, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm, process_group=process_group,
+                         average_grads=average_grads)
+        self.muon_params = list(model.muon_parameters() if muon_params is None else muon_params)
+        if not self.muon_params:
+            raise ValueError('FusedMuon needs at least one matrix (use FusedAdam otherwise)')
+        for p in self.muon_params:
+            if p.ndim != 2:
+                raise ValueError(f'Muon parameters must be 2-D matrices, got shape {tuple(p.shape)}')
+        self.muon_lr, self.muon_weight_decay, self.momentum, self.nesterov = muon_lr, muon_weight_decay, momentum, nesterov
+        self.ns_coefficients, self.ns_steps, self.muon_eps, self.adjust_lr_fn = ns_coefficients, ns_steps, muon_eps, adjust_lr_fn
+        self._tab = None
+
+    # ------------------------------------------------------------------ host tables
+    def muon_segments(self):
+        """sorted (offset, rows, cols) of the Muon matrices in the flat buffer (every one must be a contiguous fp32 view into it)"""
+        ps = self.model.store
+        base, segs = ps.flat.data_ptr(), []
+        ps.params_version()                                           # re-points parameters whose .data was re-assigned
+        for p in self.muon_params:
+            off = p.data_ptr() - base
+            if p.dtype != torch.float32 or not p.is_contiguous() or off < 0 or off % 4 or off // 4 + p.numel() > ps.numel:
+                raise ValueError('a Muon parameter must be a contiguous fp32 view into the model\'s flat parameter buffer')
+            segs.append((off // 4, p.shape[0], p.shape[1]))
+        segs.sort()
+        for (o0, r0, c0), (o1, _, _) in zip(segs, segs[1:]):
+            if o0 + r0 * c0 > o1:
+                raise ValueError('Muon parameters overlap')
+        return segs
+
+    @staticmethod
+    def _lr_ratio(adjust_lr_fn, rows, cols):                          # _muon.py:65-77
+        if adjust_lr_fn is None or adjust_lr_fn == 'original':
+            return max(1., rows / cols) ** 0.5
+        if adjust_lr_fn == 'match_rms_adamw':
+            return 0.2 * max(rows, cols) ** 0.5
+        raise ValueError(f"adjust_lr_fn must be None, 'original' or 'match_rms_adamw', got {adjust_lr_fn!r}")
+
+    @staticmethod
+    def plan(rows, cols):
+        """tfx_muon_plan (host only): dict of flip, m, n, m_pad, n_pad, gram_tiles, update_tiles, prep_blocks for a rows x cols parameter"""
+        import ctypes
+        keys = ('flip', 'm', 'n', 'm_pad', 'n_pad', 'gram_tiles', 'update_tiles', 'prep_blocks')
+        out = [ctypes.c_int32() for _ in keys]
+        capi.check(capi.lib().tfx_muon_plan(int(rows), int(cols), *[ctypes.byref(o) for o in out]), 'tfx_muon_plan')
+        return {k: o.value for k, o in zip(keys, out)}
+
+    def launches_per_step(self):
+        """kernel launches of one step's optimizer share (clip norm, Muon chain, Adam) - independent of the number of matrices"""
+        return capi.lib().tfx_muon_step_launches(int(self.ns_steps), len(self.muon_params))
+
+    def skip_ranges(self):
+        """sorted [start, end) element ranges of the flat buffer that Muon owns and Adam skips (adjacent matrices merged)"""
+        out = []
+        for off, r, c in self.muon_segments():
+            if out and out[-1][1] == off:
+                out[-1][1] = off + r * c
+            else:
+                out.append([off, off + r * c])
+        return [tuple(x) for x in out]
+
+    def adam_skip_table(self):
+        """`skip_ranges()` as tfx_adam_args.skip takes them: whole groups of 4 elements.  Segments of the flat buffer start at multiples of 4 and are
+        padded to one, so an end rounded up covers padding only"""
+        skip = []
+        for a, b in self.skip_ranges():
+            if a % 4:
+                raise ValueError('a Muon parameter must start at a multiple of 4 elements of the flat buffer')
+            b = -(-b // 4) * 4
+            if skip and skip[-1][1] >= a:
+                skip[-1][1] = b
+            else:
+                skip.append([a, b])
+        return [tuple(x) for x in skip]
+
+    def host_tables(self):
+        """the step's tables as host data (no device needed): matrix descriptors and the problems of the grouped products, with workspace OFFSETS
+        (elements) where the device tables carry pointers"""
+        return _muon_host_tables(self.muon_segments(), self.adjust_lr_fn)
+
+    def _tables(self, ps):
+        # (the parameters are views into `flat`: they move only with it - `reflatten` - and a re-assigned `.data` is copied back and re-pointed by
+        #  the forward's `params_version()`; the fused kernels read the flat buffer either way, as FusedAdam's do)
+        key = (ps.flat.data_ptr(), str(ps.flat.device), self.adjust_lr_fn)
+        if self._tab is None or self._tab.key != key:
+            self._tab = _muon_device_tables(self.host_tables(), ps.flat.device)
+            self._tab.key = key
+            skip = self.adam_skip_table()
+            self._tab.nskip = len(skip)
+            self._tab.skip = torch.tensor(skip, dtype=torch.int64, device=ps.flat.device).reshape(-1)
+        return self._tab
+
+    def momentum_buffer(self, p):
+        """Muon's momentum of matrix `p`: a view of the first-moment buffer at the matrix's range (None before the first step)"""
+        if self.m is None:
+            return None
+        off = (p.data_ptr() - self.model.store.flat.data_ptr()) // 4
+        return self.m[off:off + p.numel()].view(p.shape)
+
+    # ------------------------------------------------------------------ the step
+    def _step_other_rules(self, ps, stream, max_norm, gscale):
+        ns = int(self.ns_steps)
+        T = self._tables(ps)
+        _muon_orthogonalize(T, ps.grad, self.m, self.sumsq, max_norm, gscale, self.momentum, self.nesterov, self.muon_eps, self.ns_coefficients, ns, stream)
+        lr, wd = float(self.muon_lr), float(self.muon_weight_decay)
+        app = capi.make_args('tfx_muon_apply_args', mats=T.mats, blk_mat=T.blk_mat, nmat=T.nmat, nblk=T.nblk, p=ps.flat, ws=T.wsx[ns & 1],
+                             lr=lr, decay=1. - lr * wd)
+        capi.call('tfx_muon_apply', app, stream)
+        return T.skip, T.nskip

@@ -373,6 +373,16 @@ class Transfusion(nn.Module):
     def parameters_without_encoder_decoder(self):                     # T:1650-1655
         return set(self.parameters()) - set(self.modality_encoder.parameters()) - set(self.modality_decoder.parameters())
 
+    def muon_parameters(self):                                        # T:1657-1672
+        """the matrices the reference hands to Muon (train_image_only.py:90), in its order: per layer the attention's `to_v` and `to_out` weights
+        and the feed-forward's two weights.  They are views into the flat parameter buffer (`to_v` is the middle slice of the fused
+        to_qk | to_v | to_gates block) - the very objects `named_parameters()` yields, so `optim.FusedMuon` and `torch.optim.Muon` both take them.
+        The reference walks `self.modules()` and so also collects `Attention` / `FeedForward` instances inside user encoder / decoder modules;
+        native user modules are plain PyTorch modules that cannot contain those classes, so nothing of theirs is ever in this list."""
+        prm = self.store.params
+        return [prm[f'transformer.layers.{i}.{n}'] for i in range(self.md.depth)
+                for n in ('1.fn.to_v.0.weight', '1.fn.to_out.1.weight', '2.fn.net.0.weight', '2.fn.net.3.weight')]
+
     def get_modality_info(self, modality_type=None):                  # T:1547-1590
         """per-type record with the reference's field names.  `latent_to_model` / `model_to_latent` are the user's modules for
         `pre_post_transformer_enc_dec` types and None otherwise (the native projections live in the flat parameter buffer: `model_to_latent()`)"""
