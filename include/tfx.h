@@ -397,6 +397,19 @@ typedef struct {
   const float* recon_w; const int32_t* recon_inst; const float* recon_time; int32_t recon_mode;
 } tfx_mse_args;
 int tfx_mse_fwd_bwd(const tfx_mse_args* a, void* stream);
+/* fused cosine loss forward + backward over bf16 rows (the Self-Flow representation loss, default_rep_loss_fn: 1 - cosine_similarity(pred, target, -1).mean()):
+ *   c_t = <x_t, y_t> / (max(|x_t|, 1e-8) max(|y_t|, 1e-8)),   acc[0] += sum of c_t over the rows that count (the host forms 1 - acc / N),
+ *   dpred_t = -grad_scale (y_t / (|x_t| |y_t|) - c_t x_t / |x_t|^2)   in bf16, zero for the rows that do not count.
+ * The rows are (b, n_pad) token rows of a plan: row t counts when t % n_pad < n_valid (n_pad == 0: every row).  fp32 arithmetic, one pass: each operand is read
+ * once, dpred written once.  d a multiple of 64, <= 2048; leading dimensions multiples of 8. */
+typedef struct {
+  int32_t T, d; const tfx_bf16* pred; int32_t ld_pred; const tfx_bf16* target; int32_t ld_target;
+  int32_t n_pad, n_valid;
+  float grad_scale;                           /* weight / (number of rows that count) */
+  tfx_bf16* dpred; int32_t ld_d;
+  float* acc;
+} tfx_cosine_args;
+int tfx_cosine_fwd_bwd(const tfx_cosine_args* a, void* stream);
 /* model_output_clean: pred[r][c] <- (pred[r][c] - noised[r][c]) / max(1 - t_r, clean_eps), noised = eps ? x*t + eps*(1-t) : x,
  * t_r = inst_time[row_inst[r]]   (get_model_output_to_flow_fn, MP:100-126) */
 int tfx_output_to_flow(float* pred, const float* x, const float* eps, const int32_t* row_inst, const float* inst_time,
@@ -562,7 +575,7 @@ enum { TFX_OP_GEMM_NT = 0, TFX_OP_GEMM_TN = 1, TFX_OP_ATTN_FWD = 2, TFX_OP_ATTN_
        TFX_OP_ADALN_POST_FWD = 6, TFX_OP_ADALN_POST_BWD = 7, TFX_OP_QK_NORM_ROPE_FWD = 8, TFX_OP_QK_NORM_ROPE_BWD = 9, TFX_OP_ATTNRES_FWD = 10,
        TFX_OP_ATTNRES_BWD = 11, TFX_OP_RMSNORM_FWD = 12, TFX_OP_RMSNORM_BWD = 13, TFX_OP_EMBED_FWD = 14, TFX_OP_EMBED_BWD = 15,
        TFX_OP_NOISE_MIX = 16, TFX_OP_FOURIER = 17, TFX_OP_CE_FWD_BWD = 18, TFX_OP_MSE_FWD_BWD = 19, TFX_OP_CAST_ROWS = 20, TFX_OP_CAST_ROWS_T = 21,
-       TFX_OP_ADAM_STEP = 22, TFX_OP_DECODE_ATTN = 23, TFX_OP_LASER_V_FWD = 24, TFX_OP_LASER_V_BWD = 25,
+       TFX_OP_ADAM_STEP = 22, TFX_OP_DECODE_ATTN = 23, TFX_OP_LASER_V_FWD = 24, TFX_OP_LASER_V_BWD = 25, TFX_OP_COSINE_FWD_BWD = 26,
        /* positional entry points (args = tfx_raw_args) */
        TFX_OP_OUTPUT_TO_FLOW = 32, TFX_OP_GATHER_F32 = 33, TFX_OP_ONEHOT_BF16 = 34, TFX_OP_SCATTER_ROWS_BF16 = 35, TFX_OP_F32_TO_BF16 = 36,
        TFX_OP_SILU_BWD = 37, TFX_OP_COLSUM_BF16 = 38, TFX_OP_COLSUM_F32 = 39, TFX_OP_ADD_BF16 = 40, TFX_OP_SCALE_BF16_DEV = 41, TFX_OP_CAST_BLOCK_BF16 = 42, TFX_OP_SCALE_BF16_COPY = 43, TFX_OP_ADALN_POST_PRE_FWD = 44, TFX_OP_LAYER_END_FWD = 45,

@@ -16,5 +16,6 @@ from .transfusion import (
 )
 
 from .ema import EMA
+from .self_flow import SelfMaskedRepTraining, default_rep_loss_fn
 
-__all__ = ['Transfusion', 'Transformer', 'LossBreakdown', 'print_modality_sample', 'create_dataloader', 'EMA']
+__all__ = ['Transfusion', 'Transformer', 'LossBreakdown', 'print_modality_sample', 'create_dataloader', 'EMA', 'SelfMaskedRepTraining', 'default_rep_loss_fn']

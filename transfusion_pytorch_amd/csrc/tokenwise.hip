@@ -1705,6 +1705,50 @@ __global__ __launch_bounds__(256) void mse_k(tfx_mse_args p) {
   if (threadIdx.x == 0) { float a = 0.f; for (int i = 0; i < WAVES; i++) a += sacc[i]; atomicAdd(p.acc, a); }
 }
 
+// fused cosine loss, forward + backward (Self-Flow representation loss): one wave per row, both operands read once, d pred written once.
+//   c = <x, y> / (max(|x|, eps) max(|y|, eps)), eps = 1e-8 (F.cosine_similarity);  d c / d x = y / (nx ny) - c x / nx^2   (a clamped norm is a constant)
+// rows are (b, n_pad): a row counts when its column t % n_pad < n_valid; rows that do not count get a zero gradient
+template <int NC> __global__ __launch_bounds__(256) void cosine_k(tfx_cosine_args p) {
+  __shared__ float sacc[WAVES];
+  const int lane = threadIdx.x & 63;
+  const int d = p.d;
+  float csum = 0.f;
+  for (int t = blockIdx.x * WAVES + (threadIdx.x >> 6); t < p.T; t += gridDim.x * WAVES) {
+    Row<NC> x;
+    if (p.n_pad > 0 && t % p.n_pad >= p.n_valid) {
+#pragma unroll
+      for (int i = 0; i < NC; i++)
+#pragma unroll
+        for (int e = 0; e < 8; e++) x.v[i][e] = 0.f;
+      store_row(x, p.dpred + (size_t)t * p.ld_d, d, lane);
+      continue;
+    }
+    Row<NC> y;
+    load_row(x, p.pred + (size_t)t * p.ld_pred, d, lane);
+    load_row(y, p.target + (size_t)t * p.ld_target, d, lane);
+    float xy = 0.f, xx = 0.f, yy = 0.f;
+#pragma unroll
+    for (int i = 0; i < NC; i++)
+#pragma unroll
+      for (int e = 0; e < 8; e++) { xy += x.v[i][e] * y.v[i][e]; xx += x.v[i][e] * x.v[i][e]; yy += y.v[i][e] * y.v[i][e]; }
+    xy = wave_sum(xy); xx = wave_sum(xx); yy = wave_sum(yy);
+    const float nx = sqrtf(xx), ny = sqrtf(yy);
+    const float inv = 1.f / (fmaxf(nx, 1e-8f) * fmaxf(ny, 1e-8f));
+    const float c = xy * inv;
+    csum += c;
+    // loss = 1 - mean c: d loss / d x = -grad_scale d c / d x; a norm under the clamp does not move with x
+    const float ky = -p.grad_scale * inv, kx = nx > 1e-8f ? p.grad_scale * c / xx : 0.f;
+#pragma unroll
+    for (int i = 0; i < NC; i++)
+#pragma unroll
+      for (int e = 0; e < 8; e++) x.v[i][e] = ky * y.v[i][e] + kx * x.v[i][e];
+    store_row(x, p.dpred + (size_t)t * p.ld_d, d, lane);
+  }
+  if (lane == 0) sacc[threadIdx.x >> 6] = csum;               // (wave-uniform: every lane holds the row sums)
+  __syncthreads();
+  if (threadIdx.x == 0) { float a = 0.f; for (int i = 0; i < WAVES; i++) a += sacc[i]; if (a != 0.f) atomicAdd(p.acc, a); }
+}
+
 TFX_DEV void cast_rows_body(const tfx_cast_args& p, long long blk) {
   const long long i = blk * 256 + threadIdx.x;
   if (i >= (long long)p.Rd * p.ld_dst) return;
@@ -2249,6 +2293,12 @@ int tfx_mse_fwd_bwd(const tfx_mse_args* a, void* s) {
   long long g = (n + 255) / 256; if (g > 2048) g = 2048;
   hipLaunchKernelGGL(mse_k, dim3((unsigned)g), dim3(256), 0, ST(s), *a); RET();
 }
+int tfx_cosine_fwd_bwd(const tfx_cosine_args* a, void* s) {
+  if (!a || a->T < 0 || a->d <= 0 || a->d > 2048 || (a->d % 64) || (a->ld_pred % 8) || (a->ld_target % 8) || (a->ld_d % 8) || a->ld_pred < a->d || a->ld_target < a->d || a->ld_d < a->d) return -1;
+  if (!a->pred || !a->target || !a->dpred || !a->acc || a->n_pad < 0 || a->n_valid < 0) return -2;
+  if (a->T == 0) return 0;
+  DISPATCH_NC(a->d, hipLaunchKernelGGL(cosine_k<NC>, dim3(grid_capped(a->T)), dim3(256), 0, ST(s), *a)); RET();
+}
 int tfx_cast_rows(const tfx_cast_args* a, void* s) {
   long long n = (long long)a->Rd * a->ld_dst; if (n == 0) return 0;
   hipLaunchKernelGGL(cast_rows_k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ST(s), *a); RET();
@@ -2355,6 +2405,6 @@ int tfx_laser_v_bwd(const tfx_laser_v_args* a, void* s) {
   if (nch >= (1ll << 31)) return -4;
   hipLaunchKernelGGL(laser_v_bwd_k, dim3((unsigned)((nch + 255) / 256)), dim3(256), 0, ST(s), *a, (unsigned)nch); RET();
 }
-const char* tfx_version(void) { return "tfx-hip gfx950 r3-laser-muon"; }
+const char* tfx_version(void) { return "tfx-hip gfx950 r4-laser-muon-selfflow"; }
 
 }  // extern "C"

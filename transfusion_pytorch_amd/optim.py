@@ -150,6 +150,11 @@ class FusedAdam:
 
     def __init__(self, model, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0., max_grad_norm=None, process_group=None,
                  average_grads=True):
+        # a SelfMaskedRepTraining wrapper: the student's flat buffer as for the bare model, the prediction head's parameters (PyTorch
+        # parameters with autograd gradients) by the route of the external ones
+        head_params = list(model.head_parameters()) if hasattr(model, 'head_parameters') else []
+        if head_params:
+            model = model.student
         self.model, self.lr, self.betas, self.eps, self.weight_decay = model, lr, betas, eps, weight_decay
         self.max_grad_norm = max_grad_norm
         self.group = process_group
@@ -164,7 +169,7 @@ class FusedAdam:
         # parameters that live OUTSIDE the flat buffer: the positional-embedding MLPs and the user's pre / post transformer encoder-decoder
         # modules (PyTorch modules with autograd gradients).  They are few and small: a stock Adam steps them, under the SAME global clip
         # coefficient (their squared gradient norm is added to the flat buffer's before the fused kernel reads it)
-        self.ext_params = list(model.external_parameters()) if hasattr(model, 'external_parameters') else []
+        self.ext_params = (list(model.external_parameters()) if hasattr(model, 'external_parameters') else []) + head_params
         self.ext_opt = torch.optim.Adam(self.ext_params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay) if self.ext_params else None
 
     @contextlib.contextmanager

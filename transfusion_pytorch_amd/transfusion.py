@@ -187,7 +187,9 @@ class _NativeLoss(torch.autograd.Function):
     Beyond the scalar loss it carries the rows that cross the PyTorch / engine line for modality types whose maps live in PyTorch:
       inputs  `rows` - token rows PyTorch produced for the engine, one per entry of spec['in'] = [('tok' | 'add', type)]: the user's encoder
                        output (`pre_post_transformer_enc_dec`) or the axial positional embedding rows; their gradient is d loss / d x0 at those rows
-      outputs        - the final-embedding rows of spec['out'] types, for the user's decoder; their incoming gradient seeds the backward next to the loss"""
+      outputs        - the final-embedding rows of spec['out'] types, for the user's decoder; their incoming gradient seeds the backward next to the loss
+                     - with spec['hid'] = (indices, raw): the hiddens of those indices (`_hiddens_out`); a gradient that reaches one of them is a
+                       hidden tap of this step's backward (engine.Plan.set_taps)"""
 
     @staticmethod
     def forward(ctx, anchor, model, loss, spec, *rows):
@@ -196,6 +198,10 @@ class _NativeLoss(torch.autograd.Function):
         outs = [loss.clone()]
         for t in spec['out']:
             outs.append(plan.embed.index_select(0, plan.row_tok[t].long().clamp(min=0)).float())
+        if spec.get('hid'):
+            ctx.set_materialize_grads(False)              # a hidden nobody used is no tap
+            ctx.n_true = model._live_n_true
+            outs += model._hiddens_out(plan, ctx.n_true, *spec['hid'])
         return tuple(outs)
 
     @staticmethod
@@ -203,9 +209,22 @@ class _NativeLoss(torch.autograd.Function):
         model, spec = ctx.model, ctx.spec
         plan = model._live[0]
         for t, g in zip(spec['out'], grad_rows):
-            plan.lat[t]['gemb'].copy_(g)
+            if g is None:
+                plan.lat[t]['gemb'].zero_()
+            else:
+                plan.lat[t]['gemb'].copy_(g)
+        if spec.get('hid'):
+            if ctx.step_id != model._live[1]:
+                raise RuntimeError('backward() of a stale loss: the native engine keeps the activations of the latest forward only')
+            taps = {k: g for k, g in zip(spec['hid'][0], grad_rows[len(spec['out']):]) if g is not None}
+            plan.set_taps(taps, ctx.n_true)
+            if grad_loss is None:                         # only the hiddens were used: the loss seeds carry nothing
+                grad_loss = torch.zeros((), device=plan.dembed.device)
         model._native_backward(grad_loss, ctx.step_id)
         back = [plan.dx0.index_select(0, plan.row_tok[t].long().clamp(min=0)).float() for _, t in spec['in']]
+        if spec.get('hid') and 0 in plan.taps:            # a tap at x_0 reaches the rows PyTorch produced directly
+            back = [r + plan.tap0_rows(plan.row_tok[t].long().clamp(min=0)) for r, (_, t) in zip(back, spec['in'])]
+        plan.clear_taps()                                 # a tap lives for one step
         return (None, None, None, None, *back)
 
 
@@ -750,7 +769,9 @@ class Transfusion(nn.Module):
     def forward(self, modalities, times=None, num_modalities_to_times_fn=None, modality_type=None, cache=None, decode_length=None,
                 decoding_text_or_modality=None, velocity_consistency_ema_model=None, velocity_consistency_delta_time=1e-3,
                 return_only_pred_flows=False, return_loss=True, return_breakdown=False, return_embed=False, return_hiddens=False,
-                return_kv_cache=False, return_times=False, prob_uncond=None):
+                return_kv_cache=False, return_times=False, prob_uncond=None, _hidden_request=None):
+        """`_hidden_request` (internal, SelfMaskedRepTraining): {'raw': hiddens as bf16 views of the plan's buffers, 'hiddens_only': under no_grad run the
+        training layout on a plan that keeps the hiddens alone and stops at the final norm (loss = None)}; the return value then ends with (plan, n_true)"""
         self._require_gpu()
         # the reference looks its packer up in the registry on every call (get_processing_strategy, MP:1252-1256, called at T:3104-3107).  The fused
         # step packs with the native packer only (every name the reference ships maps to it): an entry someone replaced or added must not be
@@ -773,7 +794,9 @@ class Transfusion(nn.Module):
             if not is_decoding:
                 modalities = self._encode_modalities(modalities)                           # T:3094-3101
             modalities = self._to_channel_last(modalities)
-        if cache is not None or decoding_text_or_modality is not None or return_kv_cache or return_hiddens:
+        # hiddens next to the loss come out of the fused training step (hidden taps: a gradient wrt any of them reaches the hand-written backward)
+        train_hiddens = bool(return_hiddens) and return_loss and not return_embed and cache is None and decoding_text_or_modality is None and not return_kv_cache
+        if (cache is not None or decoding_text_or_modality is not None or return_kv_cache or return_hiddens) and not train_hiddens:
             if return_loss and not return_embed:
                 raise NotImplementedError('kv cache / hiddens are returned by the inference forward only (return_loss = False or return_embed = True), '
                                           'as in the reference\'s own decode calls (T:1917-1924, T:1998-2006)')
@@ -835,11 +858,21 @@ class Transfusion(nn.Module):
         # step and its launch lists (building one costs far more than a step), so in the plain training case the plan is built for both counts ROUNDED
         # UP - in steps of a quarter of the count's power of two, at least 64 instances / 256 rows per type (`_bucket`) - and shared: padding instances are referenced by no token (their table gradients stay zero),
         # padding rows scatter nowhere and are kept out of the losses (engine.Plan.set_rows).  TFX_PLAN_BUCKETS=0: exact counts (one plan per pair).
+        # a teacher's pass (SelfMaskedRepTraining: no gradient, hiddens wanted, nothing else): the training LAYOUT of the batch on a plan that keeps the
+        # hiddens alone (what `training=False` plans keep) and stops at the final norm - no loss comes back
+        # (bucketed like the training plan, so ragged corpora share it: padding rows scatter nowhere and set_rows keeps them out of the noising)
+        hreq = _hidden_request or {}
+        hid_only = train_hiddens and not torch.is_grad_enabled() and bool(hreq.get('hiddens_only')) and ema is None and not return_only_pred_flows
         bucket = (return_loss and not self._ext and not md.pos_types and ema is None and not return_only_pred_flows and not self.has_recon_loss
                   and not md.model_output_clean and os.environ.get('TFX_PLAN_BUCKETS', '1') != '0')
         Ip = _bucket(I, 64) if (bucket and I > 0) else I
         Rp = {t: _bucket(r, 256) for t, r in R.items()} if bucket else R
-        plan = self._plan(b, n, Ip, Rp, training=return_loss)
+        plan = self._plan(b, n, Ip, Rp, training=return_loss and not hid_only)
+        if train_hiddens and not hid_only and torch.is_grad_enabled() and not plan.pull:
+            raise NotImplementedError('return_hiddens next to the loss (hidden taps) needs the pull-form AttentionResidual backward: depth <= 32 and dim <= 1024 '
+                                      '(under torch.no_grad() the hiddens come back without a tap)')
+        if return_loss and not hid_only:
+            plan.clear_taps()                               # a tap lives for the step that set it
         if md.model_output_clean:
             plan.set_clean_mode('model')                    # interleaved path: the model-space conversion (MP:786-792)
         if plan.loaded_structure is not S:
@@ -899,6 +932,15 @@ class Transfusion(nn.Module):
                 return out if not return_times else (out, times)
             logits = plan.logits.view(b, n, md.vp)[..., :md.vocab].clone()
             return (logits, times) if return_times else logits
+
+        if hid_only:
+            Plan.run(plan.fwd, stream, 0, plan.fwd_embed_end)
+            hid_idx = list(range(md.depth + 2)) if return_hiddens is True else sorted({int(k) % (md.depth + 2) for k in return_hiddens})
+            hiddens = [None] * (md.depth + 2)
+            for k, h in zip(hid_idx, self._hiddens_out(plan, S['n_true'], hid_idx, bool(hreq.get('raw')))):
+                hiddens[k] = h
+            ret = (None, hiddens, times) if return_times else (None, hiddens)
+            return (*ret, (plan, S['n_true'])) if _hidden_request is not None else ret
 
         if return_only_pred_flows:                                                        # T:3313-3316 (the EMA teacher's call)
             Plan.run(plan.fwd, stream, 0, plan.fwd_pred_end)
@@ -991,13 +1033,28 @@ class Transfusion(nn.Module):
         self._step_id += 1
         self._live = (plan, self._step_id)
         ext_out = sorted(plan.ext)
+        hiddens = None
+        if train_hiddens:
+            # return_hiddens = True: all depth + 2 of them, fp32 like the reference's; an iterable of indices: those alone (None elsewhere)
+            hid_idx = list(range(md.depth + 2)) if return_hiddens is True else sorted({int(k) % (md.depth + 2) for k in return_hiddens})
+            hid_raw = bool(hreq.get('raw'))
         if torch.is_grad_enabled():
             if self._anchor is None or self._anchor.device != dev:
                 self._anchor = torch.zeros((), device=dev, requires_grad=True)
             spec = {'in': [(k, t) for k, t, _ in rows_in], 'out': ext_out} if (rows_in or ext_out) else _NO_ROWS
+            if train_hiddens:
+                spec = dict(spec, hid=(hid_idx, hid_raw))
             loss, *emb_rows = _NativeLoss.apply(self._anchor, self, loss, spec, *[r for _, _, r in rows_in])
+            if train_hiddens:
+                emb_rows, hid_out = emb_rows[:len(ext_out)], emb_rows[len(ext_out):]
         else:
             emb_rows = [plan.embed.index_select(0, plan.row_tok[t].long().clamp(min=0)).float() for t in ext_out]
+            if train_hiddens:
+                hid_out = self._hiddens_out(plan, S['n_true'], hid_idx, hid_raw)
+        if train_hiddens:
+            hiddens = [None] * (md.depth + 2)
+            for k, h in zip(hid_idx, hid_out):
+                hiddens[k] = h
         for t, rows in zip(ext_out, emb_rows):                                              # the user's decoders and their flow losses, in PyTorch
             preds = self._ext_decode(t, rows, ext_ctx[t])
             fl, rec = self._ext_flow_loss(t, preds, ext_ctx[t])
@@ -1014,14 +1071,28 @@ class Transfusion(nn.Module):
             velocity_losses = [velocity_losses[t] for t in sorted(velocity_losses)]
         flow_losses = [flow_losses[t] for t in sorted(flow_losses)]
         recon_losses = [recon_losses[t] for t in sorted(recon_losses)] if self.has_recon_loss else None
-        if not return_breakdown and not return_times:
+        if not return_breakdown and not return_times and hiddens is None and _hidden_request is None:
             return loss
         ret = (loss,)
         if return_breakdown:
             ret = (*ret, LossBreakdown(loss, text_loss, flow_losses, velocity_losses, recon_losses))
+        if hiddens is not None:                                                            # T:3433-3450: loss[, breakdown], hiddens[, times]
+            ret = (*ret, hiddens)
         if return_times:
             ret = (*ret, times)
+        if _hidden_request is not None:
+            ret = (*ret, (plan, S['n_true']))
         return ret
+
+    def _hiddens_out(self, plan, n_true, indices, raw=False):
+        """hiddens = [x_0 .. x_depth, final norm output] (T:1199, T:1244, T:1253) of the plan's latest forward, cut to the n real columns of its
+        bucketed rows: fp32 copies, or (raw) bf16 views of the plan's own buffers - valid until the plan's next forward"""
+        md = self.md
+        out = []
+        for k in indices:
+            h = (plan.embed if k == md.depth + 1 else plan.hid[k]).view(plan.b, plan.n, md.dim)[:, :n_true]
+            out.append(h if raw else h.float())
+        return out
 
     # ------------------------------------------------------------------ decode contract of forward() (T:2926-2948, T:3186-3271)
     def _pred_flow_closures(self, P, clean_src=None):
@@ -1579,17 +1650,17 @@ class Transfusion(nn.Module):
         if red is None or red.defer or not plan.bwd_cuts or not (torch.distributed.is_available() and torch.distributed.is_initialized()):
             if red is not None and red.defer:
                 red.check_fresh()                               # (accumulating AFTER a backward that already exchanged would add into summed ranges)
-            Plan.run(plan.bwd, stream, graph='auto')            # `opt.no_sync()`: accumulate only - the step's last backward exchanges the sums
+            plan.run_bwd(stream)                                # `opt.no_sync()`: accumulate only - the step's last backward exchanges the sums
             return
         # data parallel with overlap: replay the list group by group; a finished group's gradient ranges go out while the rest runs
         red.check_fresh()                                   # one backward per optimizer step (the groups of the previous one are already summed over the ranks)
         red.begin()
         lo = 0
         for idx, first, last in plan.bwd_cuts:
-            Plan.run(plan.bwd, stream, lo, idx, graph='auto')
+            plan.run_bwd(stream, lo, idx)
             red.group_ready(first, last)
             lo = idx
-        Plan.run(plan.bwd, stream, lo, None, graph='auto')
+        plan.run_bwd(stream, lo, None)
 
     # ------------------------------------------------------------------ sampling surface (T:1842-2583)
     @torch.no_grad()
