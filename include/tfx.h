@@ -492,6 +492,34 @@ typedef struct {
 } tfx_adam_args;
 int tfx_adam_step(const tfx_adam_args* a, void* stream);
 
+/* the same launch with parameter groups and decoupled (AdamW) weight decay.  The struct BEGINS with the fields of tfx_adam_args, in its order and
+ * layout (tfx_adam_args itself keeps its size for the callers that pass it); what follows:
+ *   decoupled   the ungrouped rule: 0 = L2 (g += weight_decay p, tfx_adam_step's), 1 = torch.optim.AdamW's (p *= 1 - lr weight_decay, then the Adam update
+ *               without a decay term in g)
+ *   ranges      DEVICE table of `nrange` sorted, disjoint [start, end) element ranges with a group index each: 3 nrange int64 (start, end, group).  Starts
+ *               and ends are multiples of 4 (the elements of one thread: the flat buffer's segments are padded to 4, the padding belongs to the segment's
+ *               range).  Elements in no range belong to group 0.  The group is decided once per block where the block's 1024 elements lie in one range,
+ *               per thread only in blocks that straddle a boundary.
+ *   group_*     the records of `ngroup` <= TFX_ADAM_MAX_GROUPS groups BY VALUE (a schedule changes lr every step: nothing to copy to the device); with
+ *               nrange > 0 the kernel reads these in place of lr, beta1, beta2, eps, weight_decay and decoupled.  Bias corrections per group on the
+ *               host side of the launch, from the ONE `step`.
+ * nrange == 0 and decoupled == 0 IS tfx_adam_step (the same kernel on the same fields).  Otherwise the per-element operations are that kernel's, in its
+ * order, with the group's scalars: groups that all carry the global values give its bits.  `skip` composes (skipped elements stay untouched whatever
+ * their group), the clip coefficient (sumsq, max_norm, grad_scale) is one for all groups. */
+enum { TFX_ADAM_MAX_GROUPS = 8 };
+typedef struct {
+  float* p; const float* g; float* m; float* v; int64_t n;
+  float lr, beta1, beta2, eps, weight_decay, max_norm, grad_scale;
+  int32_t step; const float* sumsq;
+  const int64_t* skip; int32_t nskip;
+  int32_t decoupled;
+  const int64_t* ranges; int32_t nrange, ngroup;
+  float group_lr[TFX_ADAM_MAX_GROUPS], group_beta1[TFX_ADAM_MAX_GROUPS], group_beta2[TFX_ADAM_MAX_GROUPS], group_eps[TFX_ADAM_MAX_GROUPS],
+        group_weight_decay[TFX_ADAM_MAX_GROUPS];
+  int32_t group_decoupled[TFX_ADAM_MAX_GROUPS];
+} tfx_adam_group_args;
+int tfx_adam_step_groups(const tfx_adam_group_args* a, void* stream);
+
 /* ---- Muon (torch/optim/_muon.py) ---------------------------------------------------------------
  * One optimizer step over ALL matrices of Transfusion.muon_parameters() (T:1657-1672) in a number of launches that does not depend on their count:
  *   tfx_sumsq_det (2 launches) -> tfx_muon_prep -> tfx_muon_norm -> ns_steps x { gram, poly, update: tfx_muon_gemm } -> tfx_muon_apply -> tfx_adam_step(skip)

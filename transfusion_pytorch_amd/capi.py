@@ -43,8 +43,12 @@ def parse_header(path: str = HEADER):
                 d = d.strip()
                 is_ptr = d.startswith('*')
                 fname = d.lstrip('* ').strip()
+                arr = re.match(r'(\w+)\s*\[\s*(\w+)\s*\]$', fname)
                 if is_ptr:
                     fields.append((fname, ctypes.c_void_p))
+                elif arr:                                   # `float x[N]`, N a number or an enum of the header
+                    count = arr.group(2)
+                    fields.append((arr.group(1), _SCALARS[base] * (int(count) if count.isdigit() else enums[count])))
                 else:
                     fields.append((fname, _SCALARS[base]))
         structs[name] = fields
@@ -101,12 +105,14 @@ def ptr(t):
 def make_args(struct_name: str, **kw):
     S = STRUCTS[struct_name]
     a = S()
-    names = {f for f, _ in STRUCT_FIELDS[struct_name]}
+    types = dict(STRUCT_FIELDS[struct_name])
     for k, v in kw.items():
-        if k not in names:
+        if k not in types:
             raise KeyError(f'{struct_name} has no field {k}')
         if hasattr(v, 'data_ptr'):
             v = v.data_ptr()
+        elif isinstance(v, (list, tuple)):                  # an array field: the values given, zeros behind them
+            v = types[k](*v)
         setattr(a, k, v)
     return a
 

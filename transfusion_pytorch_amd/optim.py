@@ -138,24 +138,61 @@ class GradReducer:
         assert sum(b - a for a, b in self.done) == n, 'every gradient element must be reduced exactly once'
 
 
-class FusedAdam:
+_ADAM_KEYS = ('lr', 'betas', 'eps', 'weight_decay', 'decoupled_weight_decay')
+
+
+def _group_alias(key, index=0, doc=None):
+    """attribute that reads and writes `param_groups[index][key]` (the scalars live in the groups, where schedulers and checkpoints look)"""
+    def get(self):
+        return self.param_groups[index][key]
+
+    def put(self, value):
+        self.param_groups[index][key] = value
+    return property(get, put, doc=doc)
+
+
+def decay_groups(model, weight_decay, decoupled=True):
+    """the usual two parameter groups of `model.parameters()`: matrices and tables (`ndim >= 2`) decay; gains, biases, `layerscale` and
+    `pseudo_queries` do not.  For `FusedAdam(model, param_groups=decay_groups(model, 0.1))` / `FusedMuon(...)`; every parameter is named, the
+    first group is the decaying one."""
+    names = {id(p): n for n, p in model.named_parameters()}
+    plain = lambda p: p.ndim < 2 or names.get(id(p), '').endswith(('layerscale', 'pseudo_queries', 'gamma', 'bias'))
+    params = list(model.parameters())
+    return [dict(params=[p for p in params if not plain(p)], weight_decay=weight_decay, decoupled_weight_decay=bool(decoupled)),
+            dict(params=[p for p in params if plain(p)], weight_decay=0., decoupled_weight_decay=bool(decoupled))]
+
+
+class FusedAdam(torch.optim.Optimizer):
     """global-norm clip + Adam over the flat fp32 buffer as one launch (train_toy.py:55-57), the data-parallel gradient exchange in front of it, a stock
-    Adam under the same clip coefficient for `model.external_parameters()`.  Every scalar (`lr`, `betas`, ...) is re-read at each step.
+    Adam under the same clip coefficient for `model.external_parameters()`.
+
+    A `torch.optim.Optimizer`: `torch.optim.lr_scheduler.*` and optimizer wrappers take it, `state_dict()` / `load_state_dict()` have torch's format
+    (interchangeable with `torch.optim.Adam(model.parameters())` / `AdamW`).  It owns `model.parameters()` in that order - the views into the flat
+    buffer, the external parameters, for a SelfMaskedRepTraining wrapper the head's; parameters of the model that are neither (frozen ones, the
+    user's modality encoders / decoders) are listed, never stepped and carry no state.
+
+    `param_groups`: dicts `{'params': [parameters or their names], 'lr'?, 'betas'?, 'eps'?, 'weight_decay'?, 'decoupled_weight_decay'?}` (at most
+    TFX_ADAM_MAX_GROUPS); parameters no group names belong to `param_groups[0]`.  `opt.param_groups` is live: every scalar is re-read at each step;
+    `lr`, `betas`, `eps`, `weight_decay` are `param_groups[0]`'s.  `decoupled_weight_decay`: torch.optim.AdamW's rule (p *= 1 - lr wd) instead of the
+    L2 form (g += wd p).  One group with the L2 form is the launch FusedAdam always made (`tfx_adam_step`); anything else goes through
+    `tfx_adam_step_groups` with `group_ranges()` as a device table: one launch either way, one step count, one clip coefficient over everything.
 
     `deterministic_norm` (class default False, True in FusedMuon; may be set on an instance): take the clip norm as a fixed-order sum (`tfx_sumsq_det`)
     instead of `tfx_sumsq`'s atomic one, whose last bits - and with them the clip coefficient of every element - change from run to run.  False is the
     step FusedAdam always took."""
 
     deterministic_norm = False
+    lr, betas, eps, weight_decay = (_group_alias(k) for k in _ADAM_KEYS[:4])
 
     def __init__(self, model, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0., max_grad_norm=None, process_group=None,
-                 average_grads=True):
+                 average_grads=True, *, param_groups=None, decoupled_weight_decay=False, _other_rule_params=()):
         # a SelfMaskedRepTraining wrapper: the student's flat buffer as for the bare model, the prediction head's parameters (PyTorch
         # parameters with autograd gradients) by the route of the external ones
+        outer = model
         head_params = list(model.head_parameters()) if hasattr(model, 'head_parameters') else []
         if head_params:
             model = model.student
-        self.model, self.lr, self.betas, self.eps, self.weight_decay = model, lr, betas, eps, weight_decay
+        self.model = model
         self.max_grad_norm = max_grad_norm
         self.group = process_group
         self.average = average_grads
@@ -165,12 +202,117 @@ class FusedAdam:
         self._xev = []
         self.m = self.v = self.sumsq = None
         self._sumsq_partials = None     # scratch of the fixed-order clip norm (`deterministic_norm`)
+        self._range_tab = None          # device copy of `group_ranges()` and what it was built for
         self.reducer = None             # set by `overlap_grad_sync`: the exchange then runs in layer groups during the backward
         # parameters that live OUTSIDE the flat buffer: the positional-embedding MLPs and the user's pre / post transformer encoder-decoder
         # modules (PyTorch modules with autograd gradients).  They are few and small: a stock Adam steps them, under the SAME global clip
         # coefficient (their squared gradient norm is added to the flat buffer's before the fused kernel reads it)
         self.ext_params = (list(model.external_parameters()) if hasattr(model, 'external_parameters') else []) + head_params
-        self.ext_opt = torch.optim.Adam(self.ext_params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay) if self.ext_params else None
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, decoupled_weight_decay=bool(decoupled_weight_decay))
+        super().__init__(self._resolve_groups(outer, param_groups, _other_rule_params), defaults)
+        self._ext_key, self.ext_opt = None, None
+        self._sync_ext_opt()
+
+    # ------------------------------------------------------------------ parameter groups
+    @staticmethod
+    def _resolve_groups(model, param_groups, other_rule_params=()):
+        """`param_groups` (parameters or names) as torch's list of group dicts over `model.parameters()`: unnamed parameters join group 0;
+        `other_rule_params` (a subclass steps them by another rule) leave whatever group names them"""
+        params = list(model.parameters())
+        known = {id(p) for p in params}
+        other = {id(p) for p in other_rule_params}
+        by_name = dict(model.named_parameters())
+        if hasattr(model, 'student'):
+            by_name.update((n, p) for n, p in model.student.named_parameters() if n not in by_name)
+        groups = [dict(g) for g in param_groups] if param_groups is not None else [dict(params=params)]
+        if not groups:
+            raise ValueError('param_groups is empty')
+        if len(groups) > capi.ENUMS['TFX_ADAM_MAX_GROUPS']:
+            raise ValueError(f"{len(groups)} parameter groups: the fused Adam launch takes at most {capi.ENUMS['TFX_ADAM_MAX_GROUPS']}")
+        seen = set()
+        for g in groups:
+            unknown = set(g) - set(_ADAM_KEYS) - {'params'}
+            if unknown:
+                raise ValueError(f'unknown keys in a parameter group: {sorted(unknown)} (taken: params, {", ".join(_ADAM_KEYS)})')
+            listed = g.get('params', [])
+            listed = [listed] if torch.is_tensor(listed) or isinstance(listed, str) else list(listed)
+            out = []
+            for p in listed:
+                if isinstance(p, str):
+                    if p not in by_name:
+                        raise ValueError(f'parameter group names {p!r}, which is no parameter of the model')
+                    p = by_name[p]
+                if id(p) not in known:
+                    raise ValueError('a parameter group holds a tensor that is no parameter of the model')
+                if id(p) in seen:
+                    raise ValueError('a parameter appears in two parameter groups')
+                seen.add(id(p))
+                if id(p) not in other:
+                    out.append(p)
+            g['params'] = out
+        groups[0]['params'] += [p for p in params if id(p) not in seen and id(p) not in other]
+        return groups
+
+    def _adam_groups(self):
+        """the groups the Adam rule steps (a subclass keeps another rule's group behind them)"""
+        return self.param_groups
+
+    def _group_scalars(self, g):
+        b1, b2 = g['betas']
+        return float(g['lr']), float(b1), float(b2), float(g['eps']), float(g['weight_decay']), int(bool(g.get('decoupled_weight_decay', False)))
+
+    def _membership(self):
+        return tuple(tuple(id(p) for p in g['params']) for g in self.param_groups)
+
+    def _flat_offsets(self):
+        """id(parameter) -> (element offset, padded elements) of the parameters that are views into the flat buffer"""
+        ps = self.model.store
+        return {id(p): (ps.offsets[n][0], -(-p.numel() // 4) * 4) for n, p in ps.params.items()}
+
+    def group_ranges(self):
+        """the host form of tfx_adam_group_args.ranges: sorted (start, end, group) over the whole flat buffer, bounds multiples of 4 (a segment's
+        padding belongs to it), adjacent segments of one group merged.  Segments another rule owns (FusedMuon's matrices: the kernel skips them) ride
+        with their left neighbour."""
+        flat = self._flat_offsets()
+        owner = {}
+        for k, g in enumerate(self._adam_groups()):
+            for p in g['params']:
+                if id(p) in flat:
+                    owner[flat[id(p)][0]] = k
+        out = []
+        for off, size in sorted(flat.values()):
+            k = owner.get(off, out[-1][2] if out else None)
+            if out and out[-1][2] in (k, None):
+                out[-1][1], out[-1][2] = off + size, k
+            else:
+                out.append([off, off + size, k])
+        return [(a, b, k or 0) for a, b, k in out]
+
+    def _range_table(self, ps):
+        key = (ps.flat.data_ptr(), str(ps.flat.device), self._membership())
+        if self._range_tab is None or self._range_tab[0] != key:
+            host = self.group_ranges()
+            self._range_tab = (key, torch.tensor(host, dtype=torch.int64, device=ps.flat.device).reshape(-1), len(host))
+        return self._range_tab[1], self._range_tab[2]
+
+    def _sync_ext_opt(self):
+        """the stock Adam of the external parameters: one torch group per group that holds some, the group's scalars every step (AdamW's rule where
+        the group is decoupled).  Rebuilt, state kept, when the membership of the groups changes."""
+        if not self.ext_params:
+            return
+        ext = {id(p) for p in self.ext_params}
+        key = self._membership()
+        if self._ext_key != key:
+            members = [(g, [p for p in g['params'] if id(p) in ext]) for g in self._adam_groups()]
+            state = dict(self.ext_opt.state) if self.ext_opt is not None else {}
+            self._ext_groups = [g for g, ps_ in members if ps_]
+            self.ext_opt = torch.optim.Adam([dict(params=ps_) for _, ps_ in members if ps_])
+            for p, st in state.items():
+                self.ext_opt.state[p] = st
+            self._ext_key = key
+        for src, grp in zip(self._ext_groups, self.ext_opt.param_groups):   # a schedule that sets `opt.lr = ...` or a group's lr reaches these too
+            lr, b1, b2, eps, wd, dec = self._group_scalars(src)
+            grp['lr'], grp['betas'], grp['eps'], grp['weight_decay'], grp['decoupled_weight_decay'] = src['lr'], (b1, b2), eps, wd, bool(dec)
 
     @contextlib.contextmanager
     def no_sync(self):
@@ -246,9 +388,7 @@ class FusedAdam:
         if ps.grad is None:
             raise capi.TfxError('FusedAdam needs the model on an MI355X (model.cuda())')
         world = self.sync_grads()
-        if self.m is None or self.m.device != ps.flat.device or self.m.numel() != ps.numel:
-            self.m = torch.zeros_like(ps.flat); self.v = torch.zeros_like(ps.flat)
-            self.sumsq = torch.zeros(1, device=ps.flat.device)
+        self._ensure_state(ps)
         stream = torch.cuda.current_stream(ps.flat.device).cuda_stream
         self.step_count += 1
         max_norm = float(self.max_grad_norm) if self.max_grad_norm else 0.
@@ -270,14 +410,23 @@ class FusedAdam:
                 coef = coef * (max_norm / (self.sumsq[0].sqrt() * gscale + 1e-6)).clamp(max=1.)
             for g in ext_grads:
                 g.mul_(coef)
-            for grp in self.ext_opt.param_groups:          # a schedule that sets `opt.lr = ...` (re-read by the fused kernel every step) reaches these too
-                grp['lr'], grp['betas'], grp['eps'], grp['weight_decay'] = self.lr, tuple(self.betas), self.eps, self.weight_decay
+            self._sync_ext_opt()
             self.ext_opt.step()
         skip, nskip = self._step_other_rules(ps, stream, max_norm, gscale)
-        a = capi.make_args('tfx_adam_args', p=ps.flat, g=ps.grad, m=self.m, v=self.v, n=ps.numel, lr=self.lr, beta1=self.betas[0],
-                           beta2=self.betas[1], eps=self.eps, weight_decay=self.weight_decay, max_norm=max_norm,
-                           grad_scale=gscale, step=self.step_count, sumsq=self.sumsq, skip=skip, nskip=nskip)
-        capi.call('tfx_adam_step', a, stream)
+        groups = self._adam_groups()
+        lr, beta1, beta2, eps, wd, decoupled = self._group_scalars(groups[0])
+        common = dict(p=ps.flat, g=ps.grad, m=self.m, v=self.v, n=ps.numel, lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=wd, max_norm=max_norm,
+                      grad_scale=gscale, step=self.step_count, sumsq=self.sumsq, skip=skip, nskip=nskip)
+        if len(groups) == 1 and not decoupled:              # the launch FusedAdam always made
+            capi.call('tfx_adam_step', capi.make_args('tfx_adam_args', **common), stream)
+        elif len(groups) == 1:
+            capi.call('tfx_adam_step_groups', capi.make_args('tfx_adam_group_args', decoupled=1, **common), stream)
+        else:
+            ranges, nrange = self._range_table(ps)
+            rec = list(zip(*(self._group_scalars(g) for g in groups)))
+            a = capi.make_args('tfx_adam_group_args', decoupled=decoupled, ranges=ranges, nrange=nrange, ngroup=len(groups), group_lr=rec[0],
+                               group_beta1=rec[1], group_beta2=rec[2], group_eps=rec[3], group_weight_decay=rec[4], group_decoupled=rec[5], **common)
+            capi.call('tfx_adam_step_groups', a, stream)
         # the master changed behind autograd's back: new weights epoch (shadows rebuilt, kept decode plans dropped)
         ps.mark_dirty()
 
@@ -285,6 +434,107 @@ class FusedAdam:
         """hook of subclasses that update part of the flat buffer by another rule, between the clip norm and the Adam launch: returns the device
         table of element ranges Adam then leaves alone and its length (tfx_adam_args.skip / nskip)"""
         return None, 0
+
+    def _ensure_state(self, ps):
+        """the moments and the clip norm's scalar, on the flat buffer's device (moments that exist move with it: a loaded state is not lost)"""
+        if self.m is None or self.m.numel() != ps.numel:
+            self.m = torch.zeros_like(ps.flat); self.v = torch.zeros_like(ps.flat)
+        elif self.m.device != ps.flat.device:
+            self.m, self.v = (self.m.to(ps.flat.device), self.v.to(ps.flat.device)) if self.step_count else (torch.zeros_like(ps.flat), torch.zeros_like(ps.flat))
+        if self.sumsq is None or self.sumsq.device != ps.flat.device:
+            self.sumsq = torch.zeros(1, device=ps.flat.device)
+
+    # ------------------------------------------------------------------ state (torch.optim's format)
+    def _other_rule_state(self, p):
+        """hook of subclasses: the state entry of a flat-buffer parameter another rule steps (None: Adam's)"""
+        return None
+
+    def _load_other_rule_state(self, p, entry):
+        return False
+
+    def _indexed_params(self):
+        return [p for g in self.param_groups for p in g['params']]
+
+    def state_dict(self):
+        """`torch.optim.Optimizer.state_dict()`'s format: indices over the groups in order; per flat-buffer parameter `step` (the one step count),
+        `exp_avg`, `exp_avg_sq` as views of `m` / `v`; the external parameters' entries are their stock Adam's.  Empty before the first step."""
+        groups, start = [], 0
+        for g in self.param_groups:
+            packed = {k: v for k, v in g.items() if k != 'params'}
+            packed['params'] = list(range(start, start + len(g['params'])))
+            start += len(g['params'])
+            groups.append(packed)
+        state = {}
+        flat = self._flat_offsets()
+        for i, p in enumerate(self._indexed_params()):
+            if id(p) in flat:
+                if self.m is None or self.step_count == 0:
+                    continue
+                other = self._other_rule_state(p)
+                if other is not None:
+                    state[i] = other
+                    continue
+                off = flat[id(p)][0]
+                state[i] = dict(step=torch.tensor(float(self.step_count)), exp_avg=self.m[off:off + p.numel()].view(p.shape),
+                                exp_avg_sq=self.v[off:off + p.numel()].view(p.shape))
+            elif self.ext_opt is not None and p in self.ext_opt.state and self.ext_opt.state[p]:
+                state[i] = dict(self.ext_opt.state[p])
+        return dict(state=state, param_groups=groups)
+
+    def load_state_dict(self, state_dict):
+        """takes a `state_dict()` of this class or of `torch.optim.Adam` / `AdamW` over the same parameters in the same groups: the groups'
+        scalars, the moments (copied into `m` / `v`; a missing entry means zeros) and the step count.  ValueError where group or parameter counts or
+        shapes differ, and where the flat-buffer parameters' steps differ (the fused launch has one bias correction)."""
+        saved = state_dict['param_groups']
+        if len(saved) != len(self.param_groups):
+            raise ValueError(f'loaded state dict has {len(saved)} parameter groups, the optimizer has {len(self.param_groups)}')
+        index = {}
+        for g, sg in zip(self.param_groups, saved):
+            if len(sg['params']) != len(g['params']):
+                raise ValueError(f"loaded state dict has a parameter group of {len(sg['params'])} parameters where the optimizer's has {len(g['params'])}")
+            if sg.get('amsgrad') or sg.get('maximize'):
+                raise ValueError('amsgrad / maximize states cannot be loaded: the fused Adam launch has neither')
+            index.update(zip(sg['params'], g['params']))
+        entries = {k: e for k, e in state_dict['state'].items() if e}
+        for k in entries:
+            if k not in index:
+                raise ValueError(f'loaded state dict has an entry for parameter {k}, which no group holds')
+        flat, ext = self._flat_offsets(), {id(p) for p in self.ext_params}
+        steps = set()
+        for k, e in entries.items():
+            p = index[k]
+            for name in ('exp_avg', 'exp_avg_sq', 'momentum_buffer'):
+                if name in e and tuple(e[name].shape) != tuple(p.shape):
+                    raise ValueError(f'loaded state of parameter {k}: {name} has shape {tuple(e[name].shape)}, the parameter {tuple(p.shape)}')
+            if id(p) in flat and 'step' in e:
+                steps.add(float(e['step']))
+        if len(steps) > 1:
+            raise ValueError(f'the loaded parameters are at different steps ({sorted(steps)}): the fused Adam launch has one bias correction for the whole buffer')
+        for g, sg in zip(self.param_groups, saved):
+            g.update({k: v for k, v in sg.items() if k != 'params'})
+        ps = self.model.store
+        self.step_count = int(steps.pop()) if steps else 0
+        if entries or self.m is not None:
+            self.m = self.v = None
+            self._ensure_state(ps)
+        if self.ext_opt is not None:
+            self.ext_opt.state.clear()
+        with torch.no_grad():
+            for k, e in entries.items():
+                p = index[k]
+                if id(p) in flat:
+                    if self._load_other_rule_state(p, e):
+                        continue
+                    if 'exp_avg' not in e or 'exp_avg_sq' not in e:
+                        raise ValueError(f'loaded state of parameter {k} has no exp_avg / exp_avg_sq')
+                    off = flat[id(p)][0]
+                    self.m[off:off + p.numel()].view(p.shape).copy_(e['exp_avg'])
+                    self.v[off:off + p.numel()].view(p.shape).copy_(e['exp_avg_sq'])
+                elif id(p) in ext:
+                    self.ext_opt.state[p] = {n: t if not torch.is_tensor(t) else t.detach().float().cpu().clone() if n == 'step' else t.to(p.device, p.dtype).clone()
+                                             for n, t in e.items()}
+        self._ext_key = None
+        self._sync_ext_opt()
 
     def zero_grad(self, set_to_none: bool = True):
         ps = self.model.store
@@ -419,24 +669,53 @@ class FusedMuon(FusedAdam):
     All matrices go through every stage together (csrc/muon.hip): the number of launches of a step does not depend on the depth, and nothing in
     the path is an atomic or an order-varying sum, so replicas that orthogonalise the same all-reduced gradient stay bit-identical.
     The momentum of a matrix lives in the Adam first-moment buffer at the matrix's own range (`momentum_buffer(p)`); Adam skips those ranges.
-    Every scalar (`lr`, `muon_lr`, `momentum`, ...) is re-read at each step."""
+    Muon's share is the LAST parameter group, under torch.optim.Muon's key names (`muon_lr` and the other attributes alias it); the Adam share takes
+    `param_groups` as FusedAdam does.  Every scalar (`lr`, `muon_lr`, `momentum`, ...) is re-read at each step."""
 
     deterministic_norm = True
 
+    _MUON_KEYS = ('lr', 'weight_decay', 'momentum', 'nesterov', 'ns_coefficients', 'eps', 'ns_steps', 'adjust_lr_fn')       # torch.optim.Muon's group keys
+    muon_lr, muon_weight_decay, momentum, nesterov, ns_coefficients, muon_eps, ns_steps, adjust_lr_fn = (_group_alias(k, -1) for k in _MUON_KEYS)
+
     def __init__(self, model, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0., max_grad_norm=None, process_group=None, average_grads=True, *,
                  muon_params=None, muon_lr=1e-3, muon_weight_decay=0.1, momentum=0.95, nesterov=True, ns_coefficients=(3.4445, -4.775, 2.0315),
-                 ns_steps=5, muon_eps=1e-7, adjust_lr_fn=None):
-        super().__init__(model, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm, process_group=process_group,
-                         average_grads=average_grads)
-        self.muon_params = list(model.muon_parameters() if muon_params is None else muon_params)
-        if not self.muon_params:
+                 ns_steps=5, muon_eps=1e-7, adjust_lr_fn=None, param_groups=None, decoupled_weight_decay=False):
+        muon = list(model.muon_parameters() if muon_params is None else muon_params)
+        if not muon:
             raise ValueError('FusedMuon needs at least one matrix (use FusedAdam otherwise)')
-        for p in self.muon_params:
+        for p in muon:
             if p.ndim != 2:
                 raise ValueError(f'Muon parameters must be 2-D matrices, got shape {tuple(p.shape)}')
-        self.muon_lr, self.muon_weight_decay, self.momentum, self.nesterov = muon_lr, muon_weight_decay, momentum, nesterov
-        self.ns_coefficients, self.ns_steps, self.muon_eps, self.adjust_lr_fn = ns_coefficients, ns_steps, muon_eps, adjust_lr_fn
+        # the Adam share takes groups as FusedAdam does (the matrices leave whatever group lists them: `decay_groups(model, ...)` may be passed
+        # as it is); Muon's share is the LAST group, under torch.optim.Muon's key names - a scheduler scales both learning rates
+        super().__init__(model, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm, process_group=process_group,
+                         average_grads=average_grads, param_groups=param_groups, decoupled_weight_decay=decoupled_weight_decay, _other_rule_params=muon)
+        self.param_groups.append(dict(params=muon, lr=muon_lr, weight_decay=muon_weight_decay, momentum=momentum, nesterov=nesterov,
+                                      ns_coefficients=ns_coefficients, eps=muon_eps, ns_steps=ns_steps, adjust_lr_fn=adjust_lr_fn))
+        self._muon_group = True
+        self._sync_ext_opt()
         self._tab = None
+
+    @property
+    def muon_params(self):
+        return self.param_groups[-1]['params']
+
+    _muon_group = False               # until the constructor has appended it
+
+    def _adam_groups(self):
+        return self.param_groups[:-1] if self._muon_group else self.param_groups
+
+    def _other_rule_state(self, p):
+        if any(p is q for q in self.muon_params):
+            return dict(momentum_buffer=self.momentum_buffer(p))
+        return None
+
+    def _load_other_rule_state(self, p, entry):
+        if not any(p is q for q in self.muon_params):
+            return False
+        if 'momentum_buffer' in entry and entry['momentum_buffer'] is not None:
+            self.momentum_buffer(p).copy_(entry['momentum_buffer'])
+        return True
 
     # ------------------------------------------------------------------ host tables
     def muon_segments(self):
