@@ -423,7 +423,11 @@ int tfx_output_to_flow(float* pred, const float* x, const float* eps, const int3
 int tfx_sample_tokens(const float* logits, int32_t ld, int32_t B, int32_t V, float temperature, float min_p, const float* uniforms,
                       const int32_t* active, int32_t* out_ids, void* stream);
 /* the same with the DRAW restricted to the first V_draw columns while the maximum (hence the min-p threshold, and the argmax at temperature 0)
- * still runs over all V: `generate_text_only` (T:2690-2698) filters over every logit, then masks everything but the text tokens */
+ * still runs over all V: `generate_text_only` (T:2690-2698) filters over every logit, then masks everything but the text tokens.
+ * Fallbacks of both entries, when the inverse-CDF scan ends without crossing the target: (1) fp32 rounding (uniforms[row] close to 1: the total and the
+ * prefix sums add the same terms in different orders) -> the LAST surviving column below V_draw; (2) no column below V_draw survives the min-p filter
+ * (only with V_draw < V: the maximum lies in a masked column) -> V_draw, the first masked column - the reference's masked logits are all -finfo.max
+ * there and its argmax takes the first.  temperature < 0 is refused (-3) by both. */
 int tfx_sample_tokens_range(const float* logits, int32_t ld, int32_t B, int32_t V, int32_t V_draw, float temperature, float min_p, const float* uniforms,
                             const int32_t* active, int32_t* out_ids, void* stream);
 /* ODE state update of the fixed-grid midpoint solver (torchdiffeq semantics; T:2468-2525) fused with classifier-free

@@ -9,6 +9,9 @@ namespace tfx {
 //   else             : p = softmax(logits / temperature); tokens with p < min_p * max(p) are removed; the survivor with
 //                      cumulative mass crossing u * (total surviving mass) is drawn (inverse CDF in index order - the same
 //                      distribution torch.multinomial samples from)
+// When rounding leaves the target unreached (u close to 1: `mass` and the scan sum the same terms in different orders) the draw is the LAST survivor
+// below V_draw, never a column outside the draw range.  When nothing survives below V_draw (V_draw < V, the maximum sits in a masked column and
+// min-p removes every text token) the result is V_draw: the reference's masked logits are all -finfo.max there and its argmax takes the first (T:2697-2698).
 __global__ __launch_bounds__(256) void sample_tokens_k(const float* logits, int ld, int B, int V, float temperature, float min_p, const float* uniforms,
                                                        const int* active, int* out_ids, int V_draw) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -31,7 +34,7 @@ __global__ __launch_bounds__(256) void sample_tokens_k(const float* logits, int 
   mass = wave_sum(mass);
   // pass 3: inverse CDF in index order, 64 columns per step with a wave prefix sum
   const float target = uniforms[row] * mass;
-  float run = 0.f; int pick = bi;                       // falls back to the mode if rounding leaves the target unreached
+  float run = 0.f; int pick = -1, last = -1;            // last: the last survivor seen so far (the fallback when rounding leaves the target unreached)
   bool done = false;
   for (int c0 = 0; c0 < V_draw && !done; c0 += 64) {
     const int c = c0 + lane;
@@ -41,10 +44,12 @@ __global__ __launch_bounds__(256) void sample_tokens_k(const float* logits, int 
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) { const float t = __shfl_up(pre, o, 64); if (lane >= o) pre += t; }
     const bool hit = r > 0.f && run + pre > target;
-    const unsigned long long m = __ballot(hit);
+    const unsigned long long m = __ballot(hit), alive = __ballot(r > 0.f);
     if (m) { pick = c0 + __builtin_ctzll(m); done = true; }
+    else if (alive) last = c0 + 63 - __builtin_clzll(alive);
     run += __shfl(pre, 63, 64);
   }
+  if (!done) pick = last >= 0 ? last : V_draw < V ? V_draw : bi;     // (V_draw == V and no survivor: min_p > 1 - the mode, as before)
   if (lane == 0) out_ids[row] = pick;
 }
 
@@ -226,6 +231,7 @@ int tfx_sample_tokens_range(const float* logits, int32_t ld, int32_t B, int32_t 
                             const int32_t* active, int32_t* out_ids, void* s) {
   if (B <= 0) return 0;
   if (!logits || !out_ids || V <= 0 || V_draw <= 0 || V_draw > V || ld < V || (temperature != 0.f && !uniforms)) return -1;
+  if (temperature < 0.f) return -3;
   hipLaunchKernelGGL(sample_tokens_k, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)s, logits, ld, B, V, temperature, min_p, uniforms, active, out_ids, V_draw);
   return (int)hipGetLastError();
 }

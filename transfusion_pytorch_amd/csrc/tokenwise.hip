@@ -1689,8 +1689,14 @@ __global__ __launch_bounds__(256) void mse_k(tfx_mse_args p) {
       const float pr = p.pred[(size_t)r * p.ld_pred + c], fl = p.flow[(size_t)r * p.dl + c];
       if (p.recon_w) {
         const float t = p.recon_time[p.recon_inst[r]], w = p.recon_w[r];
-        const float df = (1.f - t) * pr - (p.recon_mode ? 1.f : t) * fl;
-        s += w * df * df; g = df * (p.grad_scale * w * (1.f - t));
+        // the residual (1 - t) pred - c flow to one rounding of ITS OWN size.  Where the two terms cancel (a good prediction) the roundings of 1 - t, of
+        // the products and of the difference are each 2^-24 of a TERM - percents of a small residual, more than the bf16 rounding of the gradient.
+        // 1 - t = s1 + sl (Fast2Sum, 0 <= t <= 1) and c flow = q + ql (FMA error term) hold exactly
+        const float c = p.recon_mode ? 1.f : t;
+        const float s1 = 1.f - t, sl = (1.f - s1) - t;
+        const float q = c * fl, ql = __builtin_fmaf(c, fl, -q);
+        const float df = __builtin_fmaf(s1, pr, -q) + __builtin_fmaf(sl, pr, -ql);
+        s += w * df * df; g = df * (p.grad_scale * w * s1);
       } else {
         const float df = pr - fl;
         s += df * df; g = df * p.grad_scale;
