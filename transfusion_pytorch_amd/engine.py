@@ -726,6 +726,27 @@ class Plan:
             if self.row_gat is not self.row_tok:
                 torch.clamp(self.row_tok[t], min=0, out=self.row_gat[t])
 
+    def load_structure(self, S, rope, tok_inst, kv_end, q_start, rot_pos, segments=None, rows=None, set_rows=False):
+        """load a batch structure `S` (whatever object the caller caches it as; kept in `loaded_structure`, so a caller that sees the same one again
+        skips the reload): the rotary tables, the per-token index arrays, optionally the token segments (seg_start, seg_len) and the latent-row
+        maps `rows` = {type: (row_tok, row_inst)} of the REAL rows - rows of the plan past them (a plan is built for rounded-up counts) and whole
+        types without an entry scatter nowhere (row_tok = -1) and belong to instance 0.  `set_rows`: also tell the kernels the real counts."""
+        self.set_rope_tables(*rope)
+        self.tok_inst.copy_(tok_inst.view(-1)); self.kv_end.copy_(kv_end); self.q_start.copy_(q_start); self.rot_pos.copy_(rot_pos)
+        if segments is not None:
+            self.set_segments(*segments)
+        if rows is not None:
+            for t, cap in self.R.items():
+                row_tok, row_inst = rows.get(t, (None, None))
+                r = 0 if row_tok is None else int(row_tok.numel())
+                if r < cap:
+                    self.row_tok[t].fill_(-1); self.row_inst[t].zero_()
+                if r:
+                    self.row_tok[t][:r].copy_(row_tok); self.row_inst[t][:r].copy_(row_inst)
+            if set_rows:
+                self.set_rows({t: int(v[0].numel()) for t, v in rows.items()})
+        self.loaded_structure = S
+
     def set_noise(self, t: int, eps_ptr):
         """noise source of modality type t for this run: a device pointer (training: x_t = t x + (1 - t) eps) or None (no noising)"""
         self.noise_args[t].eps = eps_ptr

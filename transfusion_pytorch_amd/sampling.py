@@ -265,7 +265,6 @@ class Sampler:
         joint0 = joint
         cache = joint[:, :B]
         self._fill_cache(cache, plan, B, n0)
-        logits0 = plan.logits.view(B, n0, md.vp)[..., :md.vocab]
         for st in states:
             self._maybe_transition(st, fixed_modality_shape)
         stream = m._stream()

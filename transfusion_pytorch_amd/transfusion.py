@@ -7,6 +7,7 @@ Unsupported reference options raise NotImplementedError - there is no silent PyT
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 from typing import NamedTuple
@@ -121,6 +122,32 @@ def _bucket(x: int, min_step: int) -> int:
 
 
 _TRAIN_PAD = 64
+
+
+def _num_modalities(sample):
+    """modality instances of one sample: `(type, tensor)` tuples and bare float tensors (type 0)"""
+    return sum(1 for p in sample if isinstance(p, tuple) or (torch.is_tensor(p) and p.is_floating_point()))
+
+
+def _pack_outputs(out, *extras):
+    """what an entry point returns: `out` alone, or the tuple of it and the extras asked for - each given as (wanted, value), in the reference's order"""
+    ret = (out, *[v for wanted, v in extras if wanted])
+    return ret[0] if len(ret) == 1 else ret
+
+
+@contextlib.contextmanager
+def _teacher_pass(ema, flat_pred_flows=False):
+    """the EMA teacher's call: in `eval()` under `no_grad`, its mode restored afterwards.  `flat_pred_flows`: its `return_only_pred_flows`
+    forward hands back the packed per-type rows of its plan ({type: (R, dim_latent)}) instead of per-instance tensors"""
+    was_training = ema.training
+    ema.eval()
+    ema._flat_pred_flows = flat_pred_flows
+    try:
+        with torch.no_grad():
+            yield ema
+    finally:
+        ema._flat_pred_flows = False
+        ema.train(was_training)
 
 
 class ModalityInfo(NamedTuple):              # T:112-126
@@ -361,6 +388,8 @@ class Transfusion(nn.Module):
             self._register_state_dict_hook(_post)
         self._plans = {}
         self._struct_cache = {}
+        self._decode_plans = {}              # decode plans of the cached forward calls and of the sampler (sampling.Sampler._decode_plan)
+        self._flat_pred_flows = False        # set by `_teacher_pass` around a teacher's forward
         self._step_id = 0
         self._live = None
         self._consumed = -1
@@ -625,6 +654,17 @@ class Transfusion(nn.Module):
         self._plans[key] = plan                                      # (re-)insert at the most recent position
         return plan
 
+    def _structure(self, key, build):
+        """the batch structure cached under `key` (device index arrays: what a plan loads with `Plan.load_structure`), built by `build()` on a miss;
+        the cache holds the 32 most recently used (dict order = use order)"""
+        S = self._struct_cache.pop(key, None)
+        if S is None:
+            while len(self._struct_cache) >= 32:                     # least recently used structure goes first
+                self._struct_cache.pop(next(iter(self._struct_cache)))
+            S = build()
+        self._struct_cache[key] = S                                  # (re-)insert at the most recent position
+        return S
+
     def _build_structure(self, modalities, return_loss, add_meta=True, pad_n=1, presig=None):
         """full structure scan (host) + upload of every derived index array; cached per structure signature.
         `add_meta=False`: the decode-time layout (`return_embed` in the reference, MP:330): no [meta][shape][som][eom]
@@ -705,13 +745,7 @@ class Transfusion(nn.Module):
             with torch.no_grad():
                 samples, ext_ctx = self._ext_preprocess(samples, None, return_loss=False)
         sig, user_text, latents = fast_signature(samples)
-        key = (sig, 'plain', add_meta, pad_n)
-        S = self._struct_cache.pop(key, None)
-        if S is None:
-            while len(self._struct_cache) >= 32:
-                self._struct_cache.pop(next(iter(self._struct_cache)))
-            S = self._build_structure(samples, False, add_meta=add_meta, pad_n=pad_n)
-        self._struct_cache[key] = S
+        S = self._structure((sig, 'plain', add_meta, pad_n), lambda: self._build_structure(samples, False, add_meta=add_meta, pad_n=pad_n))
         tm, b, n, I, R = S['tm'], S['b'], S['n'], S['I'], S['R']
         self.store.refresh_shadows(stream)
         # The prefill plans of a decode loop differ only in their instance / latent-row counts from one modality phase to the next: round
@@ -724,21 +758,15 @@ class Transfusion(nn.Module):
             for t in range(self.num_modalities):
                 Rp.setdefault(t, 256)
         plan = self._plan(b, n, Ip, Rp, training=False)
-        plan.set_rope_tables(*self._rope_tables(int(tm.rot_pos.max()) if tm.rot_pos.size else 0))
-        plan.tok_inst.copy_(S['tok_inst'].view(-1)); plan.kv_end.copy_(S['kv_end']); plan.q_start.copy_(S['q_start']); plan.rot_pos.copy_(S['rot_pos'])
-        plan.loaded_structure = S
-        text_full = S['text_host'].clone()
-        if user_text:
-            text_full.view(-1).index_copy_(0, S['text_dest'], torch.cat(user_text).to(dev, torch.int32))
-        plan.text_ids.copy_(text_full[:, :n].reshape(-1))
+        plan.load_structure(S, self._rope_tables(int(tm.rot_pos.max()) if tm.rot_pos.size else 0), S['tok_inst'], S['kv_end'], S['q_start'], S['rot_pos'],
+                            rows={t: (S['row_tok'][t], S['row_inst'][t]) for t in R})       # (reloaded on every call)
+        self._load_text(plan, S, user_text)
         if I > 0:
             plan.inst_time.zero_()
             plan.inst_time[:I].copy_(times.to(dev, torch.float32)[S['inst_b'], S['inst_m']])
         for t in Rp:
-            plan.row_tok[t].fill_(-1); plan.row_inst[t].zero_()
             if t in R:
                 r = R[t]
-                plan.row_tok[t][:r].copy_(S['row_tok'][t]); plan.row_inst[t][:r].copy_(S['row_inst'][t])
                 if t in plan.ext:
                     plan.lat[t]['tok'][:r].copy_(torch.cat(ext_ctx[t]['tok']))
                 else:
@@ -766,12 +794,23 @@ class Transfusion(nn.Module):
         return torch.where(prev, torch.full((), 0.5, device=self.device), cur[:, None].expand(b, m))
 
     # ------------------------------------------------------------------ forward
+    def _resolve_ema(self, ema):
+        """the teacher model behind a `velocity_consistency_ema_model` argument (None stays None)"""
+        if ema is not None and hasattr(ema, 'ema_model'):                                  # EMA wrapper, T:2967-2969
+            ema = ema.ema_model
+        if ema is not None and not isinstance(ema, Transfusion):
+            raise NotImplementedError('velocity_consistency_ema_model must be a native Transfusion (or the EMA wrapper of one)')
+        if ema is self:
+            raise ValueError('velocity_consistency_ema_model is the model itself: the teacher pass would overwrite the activations the backward needs - pass an EMA copy (create_ema)')
+        return ema
+
     def forward(self, modalities, times=None, num_modalities_to_times_fn=None, modality_type=None, cache=None, decode_length=None,
                 decoding_text_or_modality=None, velocity_consistency_ema_model=None, velocity_consistency_delta_time=1e-3,
                 return_only_pred_flows=False, return_loss=True, return_breakdown=False, return_embed=False, return_hiddens=False,
                 return_kv_cache=False, return_times=False, prob_uncond=None, _hidden_request=None):
         """`_hidden_request` (internal, SelfMaskedRepTraining): {'raw': hiddens as bf16 views of the plan's buffers, 'hiddens_only': under no_grad run the
         training layout on a plan that keeps the hiddens alone and stops at the final norm (loss = None)}; the return value then ends with (plan, n_true)"""
+        # ---- dispatch and argument checks
         self._require_gpu()
         # the reference looks its packer up in the registry on every call (get_processing_strategy, MP:1252-1256, called at T:3104-3107).  The fused
         # step packs with the native packer only (every name the reference ships maps to it): an entry someone replaced or added must not be
@@ -802,25 +841,20 @@ class Transfusion(nn.Module):
                                           'as in the reference\'s own decode calls (T:1917-1924, T:1998-2006)')
             return self._forward_decode(modalities, times, cache, decode_length, decoding_text_or_modality, return_embed=return_embed,
                                         return_kv_cache=return_kv_cache, return_hiddens=return_hiddens, return_times=return_times)
-        ema = velocity_consistency_ema_model
-        if ema is not None and hasattr(ema, 'ema_model'):                                  # EMA wrapper, T:2967-2969
-            ema = ema.ema_model
-        if ema is not None and not isinstance(ema, Transfusion):
-            raise NotImplementedError('velocity_consistency_ema_model must be a native Transfusion (or the EMA wrapper of one)')
-        if ema is self:
-            raise ValueError('velocity_consistency_ema_model is the model itself: the teacher pass would overwrite the activations the backward needs - pass an EMA copy (create_ema)')
+        ema = self._resolve_ema(velocity_consistency_ema_model)
         return_loss = (return_loss and not return_embed) or return_only_pred_flows or ema is not None
-        dev = self.device
-        stream = self._stream()
-        ps, md = self.store, self.md
+        dev, stream, md = self.device, self._stream(), self.md
+        # a teacher's pass (SelfMaskedRepTraining: no gradient, hiddens wanted, nothing else): the training LAYOUT of the batch on a plan that keeps the
+        # hiddens alone (what `training=False` plans keep) and stops at the final norm - no loss comes back
+        hreq = _hidden_request or {}
+        hid_only = train_hiddens and not torch.is_grad_enabled() and bool(hreq.get('hiddens_only')) and ema is None and not return_only_pred_flows
 
         # ---- modality types whose encoder / decoder are user modules: their part of the packing happens in PyTorch, BEFORE the structure scan
         ext_ctx = orig_times = None
         packer_in = modalities                                # what the packer sees (channel-last; `ext` types in their encoder's layout)
         if self._ext:
-            is_mod = lambda p: isinstance(p, tuple) or (torch.is_tensor(p) and p.is_floating_point())
             if times is None:                                                              # T:3075-3082 (drawn before the packing, as there)
-                num_mod = np.array([sum(1 for p in sample if is_mod(p)) for sample in modalities], dtype=np.int64)
+                num_mod = np.array([_num_modalities(sample) for sample in modalities], dtype=np.int64)
                 fn = num_modalities_to_times_fn
                 times = fn(torch.from_numpy(num_mod).to(dev)) if fn is not None else self._default_times(num_mod)
             times = times.to(dev, torch.float32)
@@ -832,16 +866,11 @@ class Transfusion(nn.Module):
         # ---- structure: one cheap signature pass; everything derived from it is cached ON THE DEVICE per signature
         sig, user_text, latents = fast_signature(modalities)
         add_meta = return_loss or not return_embed           # MP:330: `return_embed` (the decode-time call) packs WITHOUT [meta][shape][som] ... [eom]
-        skey = (sig, return_loss, add_meta)
-        S = self._struct_cache.pop(skey, None)
-        if S is None:
-            while len(self._struct_cache) >= 32:                      # least recently used structure goes first (dict order = use order)
-                self._struct_cache.pop(next(iter(self._struct_cache)))
-            # training lengths are bucketed to multiples of 64 (_TRAIN_PAD): ragged data then shares a handful of plans - a plan
-            # owns every activation of the step and its launch lists, building one costs far more than the padding columns
-            S = self._build_structure(modalities, return_loss, add_meta=add_meta, pad_n=_TRAIN_PAD if return_loss else 1, presig=(sig, user_text, latents))
-        self._struct_cache[skey] = S
-        P, tm, b, n, I, R = S['P'], S['tm'], S['b'], S['n'], S['I'], S['R']
+        # training lengths are bucketed to multiples of 64 (_TRAIN_PAD): ragged data then shares a handful of plans - a plan
+        # owns every activation of the step and its launch lists, building one costs far more than the padding columns
+        S = self._structure((sig, return_loss, add_meta), lambda: self._build_structure(
+            modalities, return_loss, add_meta=add_meta, pad_n=_TRAIN_PAD if return_loss else 1, presig=(sig, user_text, latents)))
+        P, I = S['P'], S['I']
         self._live_n_true = S['n_true']
 
         # ---- times (T:3075-3082)
@@ -853,57 +882,87 @@ class Transfusion(nn.Module):
             orig_times = times.clone()
             times = times * (1. - velocity_consistency_delta_time)
 
-        ps.refresh_shadows(stream)
+        # ---- plan
+        self.store.refresh_shadows(stream)
+        plan = self._step_plan(S, return_loss, hid_only, no_teacher=ema is None and not return_only_pred_flows)
+        if train_hiddens and not hid_only and torch.is_grad_enabled() and not plan.pull:
+            raise NotImplementedError('return_hiddens next to the loss (hidden taps) needs the pull-form AttentionResidual backward: depth <= 32 and dim <= 1024 '
+                                      '(under torch.no_grad() the hiddens come back without a tap)')
+
+        # ---- inputs onto the plan: token ids (values never visit the host), CFG drop, labels, instance times, latent rows, noise
+        prob_uncond = self.prob_uncond if prob_uncond is None else prob_uncond
+        self._load_text(plan, S, user_text, prob_uncond if self.training else 0., labels=return_loss)
+        if I > 0:
+            plan.inst_time[:I].copy_(times[S['inst_b'], S['inst_m']])
+        rows_in = self._load_latents(plan, S, latents, ext_ctx, return_loss)
+
+        # ---- outputs: inference | hiddens only | pred flows | losses
+        if not return_loss:
+            Plan.run(plan.fwd, stream, 0, plan.fwd_embed_end if return_embed else plan.fwd_logits_end)
+            if not return_embed:
+                return _pack_outputs(self._logits_out(plan), (return_times, times))
+            flows = self._pred_flow_closures(P, self._clean_sources(packer_in, times) if md.model_output_clean else None)
+            return _pack_outputs((self._embed_out(plan), flows), (return_times, times))   # T:3275-3276: (embed, get_pred_flows)
+        hid = None
+        if train_hiddens:         # return_hiddens = True: all depth + 2 of them, fp32 like the reference's; an iterable of indices: those alone (None elsewhere)
+            hid = (list(range(md.depth + 2)) if return_hiddens is True else sorted({int(k) % (md.depth + 2) for k in return_hiddens}), bool(hreq.get('raw')))
+        if hid_only:
+            Plan.run(plan.fwd, stream, 0, plan.fwd_embed_end)
+            hiddens = self._hiddens_list(hid, self._hiddens_out(plan, S['n_true'], *hid))
+            return _pack_outputs(None, (True, hiddens), (return_times, times), (_hidden_request is not None, (plan, S['n_true'])))
+        if return_only_pred_flows:                                                        # T:3313-3316 (the EMA teacher's call)
+            return self._pred_flows_out(plan, S, ext_ctx)
+        def teacher_flows():                                                               # T:3383-3418; called behind the student's forward
+            with _teacher_pass(ema, flat_pred_flows=True):
+                return ema(velocity_modalities, times=orig_times + velocity_consistency_delta_time, return_only_pred_flows=True)
+        loss, breakdown, hid_out = self._losses(plan, S, ext_ctx, rows_in, teacher_flows if ema is not None else None, hid)
+        # T:3433-3450: loss[, breakdown], hiddens[, times]
+        return _pack_outputs(loss, (return_breakdown, breakdown), (train_hiddens, self._hiddens_list(hid, hid_out)), (return_times, times),
+                             (_hidden_request is not None, (plan, S['n_true'])))
+
+    def _step_plan(self, S, return_loss, hid_only, no_teacher):
+        """the plan of an interleaved `forward` step with the structure S loaded.  `no_teacher`: no EMA teacher and not a teacher's own `return_only_pred_flows` call."""
+        md, I, R = self.md, S['I'], S['R']
         # Ragged corpora change the number of modality instances and of latent rows with every batch.  A training plan owns every activation of the
         # step and its launch lists (building one costs far more than a step), so in the plain training case the plan is built for both counts ROUNDED
         # UP - in steps of a quarter of the count's power of two, at least 64 instances / 256 rows per type (`_bucket`) - and shared: padding instances are referenced by no token (their table gradients stay zero),
         # padding rows scatter nowhere and are kept out of the losses (engine.Plan.set_rows).  TFX_PLAN_BUCKETS=0: exact counts (one plan per pair).
-        # a teacher's pass (SelfMaskedRepTraining: no gradient, hiddens wanted, nothing else): the training LAYOUT of the batch on a plan that keeps the
-        # hiddens alone (what `training=False` plans keep) and stops at the final norm - no loss comes back
-        # (bucketed like the training plan, so ragged corpora share it: padding rows scatter nowhere and set_rows keeps them out of the noising)
-        hreq = _hidden_request or {}
-        hid_only = train_hiddens and not torch.is_grad_enabled() and bool(hreq.get('hiddens_only')) and ema is None and not return_only_pred_flows
-        bucket = (return_loss and not self._ext and not md.pos_types and ema is None and not return_only_pred_flows and not self.has_recon_loss
+        # (a hiddens-only pass is bucketed like the training plan, so ragged corpora share it: padding rows scatter nowhere and set_rows keeps them out of the noising)
+        bucket = (return_loss and no_teacher and not self._ext and not md.pos_types and not self.has_recon_loss
                   and not md.model_output_clean and os.environ.get('TFX_PLAN_BUCKETS', '1') != '0')
         Ip = _bucket(I, 64) if (bucket and I > 0) else I
         Rp = {t: _bucket(r, 256) for t, r in R.items()} if bucket else R
-        plan = self._plan(b, n, Ip, Rp, training=return_loss and not hid_only)
-        if train_hiddens and not hid_only and torch.is_grad_enabled() and not plan.pull:
-            raise NotImplementedError('return_hiddens next to the loss (hidden taps) needs the pull-form AttentionResidual backward: depth <= 32 and dim <= 1024 '
-                                      '(under torch.no_grad() the hiddens come back without a tap)')
+        plan = self._plan(S['b'], S['n'], Ip, Rp, training=return_loss and not hid_only)
         if return_loss and not hid_only:
             plan.clear_taps()                               # a tap lives for the step that set it
         if md.model_output_clean:
             plan.set_clean_mode('model')                    # interleaved path: the model-space conversion (MP:786-792)
         if plan.loaded_structure is not S:
-            plan.set_rope_tables(*self._rope_tables(int(tm.rot_pos.max()) if tm.rot_pos.size else 0))
-            plan.tok_inst.copy_(S['tok_inst'].view(-1)); plan.kv_end.copy_(S['kv_end']); plan.q_start.copy_(S['q_start']); plan.rot_pos.copy_(S['rot_pos'])
-            plan.set_segments(S['seg_start'], S['seg_len'])
-            for t, r in R.items():
-                if r < Rp[t]:
-                    plan.row_tok[t].fill_(-1); plan.row_inst[t].zero_()
-                plan.row_tok[t][:r].copy_(S['row_tok'][t]); plan.row_inst[t][:r].copy_(S['row_inst'][t])
-            if return_loss:
-                plan.set_rows(R)
-            plan.loaded_structure = S
+            tm = S['tm']
+            plan.load_structure(S, self._rope_tables(int(tm.rot_pos.max()) if tm.rot_pos.size else 0), S['tok_inst'], S['kv_end'], S['q_start'], S['rot_pos'],
+                                segments=(S['seg_start'], S['seg_len']), rows={t: (S['row_tok'][t], S['row_inst'][t]) for t in R}, set_rows=return_loss)
+        return plan
 
-        # ---- token ids on device (values never visit the host)
+    def _load_text(self, plan, S, user_text, prob_uncond=0., labels=False):
+        """token ids of a scanned batch onto its plan, on the device: the structure's own tokens with the caller's text scattered in, the CFG text
+        drop (`prob_uncond` > 0), and with `labels` the next-token labels"""
+        dev, n = self.device, S['n']
         text_full = S['text_host'].clone()
         if user_text:
-            vals = torch.cat(user_text).to(dev, torch.int32)
-            text_full.view(-1).index_copy_(0, S['text_dest'], vals)
-        prob_uncond = self.prob_uncond if prob_uncond is None else prob_uncond
-        if self.training and prob_uncond > 0:                                              # CFG text drop, T:3027-3043
-            drop_rows = torch.rand(b, device=dev) < prob_uncond
+            text_full.view(-1).index_copy_(0, S['text_dest'], torch.cat(user_text).to(dev, torch.int32))
+        if prob_uncond > 0:                                                                # CFG text drop, T:3027-3043
+            drop_rows = torch.rand(S['b'], device=dev) < prob_uncond
             text_full = text_full.masked_fill(S['cfg_droppable'] & drop_rows[:, None], self.null_text_id)
         plan.text_ids.copy_(text_full[:, :n].reshape(-1))
-        if return_loss:
+        if labels:
             lab = text_full[:, 1:]                                                          # T:3144
             lab = torch.where(S['is_mod'] | (lab == self.null_text_id), S['minus1'], lab)    # T:3320-3323
             plan.labels.copy_(lab.reshape(-1))
-        if I > 0:
-            plan.inst_time[:I].copy_(times[S['inst_b'], S['inst_m']])
-        rows_in = []                                                      # rows PyTorch hands to the engine: (kind, type, tensor with autograd history)
+
+    def _load_latents(self, plan, S, latents, ext_ctx, return_loss):
+        """latent rows and their noise onto the plan.  Returns the rows PyTorch hands to the engine: (kind, type, tensor with autograd history)"""
+        P, I, R = S['P'], S['I'], S['R']
+        rows_in = []
         for t in R:
             lt = plan.lat[t]
             if t in plan.ext_add:                                         # axial positional embedding of the (projected) instance shapes
@@ -917,182 +976,154 @@ class Transfusion(nn.Module):
                 continue
             lt['x'][:R[t]].copy_(torch.cat(latents[t]), non_blocking=True)   # one cat on the source device, one transfer
             if return_loss:
-                if self._noise_override is not None:
-                    lt['eps'][:R[t]].copy_(self._noise_override[t])
-                else:
-                    lt['eps'][:R[t]].normal_()                                              # MP:654 (the REAL rows only: the RNG stream a seed consumes does not depend on the plan's bucket padding)
+                self._fill_noise(lt['eps'][:R[t]], t)                       # MP:654 (the REAL rows only: the RNG stream a seed consumes does not depend on the plan's bucket padding)
             # without a loss there is no noising (MP:658-660): noise_mix with eps = NULL copies x
             plan.set_noise(t, lt['eps'].data_ptr() if return_loss else None)
+        return rows_in
 
-        if not return_loss:
-            end = plan.fwd_embed_end if return_embed else plan.fwd_logits_end
-            Plan.run(plan.fwd, stream, 0, end)
-            if return_embed:                                                               # T:3275-3276: (embed, get_pred_flows)
-                out = (plan.embed.view(b, n, md.dim).float(), self._pred_flow_closures(P, self._clean_sources(packer_in, times) if md.model_output_clean else None))
-                return out if not return_times else (out, times)
-            logits = plan.logits.view(b, n, md.vp)[..., :md.vocab].clone()
-            return (logits, times) if return_times else logits
+    def _fill_noise(self, eps, t, reshape=False):
+        """this step's noise of type t into (the real rows of) a plan's `eps` buffer: drawn on the device, or the test hook's (`reshape`: in any layout)"""
+        if self._noise_override is None:
+            eps.normal_()
+        else:
+            eps.copy_(self._noise_override[t].reshape(eps.shape) if reshape else self._noise_override[t])
 
-        if hid_only:
-            Plan.run(plan.fwd, stream, 0, plan.fwd_embed_end)
-            hid_idx = list(range(md.depth + 2)) if return_hiddens is True else sorted({int(k) % (md.depth + 2) for k in return_hiddens})
-            hiddens = [None] * (md.depth + 2)
-            for k, h in zip(hid_idx, self._hiddens_out(plan, S['n_true'], hid_idx, bool(hreq.get('raw')))):
-                hiddens[k] = h
-            ret = (None, hiddens, times) if return_times else (None, hiddens)
-            return (*ret, (plan, S['n_true'])) if _hidden_request is not None else ret
+    def _pred_flows_out(self, plan, S, ext_ctx):
+        """`return_only_pred_flows`: per type the predicted flows of its instances in scan order (or, for `_teacher_pass`, the plan's packed rows)"""
+        md, P, R = self.md, S['P'], S['R']
+        Plan.run(plan.fwd, self._stream(), 0, plan.fwd_pred_end)
+        # types with user modules: their decoder on the embedding rows of every instance, in PyTorch (the teacher's call runs under no_grad)
+        ext_preds = {t: self._ext_decode(t, plan.embed.index_select(0, plan.row_tok[t].long().clamp(min=0)).float(), ext_ctx[t]) for t in R if t in plan.ext}
+        if self._flat_pred_flows:
+            return {t: (ext_preds[t] if t in plan.ext else plan.lat[t]['pred']) for t in R}
+        out = [[] for _ in range(self.num_modalities)]
+        cursor = {t: 0 for t in R}
+        for gi in range(len(P.inst_b)):
+            t, L = int(P.inst_type[gi]), int(P.inst_len[gi])
+            if t in plan.ext:
+                out[t].append(ext_preds[t][cursor[t]]); cursor[t] += 1
+                continue
+            rows = plan.lat[t]['pred'][cursor[t]:cursor[t] + L]; cursor[t] += L
+            out[t].append(self._from_channel_last(t, rows.view(*P.inst_shape[gi], md.dim_latents[t]).clone()))
+        return out
 
-        if return_only_pred_flows:                                                        # T:3313-3316 (the EMA teacher's call)
-            Plan.run(plan.fwd, stream, 0, plan.fwd_pred_end)
-            # types with user modules: their decoder on the embedding rows of every instance, in PyTorch (the teacher's call runs under no_grad)
-            ext_preds = {t: self._ext_decode(t, plan.embed.index_select(0, plan.row_tok[t].long().clamp(min=0)).float(), ext_ctx[t]) for t in R if t in plan.ext}
-            if getattr(self, '_flat_pred_flows', False):
-                return {t: (ext_preds[t] if t in plan.ext else plan.lat[t]['pred']) for t in R}
-            out = [[] for _ in range(self.num_modalities)]
-            cursor = {t: 0 for t in R}
-            for gi in range(len(P.inst_b)):
-                t, L = int(P.inst_type[gi]), int(P.inst_len[gi])
-                if t in plan.ext:
-                    out[t].append(ext_preds[t][cursor[t]]); cursor[t] += 1
-                    continue
-                rows = plan.lat[t]['pred'][cursor[t]:cursor[t] + L]; cursor[t] += L
-                out[t].append(self._from_channel_last(t, rows.view(*P.inst_shape[gi], md.dim_latents[t]).clone()))
-            return out
-
+    def _losses(self, plan, S, ext_ctx, rows_in, teacher_flows, hid):
+        """the training step from the loaded plan to the loss: forward, the native loss terms (text, then per ascending type flow, velocity
+        consistency against `teacher_flows()`, reconstruction), the step's closing, then the terms of the types whose decoder is a user module.
+        Returns (loss, LossBreakdown, the hiddens of `hid` = (indices, raw) | [])."""
+        md, M, stream, acc = self.md, self.num_modalities, self._stream(), plan.acc
+        P, tm, R = S['P'], S['tm'], S['R']
         # ---- loss seeds (the token-count normalisers cancel: d loss / d logit = w / total_tokens, T:3331)
         total = float(P.total_tokens)
-        mse_scales = {}
-        for t, r in R.items():
-            if t in plan.ext:
-                continue
-            w_t = float(tm.is_type[t]) / total                                              # T:3343
-            mse_scales[t] = 2.0 * self.flow_loss_weight * w_t / (r * md.dim_latents[t])
-        plan.set_loss_scales(self.text_loss_weight / total, mse_scales)
+        w = {t: float(tm.is_type[t]) / total for t in R}                                   # T:3343
+        native = [t for t in sorted(R) if t not in plan.ext]
+        den = {t: R[t] * md.dim_latents[t] for t in native}
+        plan.set_loss_scales(self.text_loss_weight / total, {t: 2.0 * self.flow_loss_weight * w[t] / den[t] for t in native})
         plan.set_ce_vocab(md.vocab)
         self._bwd_scale = None
         plan.acc.zero_()
         Plan.run(plan.fwd, stream, graph='auto')
 
-        acc = plan.acc
         text_loss = acc[0] / acc[1].clamp(min=1.)
         loss = self.text_loss_weight * acc[0] / total
         flow_losses = {}
-        for t, r in sorted(R.items()):
-            if t in plan.ext:
-                continue
-            fl = acc[2 + t] / (r * md.dim_latents[t])
-            flow_losses[t] = fl
-            loss = loss + self.flow_loss_weight * fl * (float(tm.is_type[t]) / total)
+        for t in native:
+            flow_losses[t] = acc[2 + t] / den[t]
+            loss = loss + self.flow_loss_weight * flow_losses[t] * w[t]
 
         velocity_losses = None
-        if ema is not None:                                                                # T:3383-3418
-            M = self.num_modalities
-            was_training = ema.training
-            ema.eval()
-            ema._flat_pred_flows = True
-            try:
-                with torch.no_grad():
-                    teacher = ema(velocity_modalities, times=orig_times + velocity_consistency_delta_time, return_only_pred_flows=True)
-            finally:
-                ema._flat_pred_flows = False
-                ema.train(was_training)
+        if teacher_flows is not None:                                                      # T:3383-3418
+            teacher = teacher_flows()
             velocity_losses = {}
-            for t, r in sorted(R.items()):
-                if t in plan.ext:                         # the student's side of these needs the user's decoder: below, with the flow loss
-                    continue
-                w_t = float(tm.is_type[t]) / total
+            for t in native:                              # (the student's side of the other types needs the user's decoder: below, with the flow loss)
                 plan.lat[t]['vel'].copy_(teacher[t])
                 va = plan._vel_args[t]
                 va.pred, va.flow = plan.lat[t]['pred'].data_ptr(), plan.lat[t]['vel'].data_ptr()
-                va.grad_scale = 2.0 * self.velocity_consistency_loss_weight * w_t / (r * md.dim_latents[t])
+                va.grad_scale = 2.0 * self.velocity_consistency_loss_weight * w[t] / den[t]
             Plan.run(plan.vel, stream)
-            for t, r in sorted(R.items()):
-                if t in plan.ext:
-                    continue
-                vl = plan.acc[2 + M + t] / (r * md.dim_latents[t])
-                velocity_losses[t] = vl
-                loss = loss + self.velocity_consistency_loss_weight * vl * (float(tm.is_type[t]) / total)
+            for t in native:
+                velocity_losses[t] = acc[2 + M + t] / den[t]
+                loss = loss + self.velocity_consistency_loss_weight * velocity_losses[t] * w[t]
 
         recon_losses = {}
         if self.has_recon_loss:                                                            # T:3420-3431
-            M = self.num_modalities
-            for t, r in sorted(R.items()):
-                if t in plan.ext:
-                    continue
-                w_t = float(tm.is_type[t]) / total
+            for t in native:
                 plan.lat[t]['recw'].copy_(S['recw'][t])
                 ra = plan._rec_args[t]
-                ra.recon_mode, ra.grad_scale = 0, 2.0 * self.reconstruction_loss_weight * w_t / md.dim_latents[t]
+                ra.recon_mode, ra.grad_scale = 0, 2.0 * self.reconstruction_loss_weight * w[t] / md.dim_latents[t]
             Plan.run(plan.rec, stream)
-            for t, r in sorted(R.items()):
-                if t in plan.ext:
-                    continue
-                recon_losses[t] = plan.acc[2 + 2 * M + t] / md.dim_latents[t]
-                loss = loss + self.reconstruction_loss_weight * recon_losses[t] * (float(tm.is_type[t]) / total)
+            for t in native:
+                recon_losses[t] = acc[2 + 2 * M + t] / md.dim_latents[t]
+                loss = loss + self.reconstruction_loss_weight * recon_losses[t] * w[t]
 
-        self._step_id += 1
-        self._live = (plan, self._step_id)
         ext_out = sorted(plan.ext)
-        hiddens = None
-        if train_hiddens:
-            # return_hiddens = True: all depth + 2 of them, fp32 like the reference's; an iterable of indices: those alone (None elsewhere)
-            hid_idx = list(range(md.depth + 2)) if return_hiddens is True else sorted({int(k) % (md.depth + 2) for k in return_hiddens})
-            hid_raw = bool(hreq.get('raw'))
-        if torch.is_grad_enabled():
-            if self._anchor is None or self._anchor.device != dev:
-                self._anchor = torch.zeros((), device=dev, requires_grad=True)
-            spec = {'in': [(k, t) for k, t, _ in rows_in], 'out': ext_out} if (rows_in or ext_out) else _NO_ROWS
-            if train_hiddens:
-                spec = dict(spec, hid=(hid_idx, hid_raw))
-            loss, *emb_rows = _NativeLoss.apply(self._anchor, self, loss, spec, *[r for _, _, r in rows_in])
-            if train_hiddens:
-                emb_rows, hid_out = emb_rows[:len(ext_out)], emb_rows[len(ext_out):]
-        else:
-            emb_rows = [plan.embed.index_select(0, plan.row_tok[t].long().clamp(min=0)).float() for t in ext_out]
-            if train_hiddens:
-                hid_out = self._hiddens_out(plan, S['n_true'], hid_idx, hid_raw)
-        if train_hiddens:
-            hiddens = [None] * (md.depth + 2)
-            for k, h in zip(hid_idx, hid_out):
-                hiddens[k] = h
-        for t, rows in zip(ext_out, emb_rows):                                              # the user's decoders and their flow losses, in PyTorch
+        loss, outs = self._close_step(plan, loss, rows_in, ext_out, hid, S['n_true'])
+        for t, rows in zip(ext_out, outs):                                                  # the user's decoders and their flow losses, in PyTorch
             preds = self._ext_decode(t, rows, ext_ctx[t])
             fl, rec = self._ext_flow_loss(t, preds, ext_ctx[t])
             flow_losses[t] = fl
-            loss = loss + self.flow_loss_weight * fl * (float(tm.is_type[t]) / total)
+            loss = loss + self.flow_loss_weight * fl * w[t]
             if rec is not None:
                 recon_losses[t] = rec
-                loss = loss + self.reconstruction_loss_weight * rec * (float(tm.is_type[t]) / total)
-            if ema is not None:                                                             # T:3397-3411: mse(student flows, teacher flows), all instances of the type packed
+                loss = loss + self.reconstruction_loss_weight * rec * w[t]
+            if teacher_flows is not None:                                                   # T:3397-3411: mse(student flows, teacher flows), all instances of the type packed
                 vl = torch.nn.functional.mse_loss(torch.cat([p.reshape(-1) for p in preds]), torch.cat([p.reshape(-1) for p in teacher[t]]))
                 velocity_losses[t] = vl
-                loss = loss + self.velocity_consistency_loss_weight * vl * (float(tm.is_type[t]) / total)
-        if velocity_losses is not None:
-            velocity_losses = [velocity_losses[t] for t in sorted(velocity_losses)]
-        flow_losses = [flow_losses[t] for t in sorted(flow_losses)]
-        recon_losses = [recon_losses[t] for t in sorted(recon_losses)] if self.has_recon_loss else None
-        if not return_breakdown and not return_times and hiddens is None and _hidden_request is None:
-            return loss
-        ret = (loss,)
-        if return_breakdown:
-            ret = (*ret, LossBreakdown(loss, text_loss, flow_losses, velocity_losses, recon_losses))
-        if hiddens is not None:                                                            # T:3433-3450: loss[, breakdown], hiddens[, times]
-            ret = (*ret, hiddens)
-        if return_times:
-            ret = (*ret, times)
-        if _hidden_request is not None:
-            ret = (*ret, (plan, S['n_true']))
-        return ret
+                loss = loss + self.velocity_consistency_loss_weight * vl * w[t]
+        by_type = lambda d: [d[t] for t in sorted(d)]
+        breakdown = LossBreakdown(loss, text_loss, by_type(flow_losses), by_type(velocity_losses) if velocity_losses is not None else None,
+                                  by_type(recon_losses) if self.has_recon_loss else None)
+        return loss, breakdown, outs[len(ext_out):]
 
-    def _hiddens_out(self, plan, n_true, indices, raw=False):
-        """hiddens = [x_0 .. x_depth, final norm output] (T:1199, T:1244, T:1253) of the plan's latest forward, cut to the n real columns of its
-        bucketed rows: fp32 copies, or (raw) bf16 views of the plan's own buffers - valid until the plan's next forward"""
+    def _close_step(self, plan, loss, rows_in=(), out_types=(), hid=None, n_true=None):
+        """close a training step: `plan` holds the live activations of step `_step_id`, and with gradients enabled the loss goes through `_NativeLoss`
+        (`rows_in`: (kind, type, rows PyTorch produced), `out_types`: types whose embedding rows go out to a user decoder, `hid`: (indices, raw) of
+        the hiddens wanted, cut to `n_true` columns).  Returns (loss, [embedding rows per out type ..., hiddens ...]) - under no_grad the same tensors without a graph."""
+        self._step_id += 1
+        self._live = (plan, self._step_id)
+        if torch.is_grad_enabled():
+            if self._anchor is None or self._anchor.device != self.device:
+                self._anchor = torch.zeros((), device=self.device, requires_grad=True)
+            spec = {'in': [(k, t) for k, t, _ in rows_in], 'out': list(out_types)} if (rows_in or out_types) else _NO_ROWS
+            if hid:
+                spec = dict(spec, hid=hid)
+            loss, *outs = _NativeLoss.apply(self._anchor, self, loss, spec, *[r for _, _, r in rows_in])
+            return loss, outs
+        outs = [plan.embed.index_select(0, plan.row_tok[t].long().clamp(min=0)).float() for t in out_types]
+        return loss, outs + (self._hiddens_out(plan, n_true, *hid) if hid else [])
+
+    def _hiddens_list(self, hid, tensors):
+        """the depth + 2 long list `return_hiddens` hands out: the tensors at the indices of `hid` = (indices, raw), None elsewhere"""
+        if hid is None:
+            return None
+        hiddens = [None] * (self.md.depth + 2)
+        for k, h in zip(hid[0], tensors):
+            hiddens[k] = h
+        return hiddens
+
+    def _hiddens_out(self, plan, n_true, indices=None, raw=False):
+        """hiddens = [x_0 .. x_depth, final norm output] (T:1199, T:1244, T:1253) of the plan's latest forward (all of them, or those of `indices`), cut
+        to the n real columns of its bucketed rows: fp32 copies, or (raw) bf16 views of the plan's own buffers - valid until the plan's next forward"""
         md = self.md
-        out = []
-        for k in indices:
-            h = (plan.embed if k == md.depth + 1 else plan.hid[k]).view(plan.b, plan.n, md.dim)[:, :n_true]
-            out.append(h if raw else h.float())
-        return out
+        hs = [(plan.embed if k == md.depth + 1 else plan.hid[k]).view(plan.b, plan.n, md.dim)[:, :n_true] for k in (range(md.depth + 2) if indices is None else indices)]
+        return hs if raw else [h.float() for h in hs]
+
+    def _logits_out(self, plan, n_true=None):
+        """the logits of the plan's latest forward over the real vocabulary (b, n real columns, V): an fp32 copy"""
+        return plan.logits.view(plan.b, plan.n, self.md.vp)[:, :n_true, :self.md.vocab].clone()
+
+    def _embed_out(self, plan, n_true=None):
+        """the final embedding of the plan's latest forward (b, n real columns, dim): an fp32 copy"""
+        return plan.embed.view(plan.b, plan.n, self.md.dim)[:, :n_true].float()
+
+    def _kv_from_plan(self, plan, n_true):
+        """a public kv cache from a full-forward plan: a fresh native buffer with room for 64 more tokens, filled with the plan's keys / values, its
+        first `n_true` positions handed out (`_kv_public`)"""
+        from .sampling import Sampler
+        buf = torch.zeros(self.md.depth, plan.b, -(-(plan.n + 64) // 64) * 64, 2 * self.md.hdk, device=self.device, dtype=torch.bfloat16)
+        Sampler(self)._fill_cache(buf, plan, plan.b, plan.n)
+        buf._tfx_filled = n_true
+        return self._kv_public(buf, n_true)
 
     # ------------------------------------------------------------------ decode contract of forward() (T:2926-2948, T:3186-3271)
     def _pred_flow_closures(self, P, clean_src=None):
@@ -1203,38 +1234,29 @@ class Transfusion(nn.Module):
         from .sampling import Sampler
         md, dev, stream = self.md, self.device, self._stream()
         assert isinstance(modalities, list), 'the decode forward takes the list-of-samples input'
-        b = len(modalities)
+        b, kv = len(modalities), None
         if cache is None:
             if times is None:
-                nm = max((sum(1 for p in s if isinstance(p, tuple) or (torch.is_tensor(p) and p.is_floating_point())) for s in modalities), default=0)
-                times = self._default_times(np.array([sum(1 for p in s if isinstance(p, tuple) or (torch.is_tensor(p) and p.is_floating_point()))
-                                                     for s in modalities])) if nm else torch.empty((b, 0), device=dev)
+                times = self._default_times(np.array([_num_modalities(s) for s in modalities], dtype=np.int64))
             # lengths are bucketed to multiples of 64 (an un-cached decode loop calls this once per token: one plan per bucket, not per length);
             # the padding columns sit behind every real token and are cut off again below
             plan, S = self._forward_plain(modalities, times, add_meta=not return_embed, pad_n=64)
-            n_pad, n, P, tm = S['n'], S['n_true'], S['P'], S['tm']
-            out = (plan.embed.view(b, n_pad, md.dim)[:, :n].float(),
-                   self._pred_flow_closures(P, self._clean_sources(modalities, times) if md.model_output_clean else None)) if return_embed \
-                else plan.logits.view(b, n_pad, md.vp)[:, :n, :md.vocab].clone()
-            kv = None
+            n, P, clean_times = S['n_true'], S['P'], times
             if return_kv_cache:
-                buf = torch.zeros(md.depth, b, -(-(n_pad + 64) // 64) * 64, 2 * md.hdk, device=dev, dtype=torch.bfloat16)
-                Sampler(self)._fill_cache(buf, plan, b, n_pad)
-                buf._tfx_filled = n
-                rp = tm.rot_pos.reshape(b, n_pad)[:, :n]
-                kv = (self._kv_public(buf, n), int(rp.max()) + 1 if rp.size else 0)
+                rp = S['tm'].rot_pos.reshape(b, S['n'])[:, :n]
+                kv = (self._kv_from_plan(plan, n), int(rp.max()) + 1 if rp.size else 0)
         else:
             assert decode_length is not None, '`decode_length` must be passed in on forward for modality sampling. think of a cleaner way on some future date'   # T:3191
             assert decoding in ('text', 'modality')                                                                                                          # T:3192
             kv_in, seen = cache
-            L = 1 if decoding == 'text' else int(decode_length)
+            is_mod = decoding == 'modality'
+            n = L = int(decode_length) if is_mod else 1
             buf, n_cached = self._kv_native(kv_in, L)
             assert buf.shape[1] == b, 'kv cache batch does not match the number of samples'
             T = b * L
-            if not hasattr(self, '_decode_plans') or len(self._decode_plans) > 8:
+            if len(self._decode_plans) > 8:
                 self._decode_plans = {}
             smp = Sampler(self)
-            is_mod = decoding == 'modality'
             plan = smp._decode_plan(('fwd', decoding, L, buf.data_ptr()), b, L, buf, is_mod)
             ids = np.zeros(T, np.int32); tok_inst = np.full(T, -1, np.int32)
             pos = (np.arange(b, dtype=np.int32)[:, None] * buf.shape[2] + n_cached + np.arange(L, dtype=np.int32)[None, :]).reshape(-1)
@@ -1243,66 +1265,60 @@ class Transfusion(nn.Module):
                     last = sample[-1]
                     assert is_int_tensor(last) and last.numel() > 0, 'decoding text: every sample must end in a text token'
                     ids[i] = int(last.reshape(-1)[-1])
-                kve = np.full(T, n_cached + 1, np.int32)
-                rot = np.full(T, seen, np.int32)
             else:
-                tys = []
-                for i, sample in enumerate(modalities):
-                    last = sample[-1]
-                    last = (0, last) if torch.is_tensor(last) and last.is_floating_point() else last
-                    assert isinstance(last, tuple), 'decoding a modality: every sample must end in the modality being decoded'
-                    ty, x = int(last[0]), last[1]
-                    if ty in self._ext:                                    # the user's encoder makes the block's token rows (encoder layout in)
-                        x = x.to(dev, torch.float32)
-                        pre = self.latent_to_model_projs[ty]
-                        x = pre(x[None])[0] if self.channel_first_latent[ty] else pre(x)
-                    assert int(np.prod(x.shape[:-1])) == L, '`decode_length` must be the number of tokens of the trailing modality'
-                    tys.append((ty, x))
-                    tok_inst[i * L:(i + 1) * L] = i
-                kve = np.full(T, n_cached + L, np.int32)                   # own prefix + the whole (bidirectional) block
-                rot = np.full(T, seen, np.int32)                           # all tokens of the instance share one rotary position (T:3206)
-                row_tok = {t: np.full(T, -1, np.int32) for t in range(self.num_modalities)}
-                for t in plan.ext_add:
-                    plan.lat[t]['add'].zero_()
-                for i, (ty, x) in enumerate(tys):
-                    row_tok[ty][i * L:(i + 1) * L] = np.arange(i * L, (i + 1) * L)
-                    plan.lat[ty]['tok' if ty in plan.ext else 'x'][i * L:(i + 1) * L].copy_(x.reshape(L, -1).to(dev, torch.float32))
-                    if ty in plan.ext_add:                                # the decoded block's positional embedding (T:3179-3180 under the decode slice T:1167-1176)
-                        plan.lat[ty]['add'][i * L:(i + 1) * L].copy_(self._pos_rows(ty, [tuple(x.shape[:-1])]))
-                up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-                for t in row_tok:
-                    plan.row_tok[t].copy_(up(row_tok[t])); plan.row_src[t].copy_(up(np.maximum(row_tok[t], 0)))
-                    plan.row_inst[t].copy_(up(np.repeat(np.arange(b, dtype=np.int32), L)))
-                    if t not in plan.ext:
-                        plan.set_noise(t, None)
-                assert times is not None, 'decoding a modality needs `times` (the ODE step time in the last column, T:1990-1996)'
-                plan.inst_time.copy_(times.to(dev, torch.float32).reshape(b, -1)[:, -1])
-            smp._load(plan, ids=ids, pos=pos, kve=kve, rot=rot, tok_inst=tok_inst)
+                self._load_decode_block(plan, modalities, times, L)
+                tok_inst = np.repeat(np.arange(b, dtype=np.int32), L)
+            # text: the token sees its own prefix; modality: own prefix + the whole (bidirectional) block, all of whose tokens share one rotary position (T:3206)
+            smp._load(plan, ids=ids, pos=pos, kve=np.full(T, n_cached + L, np.int32), rot=np.full(T, seen, np.int32), tok_inst=tok_inst)
             Plan.run(plan.fwd, stream, 0, plan.fwd_embed_end if return_embed else plan.fwd_logits_end)
-            n = L
             if return_embed:
                 scan_in = modalities
                 if self._ext:                                                  # the closures reshape to the PROJECTED axial shapes (MP:738-741)
                     with torch.no_grad():
                         scan_in, _ = self._ext_preprocess(modalities, None, return_loss=False)
                 P = self._scan(scan_in, add_sos_eos=False, add_meta=False)
-                out = (plan.embed.view(b, L, md.dim).float(),
-                       self._pred_flow_closures(P, self._clean_sources(modalities, times.to(dev, torch.float32).reshape(b, -1) if times is not None else None) if md.model_output_clean else None))
-            else:
-                out = plan.logits.view(b, L, md.vp)[..., :md.vocab].clone()
-            kv = None
+                clean_times = times.to(dev, torch.float32).reshape(b, -1) if times is not None else None
             buf._tfx_filled = n_cached + L
             if return_kv_cache:
                 kv = (self._kv_public(buf, n_cached + L), seen + 1 if is_mod else seen + L)
-        ret = (out,)
-        if return_kv_cache:
-            ret = (*ret, kv)
-        if return_hiddens:                                                     # hiddens = [x_0 .. x_depth, final norm output] (T:1199, T:1244, T:1253)
-            nn_ = plan.T // b                                                     # the plan's (bucketed) row length; only the n real tokens go out
-            ret = (*ret, [plan.hid[i].view(b, nn_, md.dim)[:, :n].float() for i in range(md.depth + 1)] + [plan.embed.view(b, nn_, md.dim)[:, :n].float()])
-        if return_times:
-            ret = (*ret, times)
-        return ret[0] if len(ret) == 1 else ret
+        if return_embed:
+            out = (self._embed_out(plan, n), self._pred_flow_closures(P, self._clean_sources(modalities, clean_times) if md.model_output_clean else None))
+        else:
+            out = self._logits_out(plan, n)
+        # hiddens = [x_0 .. x_depth, final norm output] (T:1199, T:1244, T:1253): of the plan's (bucketed) rows only the n real tokens go out
+        return _pack_outputs(out, (return_kv_cache, kv), (return_hiddens, self._hiddens_out(plan, n) if return_hiddens else None), (return_times, times))
+
+    def _load_decode_block(self, plan, modalities, times, L):
+        """the trailing modality block of every sample (L tokens each) onto a cached-decode plan: latent / token rows, row maps, the block's time"""
+        dev, b = self.device, len(modalities)
+        tys = []
+        for i, sample in enumerate(modalities):
+            last = sample[-1]
+            last = (0, last) if torch.is_tensor(last) and last.is_floating_point() else last
+            assert isinstance(last, tuple), 'decoding a modality: every sample must end in the modality being decoded'
+            ty, x = int(last[0]), last[1]
+            if ty in self._ext:                                    # the user's encoder makes the block's token rows (encoder layout in)
+                x = x.to(dev, torch.float32)
+                pre = self.latent_to_model_projs[ty]
+                x = pre(x[None])[0] if self.channel_first_latent[ty] else pre(x)
+            assert int(np.prod(x.shape[:-1])) == L, '`decode_length` must be the number of tokens of the trailing modality'
+            tys.append((ty, x))
+        row_tok = {t: np.full(b * L, -1, np.int32) for t in range(self.num_modalities)}
+        for t in plan.ext_add:
+            plan.lat[t]['add'].zero_()
+        for i, (ty, x) in enumerate(tys):
+            row_tok[ty][i * L:(i + 1) * L] = np.arange(i * L, (i + 1) * L)
+            plan.lat[ty]['tok' if ty in plan.ext else 'x'][i * L:(i + 1) * L].copy_(x.reshape(L, -1).to(dev, torch.float32))
+            if ty in plan.ext_add:                                # the decoded block's positional embedding (T:3179-3180 under the decode slice T:1167-1176)
+                plan.lat[ty]['add'][i * L:(i + 1) * L].copy_(self._pos_rows(ty, [tuple(x.shape[:-1])]))
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        for t in row_tok:
+            plan.row_tok[t].copy_(up(row_tok[t])); plan.row_src[t].copy_(up(np.maximum(row_tok[t], 0)))
+            plan.row_inst[t].copy_(up(np.repeat(np.arange(b, dtype=np.int32), L)))
+            if t not in plan.ext:
+                plan.set_noise(t, None)
+        assert times is not None, 'decoding a modality needs `times` (the ODE step time in the last column, T:1990-1996)'
+        plan.inst_time.copy_(times.to(dev, torch.float32).reshape(b, -1)[:, -1])
 
     # ------------------------------------------------------------------ pure-text LM path (T:2586-2664)
     def forward_text(self, text, return_loss=True, return_embed=False, cache=None, return_hiddens=False, return_kv_cache=False):
@@ -1312,42 +1328,31 @@ class Transfusion(nn.Module):
         self._require_gpu()
         if (cache is not None or return_hiddens or return_kv_cache) and return_loss:
             raise NotImplementedError('forward_text: kv cache / hiddens are returned by the inference call only (return_loss = False)')
-        dev, stream, md = self.device, self._stream(), self.md
+        dev, stream = self.device, self._stream()
         text = text.to(dev)
         if cache is not None:
             return self._forward_text_cached(text, cache, return_embed, return_kv_cache, return_hiddens)
         inp, labels = (text[:, :-1], text[:, 1:]) if return_loss else (text, None)          # T:2603-2604
         b, n = inp.shape
-        key = ('text', b, n)
-        S = self._struct_cache.get(key)
-        if S is None:
+
+        def build():
             ar = torch.arange(n, dtype=torch.int32)
             tok_inst = np.full((b, n), -1, dtype=np.int32)
             seg_start, seg_len = token_segments(tok_inst, balance=True)
             D = lambda a: (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(dev)
-            S = self._struct_cache[key] = dict(tok_inst=D(tok_inst.reshape(-1)), kv_end=D((ar + 1).repeat(b)), q_start=D(ar.repeat(b)),
-                                               rot_pos=D(ar.repeat(b)), seg_start=D(seg_start), seg_len=D(seg_len))
+            return dict(tok_inst=D(tok_inst.reshape(-1)), kv_end=D((ar + 1).repeat(b)), q_start=D(ar.repeat(b)), rot_pos=D(ar.repeat(b)),
+                        seg_start=D(seg_start), seg_len=D(seg_len))
+        S = self._structure(('text', b, n), build)
         self.store.refresh_shadows(stream)
         plan = self._plan(b, n, 0, {}, training=return_loss)
         if plan.loaded_structure is not S:
-            plan.set_rope_tables(*self._rope_tables(n))
-            plan.tok_inst.copy_(S['tok_inst']); plan.kv_end.copy_(S['kv_end']); plan.q_start.copy_(S['q_start']); plan.rot_pos.copy_(S['rot_pos'])
-            plan.set_segments(S['seg_start'], S['seg_len'])
-            plan.loaded_structure = S
+            plan.load_structure(S, self._rope_tables(n), S['tok_inst'], S['kv_end'], S['q_start'], S['rot_pos'], segments=(S['seg_start'], S['seg_len']))
         plan.text_ids.copy_(inp.masked_fill(inp == -1, 0).reshape(-1))                      # T:2608
         if not return_loss:
             Plan.run(plan.fwd, stream, 0, plan.fwd_embed_end if return_embed else plan.fwd_logits_end)
-            out = plan.embed.view(b, n, md.dim).float() if return_embed else plan.logits.view(b, n, md.vp)[..., :md.vocab].clone()
-            ret = (out,)
-            if return_kv_cache:                                                            # (tensor, tokens_seen + seq_len), T:2631
-                from .sampling import Sampler
-                buf = torch.zeros(md.depth, b, -(-(n + 64) // 64) * 64, 2 * md.hdk, device=dev, dtype=torch.bfloat16)
-                Sampler(self)._fill_cache(buf, plan, b, n)
-                buf._tfx_filled = n
-                ret = (*ret, (self._kv_public(buf, n), n))
-            if return_hiddens:
-                ret = (*ret, [plan.hid[i].view(b, n, md.dim).float() for i in range(md.depth + 1)] + [plan.embed.view(b, n, md.dim).float()])
-            return ret[0] if len(ret) == 1 else ret
+            out = self._embed_out(plan) if return_embed else self._logits_out(plan)
+            kv = (self._kv_from_plan(plan, n), n) if return_kv_cache else None             # (tensor, tokens_seen + seq_len), T:2631
+            return _pack_outputs(out, (return_kv_cache, kv), (return_hiddens, self._hiddens_out(plan, n) if return_hiddens else None))
         lab = labels.reshape(-1)
         plan.labels.copy_(torch.where(lab == self.ignore_index, torch.full_like(lab, -1), lab))
         plan.set_loss_scales(1.0, {})                        # mean over the valid labels: the count lives on the device (see _bwd_scale)
@@ -1357,24 +1362,17 @@ class Transfusion(nn.Module):
         cnt = plan.acc[1].clamp(min=1.)
         loss = plan.acc[0] / cnt                             # T:2655-2659
         self._bwd_scale = (1. / cnt).detach()
-        self._step_id += 1
-        self._live = (plan, self._step_id)
-        if torch.is_grad_enabled():
-            if self._anchor is None or self._anchor.device != dev:
-                self._anchor = torch.zeros((), device=dev, requires_grad=True)
-            loss = _NativeLoss.apply(self._anchor, self, loss, _NO_ROWS)[0]
-        return loss
+        return self._close_step(plan, loss)[0]
 
     def _forward_text_cached(self, text, cache, return_embed, return_kv_cache, return_hiddens):
         """forward_text against a kv cache (T:2612-2631): the L new tokens of every row run as ONE causal multi-token decode step - token j at cache
         position n_cached + j and rotary position tokens_seen + j, attending to the cache and to the new tokens up to itself"""
         from .sampling import Sampler
-        md, dev, stream = self.md, self.device, self._stream()
         kv_in, seen = cache
         b, L = text.shape
         buf, n_cached = self._kv_native(kv_in, L)
         assert buf.shape[1] == b, 'kv cache batch does not match the number of rows'
-        if not hasattr(self, '_decode_plans') or len(self._decode_plans) > 8:
+        if len(self._decode_plans) > 8:
             self._decode_plans = {}
         smp = Sampler(self)
         plan = smp._decode_plan(('fwd_text', L, buf.data_ptr()), b, L, buf, False)
@@ -1384,15 +1382,11 @@ class Transfusion(nn.Module):
         kve = np.tile(n_cached + 1 + ar, b)
         rot = np.tile(int(seen) + ar, b)
         smp._load(plan, ids=ids, pos=pos, kve=kve, rot=rot, tok_inst=np.full(b * L, -1, np.int32))
-        Plan.run(plan.fwd, stream, 0, plan.fwd_embed_end if return_embed else plan.fwd_logits_end)
-        out = plan.embed.view(b, L, md.dim).float() if return_embed else plan.logits.view(b, L, md.vp)[..., :md.vocab].clone()
+        Plan.run(plan.fwd, self._stream(), 0, plan.fwd_embed_end if return_embed else plan.fwd_logits_end)
+        out = self._embed_out(plan) if return_embed else self._logits_out(plan)
         buf._tfx_filled = n_cached + L
-        ret = (out,)
-        if return_kv_cache:
-            ret = (*ret, (self._kv_public(buf, n_cached + L), int(seen) + L))
-        if return_hiddens:
-            ret = (*ret, [plan.hid[i].view(b, L, md.dim).float() for i in range(md.depth + 1)] + [plan.embed.view(b, L, md.dim).float()])
-        return ret[0] if len(ret) == 1 else ret
+        kv = (self._kv_public(buf, n_cached + L), int(seen) + L) if return_kv_cache else None
+        return _pack_outputs(out, (return_kv_cache, kv), (return_hiddens, self._hiddens_out(plan, L) if return_hiddens else None))
 
     # ------------------------------------------------------------------ pure flow path (T:2710-2869)
     def forward_modality(self, modalities, times=None, modality_type=None, encode_modality=True, velocity_consistency_ema_model=None,
@@ -1400,14 +1394,9 @@ class Transfusion(nn.Module):
         """`Transfusion.forward_modality`: every token is a latent of ONE instance per sample (`modality_only=True`): conditioned on
         the sample's time, no attention mask, no rotary embedding; loss = MSE(pred flow, x - noise).  Encoders / EMA velocity
         consistency / reconstruction loss are outside the native path."""
+        # ---- argument checks, frozen encoder, times
         self._require_gpu()
-        ema = velocity_consistency_ema_model
-        if ema is not None and hasattr(ema, 'ema_model'):
-            ema = ema.ema_model
-        if ema is not None and not isinstance(ema, Transfusion):
-            raise NotImplementedError('velocity_consistency_ema_model must be a native Transfusion (or the EMA wrapper of one)')
-        if ema is self:
-            raise ValueError('velocity_consistency_ema_model is the model itself: the teacher pass would overwrite the activations the backward needs - pass an EMA copy (create_ema)')
+        ema = self._resolve_ema(velocity_consistency_ema_model)
         if self.num_modalities > 1 and modality_type is None:
             raise AssertionError('`modality_type` must be explicitly passed in on forward when training on greater than 1 modality')
         t = 0 if modality_type is None else int(modality_type)
@@ -1418,7 +1407,7 @@ class Transfusion(nn.Module):
             with torch.no_grad():
                 self.modality_encoder[t].eval()
                 modalities = self.modality_encoder[t](modalities).detach()
-        ext = t in self._ext
+        ext, cf = t in self._ext, self.channel_first_latent[t]
         b = modalities.shape[0]
         if times is None:
             times = torch.rand(b, device=dev)                                              # T:2746-2747
@@ -1427,49 +1416,30 @@ class Transfusion(nn.Module):
             orig_times = times.clone()
             times = times * (1. - velocity_consistency_delta_time)
         dl, d = md.dim_latents[t], md.dim
-        tok = flow_ext = None
+
+        # ---- the rows that go in: the user's encoder on the noised input (PyTorch), or the channel-last latents
         if ext:
             # the user's encoder / decoder replace latent_to_model / model_to_latent (T:1493-1494): noising, encoder, decoder and the loss are
             # PyTorch; the transformer over the encoder's tokens (and its backward) is the native engine
-            raw = modalities.to(torch.float32)
+            raw = noised = modalities.to(torch.float32)
+            tt = times.view(b, *([1] * (raw.ndim - 1)))
             if return_loss:
-                tt = times.view(b, *([1] * (raw.ndim - 1)))
                 eps = self._noise_override[t].to(dev, torch.float32).view(raw.shape) if self._noise_override is not None else torch.randn_like(raw)
                 noised, flow_ext = tt * raw + (1. - tt) * eps, raw - eps                   # T:2756-2762
-            else:
-                noised = raw
             tok = self.latent_to_model_projs[t](noised)                                     # (b, *axial', dim)
             assert tok.shape[-1] == d, f'the encoder of modality {t} must produce model-dimension ({d}) tokens'
-            axial = tuple(tok.shape[1:-1])
+            axial, teacher_in = tuple(tok.shape[1:-1]), raw
         else:
-            if self.channel_first_latent[t]:
+            if cf:
                 modalities = modalities.movedim(1, -1)                                     # (b, d, *axial) -> (b, *axial, d)
             x = modalities.to(dev, torch.float32)
             assert x.shape[-1] == dl, f'last dimension must be dim_latent = {dl}'
-            axial = tuple(x.shape[1:-1])
+            axial, teacher_in = tuple(x.shape[1:-1]), (x.movedim(-1, 1) if cf else x)
         L = int(np.prod(axial)) if axial else 1
         rows = b * L
-        key = ('modality', b, L, t)
-        S = self._struct_cache.get(key)
-        if S is None:
-            inst = torch.arange(b, dtype=torch.int32).repeat_interleave(L)
-            S = self._struct_cache[key] = dict(tok_inst=inst.to(dev), kv_end=torch.full((rows,), L, dtype=torch.int32, device=dev),
-                                               zeros=torch.zeros(rows, dtype=torch.int32, device=dev),
-                                               row_tok=torch.arange(rows, dtype=torch.int32, device=dev),
-                                               empty=torch.zeros(0, dtype=torch.int32, device=dev))
-        self.store.refresh_shadows(stream)
-        plan = self._plan(b, L, b, {t: rows}, training=return_loss)
-        if md.model_output_clean:
-            plan.set_clean_mode('latent')                   # pure flow path: the latent-space conversion (T:2772-2810)
-        if plan.loaded_structure is not S:
-            plan.set_rope_tables(*self._rope_tables(0))
-            plan.tok_inst.copy_(S['tok_inst']); plan.kv_end.copy_(S['kv_end']); plan.q_start.copy_(S['zeros']); plan.rot_pos.copy_(S['zeros'])
-            plan.set_segments(S['empty'], S['empty'])             # one instance spans a whole row: per-token atomics for the instance gradients
-            plan.row_tok[t].copy_(S['row_tok']); plan.row_inst[t].copy_(S['tok_inst'])
-            if return_loss:
-                plan.set_rows({t: rows})                                            # (fills the gather form of the row map)
-            plan.text_ids.zero_()
-            plan.loaded_structure = S
+
+        # ---- structure, plan and its inputs
+        plan = self._modality_plan(b, L, t, return_loss)
         plan.inst_time.copy_(times)
         lt = plan.lat[t]
         rows_in = []
@@ -1484,22 +1454,23 @@ class Transfusion(nn.Module):
             rows_in.append(('tok', t, tok_rows))
         else:
             lt['x'].copy_(x.reshape(rows, dl))
+
+        # ---- inference: the predicted flow
         if not return_loss:
             if ext:
                 Plan.run(plan.fwd, stream, 0, plan.fwd_embed_end)
                 out = self.model_to_latent_projs[t](plan.embed.view(b, *axial, d).float())
                 if md.model_output_clean:                                             # T:2770-2771, T:2810: the latent-space conversion around the user's decoder
-                    out = (out - noised) / (1. - times.view(b, *([1] * (raw.ndim - 1)))).clamp_min(md.clean_eps)
+                    out = (out - noised) / (1. - tt).clamp_min(md.clean_eps)
                 return out
             plan.set_noise(t, None)                                                  # T:2759-2760: no noising
             Plan.run(plan.fwd, stream, 0, plan.fwd_pred_end)
             out = lt['pred'].view(x.shape).clone()
-            return out.movedim(-1, 1) if self.channel_first_latent[t] else out
+            return out.movedim(-1, 1) if cf else out
+
+        # ---- losses
         if not ext:
-            if self._noise_override is not None:
-                lt['eps'].copy_(self._noise_override[t].reshape(rows, dl))
-            else:
-                lt['eps'].normal_()                                                            # T:2753
+            self._fill_noise(lt['eps'], t, reshape=True)                                    # T:2753
             plan.set_noise(t, lt['eps'].data_ptr())
         plan.labels.fill_(-1)
         plan.set_loss_scales(0.0, {} if ext else {t: 2.0 / (rows * dl)})
@@ -1509,71 +1480,20 @@ class Transfusion(nn.Module):
         Plan.run(plan.fwd, stream, graph='auto')
         flow_loss = torch.zeros((), device=dev) if ext else plan.acc[2 + t] / (rows * dl)   # T:2817
         loss = flow_loss
-        velocity_loss = None
-        if ema is not None and ext:
-            # same term for a type whose maps are user modules: the teacher's flow comes back in the raw layout, the mse is PyTorch's
-            was_training = ema.training
-            ema.eval()
-            try:
-                with torch.no_grad():
-                    teacher = ema.forward_modality(raw, times=orig_times + velocity_consistency_delta_time, modality_type=t, encode_modality=False, return_loss=False)
-                    velocity_loss = torch.nn.functional.mse_loss(flow_ext, teacher)
-            finally:
-                ema.train(was_training)
-            loss = loss + self.velocity_consistency_loss_weight * velocity_loss
-        elif ema is not None:
-            # T:2823-2836: mse(FLOW TARGET, teacher flow at t + delta on the clean input) - no gradient reaches the student through it
-            was_training = ema.training
-            ema.eval()
-            try:
-                with torch.no_grad():
-                    xin = x.view(modalities.shape)
-                    teacher = ema.forward_modality(xin.movedim(-1, 1) if self.channel_first_latent[t] else xin, times=orig_times + velocity_consistency_delta_time,
-                                                   modality_type=t, encode_modality=False, return_loss=False)
-                    if self.channel_first_latent[t]:
-                        teacher = teacher.movedim(1, -1)
-            finally:
-                ema.train(was_training)
-            lt['vel'].copy_(teacher.reshape(rows, dl))
-            va = plan._vel_args[t]
-            va.pred, va.flow, va.grad_scale = lt['vel'].data_ptr(), lt['flow'].data_ptr(), 0.0
-            Plan.run(plan.vel, stream)
-            velocity_loss = plan.acc[2 + self.num_modalities + t] / (rows * dl)
+        velocity_loss = recon_loss = None
+        if ema is not None:
+            velocity_loss = self._modality_velocity_loss(plan, t, ema, teacher_in, orig_times + velocity_consistency_delta_time, flow_ext if ext else None)
             loss = loss + self.velocity_consistency_loss_weight * velocity_loss              # T:2858-2862
-        recon_loss = None
         dec = self.modality_decoder[t]
         if self.has_recon_loss:                                                            # T:2840-2853
             assert encode_modality, 'the reconstruction loss needs the un-encoded modality as its target'
-        if self.has_recon_loss and not ext:
-            if dec is None:
-                # recon = noise + pred (1 - t) against the clean latent: the native residual kernel (mode 1), gradient into the same seeds
-                if self.modality_encoder[t] is not None:
-                    raise ValueError('reconstruction loss with a modality encoder needs the matching modality decoder')
-                lt['recw'].fill_(1. / rows)
-                ra = plan._rec_args[t]
-                ra.recon_mode, ra.grad_scale = 1, 2.0 * self.reconstruction_loss_weight / dl
-                Plan.run(plan.rec, stream)
-                recon_loss = plan.acc[2 + 2 * self.num_modalities + t] / dl
-            else:
-                # through the frozen decoder, without gradients (T:2845-2848): a reported term
-                with torch.no_grad():
-                    tt = times.view(b, *([1] * (x.ndim - 1)))
-                    rec = lt['eps'].view(x.shape) + lt['pred'].view(x.shape) * (1. - tt)
-                    dec.eval()
-                    recon_loss = torch.nn.functional.mse_loss(dec(rec.movedim(-1, 1) if self.channel_first_latent[t] else rec), orig_modalities.float())
-            loss = loss + self.reconstruction_loss_weight * recon_loss
-        self._step_id += 1
-        self._live = (plan, self._step_id)
-        emb_rows = None
-        if torch.is_grad_enabled():
-            if self._anchor is None or self._anchor.device != dev:
-                self._anchor = torch.zeros((), device=dev, requires_grad=True)
-            spec = {'in': [(k, ty) for k, ty, _ in rows_in], 'out': [t] if ext else []} if rows_in else _NO_ROWS
-            loss, *emb_rows = _NativeLoss.apply(self._anchor, self, loss, spec, *[r for _, _, r in rows_in])
-        elif ext:
-            emb_rows = [plan.embed.float()]
+            if not ext:
+                recon_loss = self._modality_recon_loss(plan, t, x, times, orig_modalities)
+                loss = loss + self.reconstruction_loss_weight * recon_loss
+        loss, outs = self._close_step(plan, loss, rows_in, [t] if ext and torch.is_grad_enabled() else [])
         if ext:                                                                            # the user's decoder and the flow loss, in PyTorch (T:2806-2817)
-            pred = self.model_to_latent_projs[t](emb_rows[0].view(b, *axial, d))
+            emb = outs[0] if outs else plan.embed.float()                                  # (no_grad: every row of the plan is one of the type's, in order)
+            pred = self.model_to_latent_projs[t](emb.view(b, *axial, d))
             if md.model_output_clean:                                                   # T:2770-2771, T:2810
                 pred = (pred - noised) / (1. - tt).clamp_min(md.clean_eps)
             flow_loss = torch.nn.functional.mse_loss(pred, flow_ext)
@@ -1590,6 +1510,62 @@ class Transfusion(nn.Module):
             return loss
         zero = torch.zeros((), device=dev)
         return loss, (flow_loss.detach(), velocity_loss.detach() if velocity_loss is not None else zero, recon_loss.detach() if recon_loss is not None else zero)
+
+    def _modality_plan(self, b, L, t, return_loss):
+        """the plan of a `forward_modality` call - b instances of type t, L tokens each, one per row - with its structure loaded"""
+        dev, rows = self.device, b * L
+
+        def build():
+            inst = torch.arange(b, dtype=torch.int32).repeat_interleave(L)
+            return dict(tok_inst=inst.to(dev), kv_end=torch.full((rows,), L, dtype=torch.int32, device=dev), zeros=torch.zeros(rows, dtype=torch.int32, device=dev),
+                        row_tok=torch.arange(rows, dtype=torch.int32, device=dev), empty=torch.zeros(0, dtype=torch.int32, device=dev))
+        S = self._structure(('modality', b, L, t), build)
+        self.store.refresh_shadows(self._stream())
+        plan = self._plan(b, L, b, {t: rows}, training=return_loss)
+        if self.md.model_output_clean:
+            plan.set_clean_mode('latent')                   # pure flow path: the latent-space conversion (T:2772-2810)
+        if plan.loaded_structure is not S:
+            # no segments - one instance spans a whole row: per-token atomics for the instance gradients; (set_rows fills the gather form of the row map)
+            plan.load_structure(S, self._rope_tables(0), S['tok_inst'], S['kv_end'], S['zeros'], S['zeros'], segments=(S['empty'], S['empty']),
+                                rows={t: (S['row_tok'], S['tok_inst'])}, set_rows=return_loss)
+            plan.text_ids.zero_()
+        return plan
+
+    def _modality_velocity_loss(self, plan, t, ema, teacher_in, teacher_times, flow_ext=None):
+        """velocity consistency of `forward_modality` (T:2823-2836): mse(FLOW TARGET, teacher flow at t + delta on the clean input) - no gradient reaches
+        the student through it.  `flow_ext`: the flow target of a type whose maps are user modules - the teacher's flow comes back in the raw layout,
+        the mse is PyTorch's"""
+        with _teacher_pass(ema):
+            teacher = ema.forward_modality(teacher_in, times=teacher_times, modality_type=t, encode_modality=False, return_loss=False)
+            if flow_ext is not None:
+                return torch.nn.functional.mse_loss(flow_ext, teacher)
+            if self.channel_first_latent[t]:
+                teacher = teacher.movedim(1, -1)
+        lt = plan.lat[t]
+        lt['vel'].copy_(teacher.reshape(lt['vel'].shape))
+        va = plan._vel_args[t]
+        va.pred, va.flow, va.grad_scale = lt['vel'].data_ptr(), lt['flow'].data_ptr(), 0.0
+        Plan.run(plan.vel, self._stream())
+        return plan.acc[2 + self.num_modalities + t] / lt['vel'].numel()
+
+    def _modality_recon_loss(self, plan, t, x, times, target):
+        """reconstruction loss of `forward_modality` for a native type: recon = noise + pred (1 - t) against the clean input (T:2840-2853)"""
+        lt, dec, dl = plan.lat[t], self.modality_decoder[t], self.md.dim_latents[t]
+        if dec is None:
+            # against the clean latent: the native residual kernel (mode 1), gradient into the same seeds
+            if self.modality_encoder[t] is not None:
+                raise ValueError('reconstruction loss with a modality encoder needs the matching modality decoder')
+            lt['recw'].fill_(1. / (x.numel() // dl))
+            ra = plan._rec_args[t]
+            ra.recon_mode, ra.grad_scale = 1, 2.0 * self.reconstruction_loss_weight / dl
+            Plan.run(plan.rec, self._stream())
+            return plan.acc[2 + 2 * self.num_modalities + t] / dl
+        # through the frozen decoder, without gradients (T:2845-2848): a reported term
+        with torch.no_grad():
+            tt = times.view(-1, *([1] * (x.ndim - 1)))
+            rec = lt['eps'].view(x.shape) + lt['pred'].view(x.shape) * (1. - tt)
+            dec.eval()
+            return torch.nn.functional.mse_loss(dec(rec.movedim(-1, 1) if self.channel_first_latent[t] else rec), target.float())
 
     @torch.no_grad()
     def generate_modality_only(self, batch_size=1, modality_type=None, fixed_modality_shape=None, modality_steps=16,
