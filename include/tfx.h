@@ -446,6 +446,32 @@ int tfx_ode_stage(const float* y, const float* ym, const float* ctl, int32_t B, 
                   const int32_t* rows0, void* stream);
 int tfx_ode_update(float* y, float* ym, const float* ctl, int32_t B, int32_t Lc, int32_t dmax, const float* pred, int32_t H, int32_t Lq, int32_t dl,
                    float cfg_scale, const float* sel, const int32_t* rows0, void* stream);
+/* Explicit Runge-Kutta solvers on the same fixed grid, up to TFX_ODE_MAX_STAGES stages per step (transfusion_pytorch_amd/ode.py holds the tableaus:
+ * euler, heun2, heun3, rk4 = torchdiffeq's 3/8 rule; the midpoint rule keeps the three entry points above).  With the guided derivative of a stage
+ *   g = f_uncond ? fmaf(cfg_scale, f_cond - f_uncond, f_uncond) : f_cond
+ * every state / stage input is formed by ONE prescribed fp32 sequence, the same in the three kernels:
+ *   acc = y;  for j = 0 .. nk - 1 ascending: if (w_j != 0) acc = fmaf(w_j, k_j, acc);  [acc = fmaf(w_nk, g, acc) - the g term last]
+ * A term whose weight is exactly 0 is skipped and its k_j is NOT read (a slot never written may hold anything); k_j with j >= nk is never read.
+ *
+ * tfx_ode_rk_axpy - the dense form, one launch per evaluation (n elements): k_j = k + j k_stride (j < nk <= 3; k may be NULL when nk == 0),
+ *   g -> k_out (optional), fmaf(w_nk, g, acc) -> out (optional; the next stage's input, or the new state after the last stage).
+ *   Returns -1 (y / f_cond missing, or neither output given), -2 (nk outside [0, 3]), -3 (nk > 0 without k, or k_stride < n).
+ * tfx_ode_rk_stage / tfx_ode_rk_update - the per-sample state machine; B, Lc, dmax, H, Lq, dl, rows0, sel as in tfx_ode_stage / tfx_ode_update.
+ *   y: fp32 [B][Lc][dmax];  k: fp32 [3][B][Lc][dmax], the stage derivatives k_0 .. k_2;  ctl: fp32 [9][B], per sample
+ *     ctl[0] mode   ctl[1] stage index q   ctl[2..4] stage weights wa_0 .. wa_2   ctl[5..8] update weights wb_0 .. wb_3
+ *     mode 1  a stage that is not the last of its step: input y + sum_{j<q} wa_j k_j, result k_q = g
+ *     mode 2  the last stage of a step:                 same input,                   result y = y + sum_{j<q} wb_j k_j + wb_q g
+ *     mode 3  a finished block re-encoded at t = 1: input y, no update        mode 0 (or anything else)  not inside a modality: nothing read or written
+ *   The stage kernel writes the input to the latent rows of both halves exactly where tfx_ode_stage does.  Columns >= dl, samples with sel[i] == 0
+ *   (update) and halves with a negative rows0 entry are neither read nor written.  The table lives on the device, so a stage index cannot be
+ *   checked on the host: it is clamped to [0, 3], and a mode 1 sample at index 3 (no k slot) is skipped - k is never indexed past its 3 slots. */
+enum { TFX_ODE_MAX_STAGES = 4 };
+int tfx_ode_rk_axpy(const float* y, const float* k, int64_t k_stride, int32_t nk, float w0, float w1, float w2, float w3, const float* f_cond,
+                    const float* f_uncond, float cfg_scale, float* k_out, float* out, int64_t n, void* stream);
+int tfx_ode_rk_stage(const float* y, const float* k, const float* ctl, int32_t B, int32_t Lc, int32_t dmax, float* x, int32_t H, int32_t Lq, int32_t dl,
+                     const int32_t* rows0, void* stream);
+int tfx_ode_rk_update(float* y, float* k, const float* ctl, int32_t B, int32_t Lc, int32_t dmax, const float* pred, int32_t H, int32_t Lq, int32_t dl,
+                      float cfg_scale, const float* sel, const int32_t* rows0, void* stream);
 
 /* ---- parameter plumbing ---------------------------------------------------------------------- */
 /* dst[r][c] (bf16, ld_dst, Rd rows, Cd cols) = src[rowmap ? rowmap[r] : r][c] or 0 when out of range / map < 0 */

@@ -97,6 +97,75 @@ __global__ void ode_update_k(float* y, float* ym, const float* ctl, int B, int L
   if (mode == 1) ym[at] = r; else y[at] = r;
 }
 
+// ---- explicit Runge-Kutta tableaus of up to TFX_ODE_MAX_STAGES stages (tfx.h: tfx_ode_rk_stage / tfx_ode_rk_update / tfx_ode_rk_axpy) ----
+// The arithmetic the header fixes, shared by the three kernels: fp32 from y, j ascending, one fmaf per term, a zero weight = the term is skipped and
+// its k_j is not read; the guided derivative is one fmaf as well.
+TFX_DEV float rk_guided(float f, float u, float cfg) { return fmaf(cfg, f - u, u); }
+TFX_DEV float rk_accumulate(float acc, const float* k, size_t stride, int nk, const float* w) {
+#pragma unroll
+  for (int j = 0; j < TFX_ODE_MAX_STAGES - 1; j++)
+    if (j < nk && w[j] != 0.f) acc = fmaf(w[j], k[(size_t)j * stride], acc);
+  return acc;
+}
+TFX_DEV int rk_stage_index(float q) { const int v = (int)q; return v < 0 ? 0 : v > TFX_ODE_MAX_STAGES - 1 ? TFX_ODE_MAX_STAGES - 1 : v; }
+
+struct RkWeights { float w[TFX_ODE_MAX_STAGES]; };
+
+__global__ void ode_rk_axpy_k(const float* y, const float* k, long long k_stride, int nk, RkWeights w, const float* fc, const float* fu, float cfg,
+                              float* k_out, float* out, long long n) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float g = fc[i];
+  if (fu) g = rk_guided(g, fu[i], cfg);
+  if (k_out) k_out[i] = g;
+  if (out) out[i] = fmaf(w.w[nk], g, rk_accumulate(y[i], k + i, (size_t)k_stride, nk, w.w));
+}
+
+// one thread per (sample, row, column < dl), as ode_stage_k / ode_update_k.  ctl: [9][B] = mode, stage index, 3 stage weights, 4 update weights
+__global__ void ode_rk_stage_k(const float* y, const float* k, const float* ctl, int B, int Lc, int dmax, float* x, int H, int Lq, int dl, const int32_t* rows0) {
+  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (long long)B * Lc * dl) return;
+  const int c = (int)(e % dl), j = (int)((e / dl) % Lc), i = (int)(e / ((long long)dl * Lc));
+  const int mode = (int)ctl[i];
+  if (mode < 1 || mode > 3) return;
+  bool any = false;
+  for (int h = 0; h < H; h++) any |= (rows0 ? rows0[h * B + i] : 0) >= 0;
+  if (!any) return;
+  const size_t src = ((size_t)i * Lc + j) * dmax + c;
+  float v = y[src];
+  if (mode != 3) {
+    const float wa[3] = {ctl[2 * B + i], ctl[3 * B + i], ctl[4 * B + i]};
+    v = rk_accumulate(v, k + src, (size_t)B * Lc * dmax, rk_stage_index(ctl[B + i]), wa);
+  }
+  for (int h = 0; h < H; h++) {
+    const int r0 = rows0 ? rows0[h * B + i] : (h * B + i) * Lq;
+    if (r0 >= 0) x[((size_t)r0 + j) * dl + c] = v;
+  }
+}
+
+__global__ void ode_rk_update_k(float* y, float* k, const float* ctl, int B, int Lc, int dmax, const float* pred, int H, int Lq, int dl, float cfg,
+                                const float* sel, const int32_t* rows0) {
+  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (long long)B * Lc * dl) return;
+  const int c = (int)(e % dl), j = (int)((e / dl) % Lc), i = (int)(e / ((long long)dl * Lc));
+  const int mode = (int)ctl[i];
+  if ((mode != 1 && mode != 2) || (sel && sel[i] == 0.f)) return;
+  const int q = rk_stage_index(ctl[B + i]);
+  if (mode == 1 && q >= TFX_ODE_MAX_STAGES - 1) return;      // a stage that is not the last has one of the k slots: anything else is skipped
+  const int rc = rows0 ? rows0[i] : i * Lq;
+  if (rc < 0) return;
+  float g = pred[((size_t)rc + j) * dl + c];
+  if (H == 2) {
+    const int ru = rows0 ? rows0[B + i] : (B + i) * Lq;
+    if (ru < 0) return;
+    g = rk_guided(g, pred[((size_t)ru + j) * dl + c], cfg);
+  }
+  const size_t at = ((size_t)i * Lc + j) * dmax + c, stride = (size_t)B * Lc * dmax;
+  if (mode == 1) { k[(size_t)q * stride + at] = g; return; }
+  const float wb[3] = {ctl[5 * B + i], ctl[6 * B + i], ctl[7 * B + i]};
+  y[at] = fmaf(ctl[(5 + q) * B + i], g, rk_accumulate(y[at], k + at, stride, q, wb));
+}
+
 // R x C block of a fp32 matrix -> bf16 block of another matrix (8 elements per thread)
 __global__ void cast_block_k(const float* src, int ld_src, bf16* dst, int ld_dst, int R, int C8) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -255,6 +324,33 @@ int tfx_ode_update(float* y, float* ym, const float* ctl, int32_t B, int32_t Lc,
   if (!y || !ym || !ctl || !pred || H < 1 || H > 2 || Lq < Lc || dl > dmax) return -1;
   const long long n = (long long)B * Lc * dl;
   hipLaunchKernelGGL(ode_update_k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)s, y, ym, ctl, B, Lc, dmax, pred, H, Lq, dl, cfg_scale, sel, rows0);
+  return (int)hipGetLastError();
+}
+int tfx_ode_rk_axpy(const float* y, const float* k, int64_t k_stride, int32_t nk, float w0, float w1, float w2, float w3, const float* f_cond,
+                    const float* f_uncond, float cfg_scale, float* k_out, float* out, int64_t n, void* s) {
+  if (n <= 0) return 0;
+  if (!y || !f_cond || (!out && !k_out)) return -1;
+  if (nk < 0 || nk > TFX_ODE_MAX_STAGES - 1) return -2;
+  if (nk > 0 && (!k || k_stride < n)) return -3;
+  const tfx::RkWeights w = {{w0, w1, w2, w3}};
+  hipLaunchKernelGGL(ode_rk_axpy_k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)s, y, k, (long long)k_stride, nk, w, f_cond, f_uncond,
+                     cfg_scale, k_out, out, (long long)n);
+  return (int)hipGetLastError();
+}
+int tfx_ode_rk_stage(const float* y, const float* k, const float* ctl, int32_t B, int32_t Lc, int32_t dmax, float* x, int32_t H, int32_t Lq, int32_t dl,
+                     const int32_t* rows0, void* s) {
+  if (B <= 0 || Lc <= 0 || dl <= 0) return 0;
+  if (!y || !k || !ctl || !x || H < 1 || H > 2 || Lq < Lc || dl > dmax) return -1;
+  const long long n = (long long)B * Lc * dl;
+  hipLaunchKernelGGL(ode_rk_stage_k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)s, y, k, ctl, B, Lc, dmax, x, H, Lq, dl, rows0);
+  return (int)hipGetLastError();
+}
+int tfx_ode_rk_update(float* y, float* k, const float* ctl, int32_t B, int32_t Lc, int32_t dmax, const float* pred, int32_t H, int32_t Lq, int32_t dl,
+                      float cfg_scale, const float* sel, const int32_t* rows0, void* s) {
+  if (B <= 0 || Lc <= 0 || dl <= 0) return 0;
+  if (!y || !k || !ctl || !pred || H < 1 || H > 2 || Lq < Lc || dl > dmax) return -1;
+  const long long n = (long long)B * Lc * dl;
+  hipLaunchKernelGGL(ode_rk_update_k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)s, y, k, ctl, B, Lc, dmax, pred, H, Lq, dl, cfg_scale, sel, rows0);
   return (int)hipGetLastError();
 }
 int tfx_scale_bf16_copy(const tfx_bf16* src, tfx_bf16* dst, int64_t n, float scale, void* s) {

@@ -188,7 +188,7 @@ class LaunchList(list):
 
 
 class Plan:
-    def __init__(self, ps: ParamStore, b: int, n: int, I: int, R: dict, training: bool = True, cache=None, dp_groups: int = 0, tile_attn: bool = False, units=None):
+    def __init__(self, ps: ParamStore, b: int, n: int, I: int, R: dict, training: bool = True, cache=None, dp_groups: int = 0, tile_attn: bool = False, units=None, ctl_rows: int = 2):
         """cache: None, or a KV cache tensor [depth, b, maxlen, 2*heads*64] (k~ | v per token).  With a cache the plan is a
         DECODE step: each layer appends this step's k~ / v rows at `cache_pos` (flat row b*maxlen + position, -1 = skip) and
         attention reads keys / values from the cache (per-token visible length in `kv_end`).
@@ -228,11 +228,11 @@ class Plan:
         self.row_tok = {t: z(r, dtype=torch.int32) for t, r in R.items()}
         self.rowbuf = None
         if cache is not None and R and len(set(R.values())) == 1:
-            # decode plans: the per-step row maps of all types (row_tok, then row_src) and a small fp32 control area live in ONE buffer, so a step
+            # decode plans: the per-step row maps of all types (row_tok, then row_src) and a small fp32 control area (`ctl_rows` per-sample rows: 2 for the midpoint solver, 9 for the Runge-Kutta table) live in ONE buffer, so a step
             # uploads them with one copy
             r = next(iter(R.values()))
             self.row_stride = rs = (r + 3) // 4 * 4                       # 16-byte aligned rows
-            self.rowbuf = z(2 * len(R) * rs + 2 * max(b, units[0] if units else 0), dtype=torch.int32)
+            self.rowbuf = z(2 * len(R) * rs + ctl_rows * max(b, units[0] if units else 0), dtype=torch.int32)
             self.row_tok = {t: self.rowbuf[k * rs:k * rs + r] for k, t in enumerate(R)}
             self.ctl = self.rowbuf[2 * len(R) * rs:].view(torch.float32)
         self.row_inst = {t: z(r, dtype=torch.int32) for t, r in R.items()}

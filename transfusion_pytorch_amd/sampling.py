@@ -31,6 +31,7 @@ import torch
 
 from . import capi
 from .engine import Plan
+from .ode import ode_schedule
 
 
 @dataclass
@@ -86,6 +87,29 @@ def _ode_axpy(y, f_cond, f_uncond, cfg_scale, a, stream):
     capi.check(capi.lib().tfx_ode_axpy(y.data_ptr(), f_cond.data_ptr(), capi.ptr(f_uncond), float(cfg_scale), float(a), out.data_ptr(), y.numel(),
                                        ctypes.c_void_p(stream)), 'tfx_ode_axpy')
     return out
+
+
+def _ode_rk_axpy(y, K, ev, f_cond, f_uncond, cfg_scale, stream):
+    """one evaluation of a Runge-Kutta step in dense form (tfx_ode_rk_axpy, one launch): the guided derivative goes to K[ev.q] unless the step ends
+    here, and y + sum_{j<q} ev.w[j] K[j] + ev.w[q] g - the next stage's input, or the new state - is returned.  K: fp32 [3, *y.shape]"""
+    out = torch.empty_like(y)
+    w = tuple(ev.w) + (0.,) * (4 - len(ev.w))
+    capi.check(capi.lib().tfx_ode_rk_axpy(y.data_ptr(), K.data_ptr(), y.numel(), ev.q, *w, f_cond.data_ptr(), capi.ptr(f_uncond), float(cfg_scale),
+                                          None if ev.last else K[ev.q].data_ptr(), out.data_ptr(), y.numel(), ctypes.c_void_p(stream)), 'tfx_ode_rk_axpy')
+    return out
+
+
+def _ode_rk_solve(method, modality_steps, y, velocity, cfg_scale, stream):
+    """the general stage loop of the dense sampling paths: `velocity(t, x)` -> (f_cond, f_uncond | None), contiguous fp32 of y's shape"""
+    y = y.contiguous()
+    K = torch.empty(3, *y.shape, device=y.device, dtype=torch.float32)
+    x = y
+    for ev in ode_schedule(method, modality_steps):
+        fc, fu = velocity(ev.t, x)
+        x = _ode_rk_axpy(y, K, ev, fc, fu, cfg_scale, stream)
+        if ev.last:
+            y = x
+    return y
 
 
 # continuous schedule: compacted mixed steps (1) instead of the dense (L + 1)-rows-per-sample layout.  Built, token-identical (tests/test_sampling_gpu.py runs
@@ -198,12 +222,12 @@ class Sampler:
         cache[:, :, :n, :hd].copy_(plan.qkr.view(D, B, n, 2 * hd)[..., hd:])
         cache[:, :, :n, hd:].copy_(plan.qkvg.view(D, B, n, ldq)[..., 2 * hd:3 * hd])
 
-    def _decode_plan(self, key, B, Lq, cache, with_latents, n_inst=None, tile_attn=False, units=None):
+    def _decode_plan(self, key, B, Lq, cache, with_latents, n_inst=None, tile_attn=False, units=None, ctl_rows=2):
         plans = self.m._decode_plans
         if key not in plans:
             R = {t: B * Lq for t in range(self.m.num_modalities)} if with_latents else {}
             self.m.store.refresh_shadows(self.m._stream())
-            p = Plan(self.m.store, B, Lq, (n_inst or B) if with_latents else 0, R, training=False, cache=cache, tile_attn=tile_attn, units=units)
+            p = Plan(self.m.store, B, Lq, (n_inst or B) if with_latents else 0, R, training=False, cache=cache, tile_attn=tile_attn, units=units, ctl_rows=ctl_rows)
             p.q_start.zero_()
             plans[key] = p
         return plans[key]
@@ -248,11 +272,11 @@ class Sampler:
         # Decode plans - launch lists, their captured graphs, per-plan AdaLN tables of the solver's time grid - are bound to the cache buffer they were
         # built on.  A serving process calls sample_many over and over with the same geometry: the buffer and its plans are KEPT on the model between
         # calls (plan build + graph capture were ~30 ms of every call) and reused while everything they froze still holds - rows,
-        # capacity, solver grid, guidance on / off, the parameter version (shadows and cond tables are functions of the weights).  TFX_DECODE_KEEP=0
+        # capacity, solver and its grid, guidance on / off, the parameter version (shadows and cond tables are functions of the weights).  TFX_DECODE_KEEP=0
         # turns it off; TFX_DECODE_KEEP_GB bounds the kept cache (default 16); `model.train()` drops it.
         rows, need = (2 * B if use_cfg else B), max(maxlen, n0)
         keep_on = os.environ.get('TFX_DECODE_KEEP', '1') != '0'
-        keep_key = (rows, int(modality_steps), bool(use_cfg), m.store.params_version(), tuple(fixed_modality_shape or ()), bool(pos_emb_in_decode))
+        keep_key = (rows, int(modality_steps), bool(use_cfg), m.store.params_version(), tuple(fixed_modality_shape or ()), bool(pos_emb_in_decode), m.ode_method)
         ent = getattr(m, '_decode_keep', None) if keep_on else None
         self._grew = False
         if ent is not None and ent['key'] == keep_key and ent['joint'].shape[2] >= need:
@@ -333,13 +357,23 @@ class Sampler:
         nb = H * B
         M, dmax = m.num_modalities, max(md.dim_latents)
         ts = torch.linspace(0, 1, modality_steps)
+        method = m.ode_method
+        rk = method != 'midpoint'                                           # the other tableaus of ode.py: tfx_ode_rk_stage / tfx_ode_rk_update
         evals = []                                                          # (time, coefficient, sub-step): torchdiffeq fixed-grid midpoint
-        for k in range(modality_steps - 1):
-            t0, dt = float(ts[k]), float(ts[k + 1] - ts[k])
-            evals += [(t0, dt * 0.5, 1), (t0 + dt * 0.5, dt, 2)]
+        if rk:
+            sched = ode_schedule(method, modality_steps)
+            evals = [(e.t, 0., 2 if e.last else 1) for e in sched]
+            # control rows 1 .. 8 of every evaluation: stage index, the 3 weights of its input, the 4 weights of the step's update
+            rk_rows = np.zeros((8, len(sched)), np.float32)
+            for n, e in enumerate(sched):
+                rk_rows[0, n] = e.q; rk_rows[1:1 + e.q, n] = e.wa; rk_rows[4:4 + len(e.wb), n] = e.wb
+        else:
+            for k in range(modality_steps - 1):
+                t0, dt = float(ts[k]), float(ts[k + 1] - ts[k])
+                evals += [(t0, dt * 0.5, 1), (t0 + dt * 0.5, dt, 2)]
         # The time conditioning of a decode step - Fourier features -> MLP -> every layer's AdaLN tables, a GEMM that streams ALL the conditioning
         # weights (1.2 GB at dim 1024 / depth 24: 0.5 ms of a 4 ms step) - depends on the step time alone, and a fixed-grid solver only ever asks
-        # for 2 (S - 1) times plus t = 1 (finished blocks).  The "instances" of the mixed plan are therefore those TIMES: their tables are computed
+        # for stages x (S - 1) times plus t = 1 (finished blocks).  The "instances" of the mixed plan are therefore those TIMES: their tables are computed
         # once per plan, a token's instance index says which row it reads, and the conditioning launches drop out of the per-step replay.
         cond_times = torch.tensor([e[0] for e in evals] + [1.], dtype=torch.float32, device=dev)
         n_t = cond_times.numel()
@@ -364,7 +398,7 @@ class Sampler:
             torch.cuda.synchronize(); tm['prefill'] = time.perf_counter() - t_a; t_a = time.perf_counter()
 
         Lc = 0
-        Y = Ym = None
+        Y = Ym = None                                                       # Ym: the midpoint state, or (rk) K [3][B][Lc][dmax], the stage derivatives
         multi = M > 1
         sel = torch.zeros(M, B, device=dev) if multi else None              # per type: which samples are decoding a block of that type
         lib = capi.lib()
@@ -383,9 +417,9 @@ class Sampler:
             nonlocal Lc, Y, Ym
             L, dl = st.modality_length, md.dim_latents[st.curr_modality_id]
             if L > Lc:
-                newY, newYm = torch.zeros(B, L, dmax, device=dev), torch.zeros(B, L, dmax, device=dev)
+                newY, newYm = torch.zeros(B, L, dmax, device=dev), torch.zeros(*((3,) if rk else ()), B, L, dmax, device=dev)
                 if Y is not None:
-                    newY[:, :Lc], newYm[:, :Lc] = Y, Ym
+                    newY[:, :Lc], newYm[..., :Lc, :] = Y, Ym
                 Y, Ym, Lc = newY, newYm, L
             Y[i, :L, :dl] = init_modality_noise[:L, :dl].to(dev) if init_modality_noise is not None else torch.randn(L, dl, device=dev)
             st.ode_k, st.som_pending = 0, bool(use_cfg and st.unfed)
@@ -398,6 +432,8 @@ class Sampler:
             mirror(i, st)
         ar_b = np.arange(B, dtype=np.int64)
         modes = np.array([e[2] for e in evals], np.float32); coefs = np.array([e[1] for e in evals], np.float32)
+        ctl_rows = 9 if rk else 2
+        ode_stage, ode_update = (lib.tfx_ode_rk_stage, lib.tfx_ode_rk_update) if rk else (lib.tfx_ode_stage, lib.tfx_ode_update)
 
         while A[PH].any():
             t_0 = time.perf_counter()
@@ -439,7 +475,7 @@ class Sampler:
                 row0 = np.cumsum(cnt) - cnt
                 Ts = int(cnt.sum())
                 Tb = max(_COMPACT_STEP, -(-Ts // _COMPACT_STEP) * _COMPACT_STEP)
-                p = self._decode_plan(('mixc', nb, Tb, Lq, joint.data_ptr()), Tb, 1, joint, True, n_inst=n_t, tile_attn=True, units=(U, Lq))
+                p = self._decode_plan(('mixc', nb, Tb, Lq, joint.data_ptr(), method), Tb, 1, joint, True, n_inst=n_t, tile_attn=True, units=(U, Lq), ctl_rows=ctl_rows)
                 T = Tb
                 u = np.repeat(np.arange(U, dtype=np.int64), cnt)
                 j = np.arange(Ts, dtype=np.int64) - row0[u]
@@ -461,7 +497,7 @@ class Sampler:
                 self._load(p, ids, pos, kve, rot, tok_inst, units=unit_arrays)
             else:
                 # one attention kernel - the tiled forward kernel - for every plan of the run: a token's arithmetic must not depend on which plan carried it
-                p = self._decode_plan(('mix' if mixed else 'txt', nb, Lq, joint.data_ptr()), nb, Lq, joint, mixed, n_inst=n_t, tile_attn=True)
+                p = self._decode_plan(('mix' if mixed else 'txt', nb, Lq, joint.data_ptr(), method), nb, Lq, joint, mixed, n_inst=n_t, tile_attn=True, ctl_rows=ctl_rows)
                 T = nb * Lq
                 ids = np.zeros((H, B, Lq), np.int32); pos = np.full((H, B, Lq), -1, np.int64); kve = np.ones((H, B, Lq), np.int64)
                 rot = np.zeros((H, B, Lq), np.int64); tok_inst = np.full((H, B, Lq), -1, np.int64)
@@ -514,14 +550,17 @@ class Sampler:
                 ctl = hv[2 * M * rs:].view(np.float32)
                 kk = np.minimum(A[OK], len(evals) - 1)
                 ctl[:B] = np.where(is_m, modes[kk], np.where(com, 3., 0.))
-                ctl[B:2 * B] = np.where(is_m, coefs[kk], 0.)
+                if rk:
+                    ctl[B:9 * B] = np.where(is_m, rk_rows[:, kk], 0.).reshape(-1)
+                else:
+                    ctl[B:2 * B] = np.where(is_m, coefs[kk], 0.)
                 p.rowbuf.copy_(hb, non_blocking=True)
                 if md.model_output_clean:                                   # the clean-prediction conversion reads a row's time through its instance
                     for t in range(M):
                         p.row_inst[t].copy_(p.tok_inst.clamp(min=0))
                 for t in range(M):
                     dl = md.dim_latents[t]
-                    capi.check(lib.tfx_ode_stage(Y.data_ptr(), Ym.data_ptr(), p.ctl.data_ptr(), B, Lc, dmax, p.lat[t]['x'].data_ptr(), H, Lq, dl, p.unit_blk0.data_ptr() if compact else None, sp), 'tfx_ode_stage')
+                    capi.check(ode_stage(Y.data_ptr(), Ym.data_ptr(), p.ctl.data_ptr(), B, Lc, dmax, p.lat[t]['x'].data_ptr(), H, Lq, dl, p.unit_blk0.data_ptr() if compact else None, sp), 'tfx_ode_stage')
                 for t in p.ext_add:                                         # blocks that carry their axial positional embedding (history-style always, T:3173-3176)
                     add = p.lat[t]['add']
                     add.zero_()
@@ -536,7 +575,7 @@ class Sampler:
                 self._run(p, stream, p.fwd_cond[1], p.fwd_pred_end)
                 for t in range(M):
                     dl = md.dim_latents[t]
-                    capi.check(lib.tfx_ode_update(Y.data_ptr(), Ym.data_ptr(), p.ctl.data_ptr(), B, Lc, dmax, p.lat[t]['pred'].data_ptr(), H, Lq, dl,
+                    capi.check(ode_update(Y.data_ptr(), Ym.data_ptr(), p.ctl.data_ptr(), B, Lc, dmax, p.lat[t]['pred'].data_ptr(), H, Lq, dl,
                                                   float(cfg_scale), sel[t].data_ptr() if multi else None, p.unit_blk0.data_ptr() if compact else None, sp), 'tfx_ode_update')
             else:
                 self._run(p, stream, 0, p.fwd_logits_end)
@@ -671,11 +710,20 @@ class Sampler:
                 out = self._eval(jp, type_mask, Lmax, t, torch.cat([y_eval, y_eval]), stream)
                 return _ode_axpy(y_base, out[:B], out[B:], cfg_scale, a, stream)
 
+            def velocity(t, x):
+                if not use_cfg:
+                    return self._eval(jp, type_mask, Lmax, t, x, stream), None
+                out = self._eval(jp, type_mask, Lmax, t, torch.cat([x, x]), stream)
+                return out[:B], out[B:]
+
             ts = torch.linspace(0, 1, modality_steps)                  # fixed grid = the linspace itself (odeint midpoint)
-            for k in range(modality_steps - 1):
-                t0, dt = float(ts[k]), float(ts[k + 1] - ts[k])
-                y_mid = step(t0, y, y, dt * 0.5)
-                y = step(t0 + dt * 0.5, y_mid, y, dt)
+            if m.ode_method != 'midpoint':                             # the other tableaus: one tfx_ode_rk_axpy per evaluation
+                y = _ode_rk_solve(m.ode_method, modality_steps, y, velocity, cfg_scale, stream)
+            else:
+                for k in range(modality_steps - 1):
+                    t0, dt = float(ts[k]), float(ts[k + 1] - ts[k])
+                    y_mid = step(t0, y, y, dt * 0.5)
+                    y = step(t0 + dt * 0.5, y_mid, y, dt)
             if tm is not None: tm['ode'] += mark() - t_c
             for i in group:                                            # commit, T:2531-2556
                 st = states[i]; L, dl, ty = st.modality_length, md.dim_latents[st.curr_modality_id], st.curr_modality_id

@@ -18,6 +18,7 @@ from torch import nn
 
 from . import capi
 from .engine import Plan
+from .ode import check_odeint_kwargs
 from .packing import fast_signature, is_int_tensor, scan_batch, scan_signature, token_maps, token_segments
 from .axial import ContinuousAxialPositionalEmbedding
 from .params import ModelDims, ParamStore
@@ -282,8 +283,7 @@ class Transfusion(nn.Module):
         self.modality_processing = modality_processing
         self.reconstruction_loss_weight = float(reconstruction_loss_weight)                 # T:1522-1525
         self.has_recon_loss = self.reconstruction_loss_weight > 0.
-        if odeint_kwargs.get('method', 'midpoint') != 'midpoint':
-            raise NotImplementedError('only the fixed-grid midpoint solver is implemented')
+        self.ode_method = check_odeint_kwargs(odeint_kwargs)                                # fixed-grid solvers only (ode.py); atol / rtol unused
         if isinstance(transformer, dict):
             transformer = Transformer(**transformer)
         self.transformer_config = transformer
@@ -1570,7 +1570,7 @@ class Transfusion(nn.Module):
     @torch.no_grad()
     def generate_modality_only(self, batch_size=1, modality_type=None, fixed_modality_shape=None, modality_steps=16,
                                return_unprocessed_modalities=False):
-        """T:2871-2923: fixed-grid midpoint ODE from noise to a sample, `modality_steps` grid points on [0, 1]."""
+        """T:2871-2923: fixed-grid ODE (`odeint_kwargs['method']`, ode.py) from noise to a sample, `modality_steps` grid points on [0, 1]."""
         self._require_gpu()
         if self.num_modalities > 1 and modality_type is None:
             raise AssertionError('`modality_type` must be explicitly passed in on forward when training on greater than 1 modality')
@@ -1587,10 +1587,15 @@ class Transfusion(nn.Module):
         try:
             grid = torch.linspace(0., 1., modality_steps, device=dev)
             f = lambda tt, yy: self.forward_modality(yy, times=tt.expand(batch_size), modality_type=t, encode_modality=False, return_loss=False)
-            for i in range(modality_steps - 1):                                            # torchdiffeq fixed-grid 'midpoint'
-                t0, dt = grid[i], grid[i + 1] - grid[i]
-                y_mid = y + f(t0, y) * (dt * 0.5)
-                y = y + dt * f(t0 + dt * 0.5, y_mid)
+            if self.ode_method != 'midpoint':                                              # the other tableaus: one tfx_ode_rk_axpy per evaluation
+                from .sampling import _ode_rk_solve
+                vel = lambda tt, yy: (f(torch.full((1,), tt, device=dev), yy).float().contiguous(), None)
+                y = _ode_rk_solve(self.ode_method, modality_steps, y, vel, 1., self._stream())
+            else:
+                for i in range(modality_steps - 1):                                        # torchdiffeq fixed-grid 'midpoint'
+                    t0, dt = grid[i], grid[i + 1] - grid[i]
+                    y_mid = y + f(t0, y) * (dt * 0.5)
+                    y = y + dt * f(t0 + dt * 0.5, y_mid)
         finally:
             self.train(was_training)
         if self.modality_decoder[t] is not None:                                           # T:2917-2921
@@ -1725,7 +1730,7 @@ class Transfusion(nn.Module):
         text token (T:1917-1924) and per ODE evaluation (T:1998-2006, T:2021-2029), with (`cache_kv=True`) or without the kv cache it returns.
         `sample_one` itself runs the batched KV-cached decoder; this loop exists so that the contract has a caller (the reference's
         cache-equivalence tests go through it, tests/test_transfusion.py:578-662) - tests/test_decode_contract_gpu.py compares the three."""
-        from .sampling import Sampler, _sample_text_token, _ode_axpy
+        from .sampling import Sampler, _sample_text_token, _ode_axpy, _ode_rk_solve
         was_training = self.training
         self.eval()
         try:
@@ -1786,12 +1791,15 @@ class Transfusion(nn.Module):
                     return fc, fu
 
                 ts = torch.linspace(0, 1, modality_steps)
-                for k in range(modality_steps - 1):                                  # torchdiffeq fixed-grid midpoint
-                    t0, dt = float(ts[k]), float(ts[k + 1] - ts[k])
-                    fc, fu = velocity(t0, y)
-                    y_mid = _ode_axpy(y.contiguous(), fc.contiguous(), fu, cfg_scale, dt * 0.5, stream)
-                    fc, fu = velocity(t0 + dt * 0.5, y_mid)
-                    y = _ode_axpy(y.contiguous(), fc.contiguous(), fu, cfg_scale, dt, stream)
+                if self.ode_method != 'midpoint':                                    # the other tableaus (ode.py): one tfx_ode_rk_axpy per evaluation;
+                    y = _ode_rk_solve(self.ode_method, modality_steps, y, velocity, cfg_scale, stream)   # new_cache: the last evaluation's, as below
+                else:
+                    for k in range(modality_steps - 1):                              # torchdiffeq fixed-grid midpoint
+                        t0, dt = float(ts[k]), float(ts[k + 1] - ts[k])
+                        fc, fu = velocity(t0, y)
+                        y_mid = _ode_axpy(y.contiguous(), fc.contiguous(), fu, cfg_scale, dt * 0.5, stream)
+                        fc, fu = velocity(t0 + dt * 0.5, y_mid)
+                        y = _ode_axpy(y.contiguous(), fc.contiguous(), fu, cfg_scale, dt, stream)
                 sample.append((ty, y))
                 sample.append(torch.tensor([self.eom_ids[ty]], device=dev))
                 st.curr_seq = [self.eom_ids[ty]]
