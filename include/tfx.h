@@ -121,12 +121,27 @@ typedef struct {
    * split-M sums (which the chip retires at ~1.25 TB/s: 27-42 % of the ungrouped kernels) and 256 x 256 tiles for the 512 x 512 products.  Products the one-wave
    * kernel does not take (row-gathered operands, M % 64 != 0, chunks under 192 rows) make the library run the chain one by one - same results.  NULL = single. */
   const void* group_next;
+  /* table launch (round 7): any number of products over the same M rows - the weight gradients of a RUN OF LAYERS - as ONE launch of the one-wave kernel, the problem
+   * list in DEVICE memory instead of the kernel-argument segment that bounds a `group_next` chain at 6.  `table`: device pointer to `table_count` records of
+   * tfx_gemm_tn_args followed by `table_count` int32 - the inclusive prefix sums of the records' 256 x 256 tile counts ceil(N / 256) * ceil(K / 256).  `table_host`:
+   * the same bytes in host memory, owned by the caller like a `group_next` chain: the library plans the launch from it (tile sum, chunk count, whether every member
+   * qualifies) and never uploads anything, so the launch replays from a captured graph.  The head struct is the table's first product with these fields set (its M and
+   * `splits` apply to all; a record's own group_next / table fields are ignored).  With several hundred tiles the grid is several rounds of the chip at 2-4 row chunks
+   * per tile where a layer's group needs 7-13: a quarter of the fp32 atomics, one launch instead of two per layer, and blocks that finish at different times, so one
+   * block's atomics drain under the others' MFMAs.  splits == 0: the chunk count that minimises ceil(tiles x chunks / 256) x chunk length over chunks of >= 256
+   * rows (multiples of 64), each block's 256 KiB of atomics charged at the chip's rate so that ragged tile counts do not run to 256-row chunks.  A table with a member the one-wave kernel does not take (row-gathered operands, M % 64 != 0, another M, a chunk under 192 rows) runs
+   * its records one by one - same results.  `table` wins over `group_next`.  NULL = no table. */
+  const void* table;
+  const void* table_host;
+  int32_t table_count;
+  int32_t table_reserved;
 } tfx_gemm_tn_args;
 int tfx_gemm_tn(const tfx_gemm_tn_args* a, void* stream);
 /* what tfx_gemm_tn would launch for these arguments, without launching (host logic only, no device needed): kernel form (-1 register-staged
  * fallback, 0 = 128 x 128 tiles / 4 waves, 2 = 256 x 256 / 8 waves, 3 = 256 x 256 / 4 waves of 128 x 128 (one wave per SIMD, round 5)), output tiles,
  * row chunks (`splits`, chosen when a->splits == 0), grid.  For the head of a `group_next` chain that runs as one launch: kind 3 with the chain's summed tiles, its
- * chunk count and grid; a chain that runs product by product reports the head's own plan. */
+ * chunk count and grid; a chain that runs product by product reports the head's own plan.  The head of a `table` likewise: kind 3 with the table's summed tiles,
+ * chunk count and grid (which may be several rounds of the chip), or the head's own plan when the table runs record by record. */
 int tfx_gemm_tn_plan(const tfx_gemm_tn_args* a, int32_t* kind, int32_t* tiles, int32_t* splits, int32_t* grid);
 
 /* ---- attention ------------------------------------------------------------------------------- */

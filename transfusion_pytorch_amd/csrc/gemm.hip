@@ -2174,6 +2174,44 @@ __global__ __launch_bounds__(256, 1) void gemm_tn_ow_group_kernel(TnGroup g, int
   blk.tile -= first;
   tn_ow_body<SUM>(g.p[__builtin_amdgcn_readfirstlane(pid)], blk);        // (uniform index into the kernel-argument segment: scalar loads)
 }
+// table launch (tfx.h `table`, round 7): the same idea over a problem list in device memory - `count` records + the inclusive prefix sums `tile_end` of their tile
+// counts - so a launch holds the weight gradients of a whole run of layers (config 2: 448 tiles) and its grid is several rounds of the chip.
+// Block order: the pairs are numbered PRODUCT-major, and chunk-major within a product (product r owns the numbers splits x tile_end[r - 1] ... splits x tile_end[r];
+// inside, number = chunk x tiles(r) + tile), and cut into 8 contiguous runs, one per XCD (block b runs on XCD b % 8) as in tn_block.  The ~32 blocks an XCD holds at a
+// time are then consecutive tiles of ONE row chunk of ONE product (or of two neighbours of the same layer: the table lists a layer's products side by side): every
+// 64-row slab of A and B comes from HBM once and the other tiles re-read it from that XCD's L2.  Chunk-major over the WHOLE table would walk every layer's operands
+// once per chunk index, the same rows of eight layers' activations in flight across the XCDs; product-major keeps the chip inside one layer's buffers at a time.
+// The search and the record are block-uniform: scalar loads (the record's words go through readfirstlane so that no field can end up in vector registers - the
+// loop's fragments own v[64:191]).
+constexpr int TN_REC_WORDS = (int)(sizeof(GemmTN) / 4);
+static_assert(sizeof(GemmTN) % 8 == 0, "records are copied as 32-bit words and followed by an int32 array");
+template <bool SUM>
+__global__ __launch_bounds__(256, 1) void gemm_tn_ow_table_kernel(const uint32_t* __restrict__ recs, const int* __restrict__ tile_end, int count, int M, int splits) {
+  const int per = gridDim.x >> 3;
+  const int g = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
+  int lo = 0, hi = count;                                                // first product whose numbers end behind g
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (g >= splits * tile_end[mid]) lo = mid + 1; else hi = mid;
+  }
+  if (lo >= count) return;                                               // (the grid is rounded up to a multiple of 8)
+  const int r = __builtin_amdgcn_readfirstlane(lo);
+  const int first = r > 0 ? tile_end[r - 1] : 0, nt = tile_end[r] - first;
+  const int local = g - splits * first;
+  const int split = local / nt;
+  const int chunk = ((M + splits - 1) / splits + TN_BMK - 1) / TN_BMK * TN_BMK;
+  TnBlock blk;
+  blk.tile = local - split * nt;
+  blk.mbeg = min(split * chunk, M);
+  blk.mend = min(M, blk.mbeg + chunk);
+  uint32_t w[TN_REC_WORDS];
+#pragma unroll
+  for (int i = 0; i < TN_REC_WORDS; i++) w[i] = __builtin_amdgcn_readfirstlane(recs[(size_t)r * TN_REC_WORDS + i]);
+  GemmTN p;
+  __builtin_memcpy(&p, w, sizeof(GemmTN));
+  if (p.M != M) return;                                                  // (the launcher checked it on the host copy)
+  tn_ow_body<SUM>(p, blk);
+}
 #undef OWT_OUT
 #undef OWT_IN
 #undef OWT_CLOBBER
@@ -2479,6 +2517,53 @@ static TnGroupPlan tn_group_plan(const GemmTN& head) {
   gp.ok = true;
   return gp;
 }
+// table launch (tfx.h `table`): planned from the caller's host copy of the table.  Chunk count of the one-wave kernel on a grid of SEVERAL rounds of the chip: all
+// blocks are equally long (one chunk of one tile, one block per CU), so the launch takes ceil(tiles x chunks / 256) rounds of one chunk each.  The count that makes
+// rounds x chunk length smallest, over chunks of >= 256 rows in multiples of 64 without empty trailing chunks - with the fp32 atomics priced in, or the rule
+// would run to 256-row chunks whenever the tile count does not divide the rounds evenly (52 tiles: 256 chunks, 20 x the atomics, for 3 % less idle): a block adds
+// 256 KiB, which the chip retires at ~1.3 TB/s = 0.2 us = 9.5 rows of a block's loop (64 rows per 1.35 us), charged per block as if none of it were hidden.
+// 448 tiles x 65536 rows (config 2, 8 layers): 4 chunks = 7 full rounds of 16384 rows, the ideal 448 x 65536 / 256 and the plain makespan rule's choice too.
+static int tn_table_splits(int M, int tiles) {
+  constexpr double atom_rows = 9.5;
+  int best = 1; double best_cost = -1;
+  for (int s = 1; s <= 256; s++) {
+    const int chunk = ((M + s - 1) / s + TN_BMK - 1) / TN_BMK * TN_BMK;
+    if (s > 1 && chunk < 256) break;
+    if ((long long)(s - 1) * chunk >= M) continue;                      // (rounding up to 64 rows left a trailing chunk empty)
+    if (M - (s - 1) * chunk < 192) continue;
+    const double cost = (double)(((long long)tiles * s + 255) / 256) * chunk + atom_rows * tiles * s;
+    if (best_cost < 0 || cost < best_cost) { best = s; best_cost = cost; }
+  }
+  return best;
+}
+struct TnTablePlan { bool ok, sum; int tiles, splits, grid; };
+static const GemmTN* tn_table_rec(const GemmTN& head, int i) { return (const GemmTN*)head.table_host + i; }
+static TnTablePlan tn_table_plan(const GemmTN& head) {
+  TnTablePlan tp; memset(&tp, 0, sizeof(tp));
+  static int tab = -1;                // TFX_TN_TABLE=0: tables run record by record (A/B)
+  if (tab < 0) { const char* e = getenv("TFX_TN_TABLE"); tab = e ? atoi(e) : 1; }
+  const int n = head.table_count;
+  const int32_t* tile_end = (const int32_t*)(tn_table_rec(head, n));
+  bool ok = tab != 0 && tn_ow_mode() != 0 && (((uintptr_t)head.table) & 7) == 0;
+  int tiles = 0;
+  for (int i = 0; i < n; i++) {
+    const GemmTN* q = tn_table_rec(head, i);
+    ok = ok && q->M == head.M && tn_ow_operands_ok(*q);
+    tiles += ((q->N + 255) / 256) * ((q->K + 255) / 256);
+    ok = ok && tile_end[i] == tiles;                                   // (the kernel maps blocks by the caller's prefix sums)
+    tp.sum = tp.sum || q->colsum != nullptr;
+  }
+  tp.tiles = tiles;
+  if (!ok) return tp;
+  tp.splits = head.splits == 0 ? tn_table_splits(head.M, tiles) : head.splits;
+  const int chunk = ((head.M + tp.splits - 1) / tp.splits + TN_BMK - 1) / TN_BMK * TN_BMK;
+  const int last = head.M % chunk == 0 ? chunk : head.M % chunk;
+  if (chunk < 192 || last < 192) return tp;
+  if ((long long)tiles * tp.splits > (1ll << 30)) return tp;
+  tp.grid = (tiles * tp.splits + 7) / 8 * 8;
+  tp.ok = true;
+  return tp;
+}
 static int tn_ramp(int M, int tiles, int splits) {   // tn_block_ramp's d for a launch (see the kind-3 branch of gemm_tn)
   constexpr int ramp_min = 8;          // fewest row chunks that get a ramp (2-5-chunk launches measured nothing to +1 %; 6 - the 7-chunk FeedForward group - 4.19 -> 4.17 ms, noise)
   int ramp = 0;
@@ -2492,7 +2577,11 @@ static int tn_ramp(int M, int tiles, int splits) {   // tn_block_ramp's d for a 
 
 int gemm_tn_plan(const GemmTN& p, int* kind, int* tiles, int* splits, int* grid) {
   if (p.M <= 0 || p.N <= 0 || p.K <= 0 || p.splits < 0) return -1;
-  if (p.group_next) {                                               // a chain that runs as one launch: kind 3 with the group's tiles / chunks / grid
+  if (p.table) {                                                    // a table that runs as one launch: kind 3 with the table's tiles / chunks / grid
+    if (!p.table_host || p.table_count <= 0) return -8;
+    const TnTablePlan tp = tn_table_plan(p);
+    if (tp.ok) { if (kind) *kind = 3; if (tiles) *tiles = tp.tiles; if (splits) *splits = tp.splits; if (grid) *grid = tp.grid; return 0; }
+  } else if (p.group_next) {                                        // a chain that runs as one launch: kind 3 with the group's tiles / chunks / grid
     const TnGroupPlan gp = tn_group_plan(p);
     if (gp.ok) { if (kind) *kind = 3; if (tiles) *tiles = gp.tiles; if (splits) *splits = gp.splits; if (grid) *grid = gp.grid; return 0; }
   }
@@ -2504,6 +2593,24 @@ int gemm_tn_plan(const GemmTN& p, int* kind, int* tiles, int* splits, int* grid)
 int gemm_tn(const GemmTN& p, hipStream_t s) {
   if (p.M <= 0 || p.N <= 0 || p.K <= 0 || p.splits < 0) return -1;
   if ((p.lda | p.ldb | p.a_cols | p.b_cols) & 7) return -2;
+  if (p.table) {
+    if (!p.table_host || p.table_count <= 0) return -8;
+    const TnTablePlan tp = tn_table_plan(p);
+    if (tp.ok) {
+      const uint32_t* recs = (const uint32_t*)p.table;
+      const int* tile_end = (const int*)((const GemmTN*)p.table + p.table_count);
+      static uint32_t attr_t0 = 0, attr_t1 = 0;
+      if (tp.sum) { ensure_smem_attr((const void*)gemm_tn_ow_table_kernel<true>, 131072, attr_t1); hipLaunchKernelGGL(gemm_tn_ow_table_kernel<true>, dim3(tp.grid), dim3(256), 131072, s, recs, tile_end, p.table_count, p.M, tp.splits); }
+      else { ensure_smem_attr((const void*)gemm_tn_ow_table_kernel<false>, 131072, attr_t0); hipLaunchKernelGGL(gemm_tn_ow_table_kernel<false>, dim3(tp.grid), dim3(256), 131072, s, recs, tile_end, p.table_count, p.M, tp.splits); }
+      return (int)hipGetLastError();
+    }
+    for (int i = 0; i < p.table_count; i++) {                            // a member the one-wave kernel does not take: the records one by one
+      GemmTN one = *tn_table_rec(p, i); one.group_next = nullptr; one.table = nullptr; one.table_host = nullptr; one.table_count = 0;
+      const int rc = gemm_tn(one, s);
+      if (rc) return rc;
+    }
+    return 0;
+  }
   if (p.group_next) {
     const TnGroupPlan gp = tn_group_plan(p);
     if (gp.ok) {

@@ -257,6 +257,8 @@ extern "C" int tfx_list_fingerprint(const tfx_launch* list, int32_t n, int64_t* 
       case TFX_OP_GEMM_TN: {                                        // a `group_next` chain: the chained structs are copied by value into the launch a capture freezes
         const tfx_gemm_tn_args* g = static_cast<const tfx_gemm_tn_args*>(l.args);
         for (int k = 0; k < 8 && g->group_next; ++k) { g = static_cast<const tfx_gemm_tn_args*>(g->group_next); h = mix(h, g, sizeof(tfx_gemm_tn_args)); }
+        const tfx_gemm_tn_args* t = static_cast<const tfx_gemm_tn_args*>(l.args);      // a `table`: the host copy the launch is planned from (records + prefix sums)
+        if (t->table && t->table_host && t->table_count > 0) h = mix(h, t->table_host, (size_t)t->table_count * (sizeof(tfx_gemm_tn_args) + 4));
         break;
       }
       default: break;

@@ -188,7 +188,7 @@ class LaunchList(list):
 
 
 class Plan:
-    def __init__(self, ps: ParamStore, b: int, n: int, I: int, R: dict, training: bool = True, cache=None, dp_groups: int = 0, tile_attn: bool = False, units=None, ctl_rows: int = 2):
+    def __init__(self, ps: ParamStore, b: int, n: int, I: int, R: dict, training: bool = True, cache=None, dp_groups: int = 0, tile_attn: bool = False, units=None, ctl_rows: int = 2, tn_defer=None):
         """cache: None, or a KV cache tensor [depth, b, maxlen, 2*heads*64] (k~ | v per token).  With a cache the plan is a
         DECODE step: each layer appends this step's k~ / v rows at `cache_pos` (flat row b*maxlen + position, -1 = skip) and
         attention reads keys / values from the cache (per-token visible length in `kv_end`).
@@ -206,6 +206,7 @@ class Plan:
         assert cache is None or not training
         self.dp_groups = dp_groups          # > 0: the backward list is cut into that many layer groups for the overlapped gradient all-reduce (optim.GradReducer)
         self.bwd_cuts = []                  # [(list index, first layer of the group, last layer of the group)], in backward order
+        self.tn_defer = tn_defer            # layers per deferred weight-gradient table launch: None = TFX_TN_DEFER / the default rule, 0 = per-layer groups, N, 'all' (_tn_run_length)
         self.ps, self.md, self.b, self.n, self.I, self.R = ps, md, b, n, I, dict(R)
         self.T = T = b * n
         dev = ps.device
@@ -324,8 +325,13 @@ class Plan:
             # (TFX_SIDE_STREAM=1 forces it on, =0 off)
             env = os.environ.get('TFX_SIDE_STREAM')
             self.side = D <= 30 and (env == '1' or (env is None and md.dim <= 1024))
-            nb = 2 if self.side else 1
-            self.dy_f = [e(T, d) for _ in range(nb)]; self.dy_a = [e(T, d) for _ in range(nb)] if self.side else self.dy_f
+            # deferred weight gradients (round 7, _tn_run_length): the products of a RUN of layers wait for one table launch at the run's lowest layer, so what they
+            # read - dy of both wrappers, d[a|g], d[q|k|v|gates] - is kept per layer: two runs' worth (a run's buffers are reused two runs later, behind a wait
+            # for the launch that read them), or one per layer when that covers the stack
+            self.tn_run = self._tn_run_length()
+            self.tn_tables = []                 # [(index in the backward list, lowest layer, highest layer, table bytes on ps.device, records)]
+            nb = min(D, 2 * self.tn_run) if self.tn_run else (2 if self.side else 1)
+            self.dy_f = [e(T, d) for _ in range(nb)]; self.dy_a = [e(T, d) for _ in range(nb)] if (self.side or self.tn_run) else self.dy_f
             self.dskip = {j: e(T, d) for j in set(skip_sources(md).values())}
             self.dqkvg_p = [z(T, ldq) for _ in range(nb)]; self.dog = e(T, hd); self.do_eff = e(T, hd)
             # d q~ | d k~: written only when the QK-norm / RoPE backward is its own launch (TFX_ATTN_QKNR=0); the fused epilogues never touch dq / dk
@@ -373,6 +379,61 @@ class Plan:
         head._chain = structs[1:]                                # (keeps the chained structs alive with the list)
         head._algo_flops = flops
         lst.append(Side(('tfx_gemm_tn', head)) if side else ('tfx_gemm_tn', head))
+
+    def _tn_run_length(self):
+        """layers whose weight-gradient products run as ONE table launch (tfx.h `table`), 0 = the per-layer groups.  Constructor argument `tn_defer`, else
+        TFX_TN_DEFER (0, N or 'all'), else the default rule: the whole stack (within an exchange group, see _build_backward) where a layer's own chains run as
+        one-wave groups - there a layer has few tiles and its launches pay 7-13 row chunks of fp32 atomics each; plans whose chains the library runs product
+        by product (small T) and models wider than the measured dim 512 keep their list item for item."""
+        md, D = self.md, self.md.depth
+        v = self.tn_defer if self.tn_defer is not None else os.environ.get('TFX_TN_DEFER')
+        if v is not None and str(v) != '':
+            return D if str(v) == 'all' else max(0, min(int(v), D))
+        if os.environ.get('TFX_TN_GROUP', '1') == '0' or md.dim > 512:
+            return 0                       # (dim 768 / 1024: no A/B of the deferred form yet, and ~1 GiB of buffers per deferred layer - they keep the per-layer groups)
+        d, hd, di, dip, ldq = md.dim, md.hdk, md.di, md.dip, md.ldq
+        mk = lambda N, K, lda, ldb: capi.make_args('tfx_gemm_tn_args', M=self.T, N=N, K=K, lda=lda, a_cols=lda, ldb=ldb, b_cols=ldb, ldc=K, k_valid=K, splits=0,
+                                                   accumulate=1, alpha=1.0)
+        for chain in ([mk(d, di, d, dip), mk(2 * dip, d, 2 * dip, d)], [mk(d, hd, d, hd), mk(md.nqk, d, ldq, d)]):
+            chain[0].group_next = ctypes.addressof(chain[1])
+            out = [ctypes.c_int32(-9) for _ in range(4)]
+            if capi.lib().tfx_gemm_tn_plan(ctypes.byref(chain[0]), *[ctypes.byref(o) for o in out]) != 0:
+                return 0
+            tiles = sum(-(-int(a.N) // 256) * -(-int(a.K) // 256) for a in chain)
+            if out[0].value != 3 or out[1].value != tiles:
+                return 0
+        return D
+
+    def _bwd_slot(self, i):
+        """which of the per-layer backward buffers (dy_f, dy_a, d[a|g], d[q|k|v|gates]) layer i writes"""
+        nb = len(self.dag_p)
+        return (self.md.depth - 1 - i) % nb if self.tn_run else i % nb
+
+    def _tn_table(self, lst, M, problems, side=False):
+        """Weight-gradient products over the same M rows - a run of layers' - as ONE launch from a problem table in device memory (tfx.h `table`): records of
+        tfx_gemm_tn_args + the prefix sums of their tile counts, built once per plan; the head is the first product with the table fields set.  Returns the
+        table's byte tensor."""
+        REC = capi.STRUCTS['tfx_gemm_tn_args']
+        n, rs = len(problems), ctypes.sizeof(REC)
+        host = ctypes.create_string_buffer(n * (rs + 4))
+        ends = (ctypes.c_int32 * n).from_buffer(host, n * rs)
+        flops, tiles = 0.0, 0
+        for k, (N, K, kw) in enumerate(problems):
+            kw = dict(kw); kw.setdefault('k_valid', K)
+            algo_n = kw.pop('algo_n', None)
+            a = capi.make_args('tfx_gemm_tn_args', M=M, N=N, K=K, splits=0, accumulate=1, alpha=1.0, **kw)
+            flops += 2.0 * M * (algo_n or N) * kw['k_valid']
+            ctypes.memmove(ctypes.addressof(host) + k * rs, ctypes.addressof(a), rs)
+            tiles += -(-N // 256) * -(-K // 256)
+            ends[k] = tiles
+        dev = torch.frombuffer(bytearray(host.raw), dtype=torch.uint8).to(self.ps.device)
+        self.nbytes += dev.numel()
+        head = REC.from_buffer_copy(host, 0)
+        head.table, head.table_host, head.table_count = dev.data_ptr(), ctypes.addressof(host), n
+        head._table = (host, dev)                                # (keeps both copies alive with the list)
+        head._algo_flops = flops
+        lst.append(Side(('tfx_gemm_tn', head)) if side else ('tfx_gemm_tn', head))
+        return dev
 
     def _k(self, lst, fn, struct, **kw):
         lst.append((fn, capi.make_args(struct, **kw)))
@@ -679,7 +740,7 @@ class Plan:
         if md.laser:
             kw.update(v=self.vl[li] if self.cache is None else self.vlc[i], ld_v=hd, laser=1)
         if bwd:
-            dqkvg = self.dqkvg_p[i % len(self.dqkvg_p)]
+            dqkvg = self.dqkvg_p[self._bwd_slot(i)]
             kw.update(dout=self.dog, ld_dout=hd, do_eff=self.do_eff, ld_do=hd, delta=self.delta,
                       dgate=dqkvg.data_ptr() + 2 * 3 * hd, ld_dgate=ldq, dq=self.dqk if self.dqk is not None else 0,
                       dk=self.dqk.data_ptr() + 2 * hd if self.dqk is not None else 0,
@@ -851,15 +912,24 @@ class Plan:
             self._hbm(L, ns + 6 if post is not None else ns + 4, 12 * ns * T)     # n_src gradient rows + h, out, err in, dh out (+ g, y in, dy out of the wrapper side); saved softmax state
             if export:
                 self._tn(L, T, ns, d, A=self.k1buf, lda=32, a_cols=32, B=self.hid[l], ldb=d, b_cols=d, C=self.wtab[1, j0], ldc=d)
+        run, pending = self.tn_run, []
+        run_low = {}                          # layer -> lowest layer of its run (where the run's table launch sits and its join event is recorded)
+        if run:
+            per_g = -(-D // self.dp_groups) if self.dp_groups > 0 else D
+            for j in range(D - 1, -1, -1):
+                top = min((j // per_g + 1) * per_g, D) - 1
+                run_low[j] = max(top - ((top - j) // run + 1) * run + 1, j // per_g * per_g)
         for i in range(D - 1, -1, -1):
             p = f'transformer.layers.{i}'
             x_in = self.xres[i]
             x_a = self.xa[i] if md.has_skip(i) else x_in
             (ta, dta), (tf, dtf) = self._tab(i, 0), self._tab(i, 1)
-            par = i % len(self.dag_p)
+            par = self._bwd_slot(i)
             dy_f, dy_a, dag, dqkvg = self.dy_f[par], self.dy_a[par], self.dag_p[par], self.dqkvg_p[par]
-            if i + 2 <= D - 1:
+            if not run and i + 2 <= D - 1:
                 sync('tfx_join_wait', i + 2)       # this layer reuses the buffers of layer i+2: its weight gradients must have read them
+            if run and i + len(self.dag_p) <= D - 1:
+                sync('tfx_join_wait', run_low[i + len(self.dag_p)])      # ... of layer i + (number of buffers): the table launch of that layer's run
             G = self.dH[i + 1]
             a_postf = capi.make_args('tfx_adaln_post_args', T=T, d=d, y=self.yf[i], tok_inst=self.tok_inst, table=tf, ld_table=nt3,
                                      layerscale=pp(f'{p}.2.layerscale'), g=G, dy=dy_f, dtable=dtf, dlayerscale=gp(f'{p}.2.layerscale'),
@@ -880,7 +950,8 @@ class Plan:
                      aux=self.ag[i], ldaux=2 * dip)
             # the weight gradients of this wrapper go to the side stream (dy_f and d[a|g] are final); net.0 carries its bias gradient
             # (column sums of d[a|g]) folded into the same GEMM
-            sync('tfx_fork', 2 * i)
+            if not run:
+                sync('tfx_fork', 2 * i)
             # (round 5 tried net.3's bias gradient as this GEMM's `colsum` to free 8 registers of the pull kernel: the SUM form of the GEMM is 13 us slower per
             # launch (158 vs 145 us, profiles/r05_shapes.txt) - and with its scale row in LDS the pull kernel no longer spills WITH the bias partials)
             ff_grp = [(d, di, dict(A=dy_f, lda=d, a_cols=d, B=self.hm[i], ldb=dip, b_cols=dip, C=gp(f'{p}.2.fn.net.3.weight'), ldc=di)),
@@ -888,7 +959,10 @@ class Plan:
                                         C=gp(f'{p}.2.fn.net.0.weight'), ldc=d, colsum=gp(f'{p}.2.fn.net.0.bias')))]
             # (one launch per LAYER - these two waiting for the attention wrapper's products - measured 4.21 -> 3.97 ms on the family and nothing on the overlapped
             #  step, profiles/r05b_ab_tn_layer_group.txt: removed in round 6)
-            self._tn_group(L, T, ff_grp, side=side)
+            if run:
+                pending += ff_grp
+            else:
+                self._tn_group(L, T, ff_grp, side=side)
             self._nt(L, algo_k=2 * di, A=dag, lda=2 * dip, B=S[f'ff1_t{i}'], ldb=2 * dip, M=T, N=d, K=2 * dip, epi=E['TFX_EPI_BF16'], C=self.du, ldc=d)
             a_pref = capi.make_args('tfx_adaln_pre_args', T=T, d=d, x=self.xb[i], tok_inst=self.tok_inst, table=tf, ld_table=nt3,
                                     gamma_text=pp(f'{p}.2.layernorm_gamma'), mean=_p(self.stats, 2, i), rstd=_p(self.stats, 3, i), du=self.du, dx=G,
@@ -936,7 +1010,10 @@ class Plan:
             self._hbm(L, 4 + (1 if (pull and i in pushed) else 0))          # du, x in; residual gradient in / out (+ the U-Net skip's share)
             self._seg_args.append(L[-1][1])
             # weight gradients of the attention wrapper (dy_a, d[q|k|v|gates] and G = dH[i+1] are final) on the side stream
-            sync('tfx_fork', 2 * i + 1)
+            per = -(-D // self.dp_groups) if self.dp_groups > 0 else D
+            launch = bool(run) and run_low[i] == i             # lowest layer of a run: runs count down from the top of an exchange group and end with it
+            if not run or launch:
+                sync('tfx_fork', 2 * i + 1)
             grp = [(d, hd, dict(A=dy_a, lda=d, a_cols=d, B=self.og[i], ldb=hd, b_cols=hd, C=gp(f'{p}.1.fn.to_out.1.weight'), ldc=md.hd,
                                 k_group=0 if md.dim_head == 64 else md.dim_head)),
                    (md.nqk, d, dict(algo_n=md.nq, A=dqkvg, lda=ldq, a_cols=ldq, B=self.ua[i], ldb=d, b_cols=d, C=gp(f'{p}.1.fn.to_qk.0.weight'), ldc=d,
@@ -947,8 +1024,18 @@ class Plan:
                 # profiles/r05b_ab_skip_tn_split.txt: the split-B form was removed in round 6)
                 grp.append((d, d, dict(A=G, lda=d, a_cols=d, B=x_in, ldb=d, b_cols=d, C=gp(f'{p}.0.weight'), ldc=2 * d)))
                 grp.append((d, d, dict(A=G, lda=d, a_cols=d, B=sk, ldb=d, b_cols=d, C=gp(f'{p}.0.weight', d), ldc=2 * d)))
-            self._tn_group(L, T, grp, side=side)
-            per = -(-D // self.dp_groups) if self.dp_groups > 0 else D
+            if run:
+                # deferred: nothing reads a weight gradient before the optimizer or its group's exchange, so the run's products wait for ONE table launch at the
+                # run's lowest layer, behind the fork the per-layer launch would have used and in front of the exchange cut (a run never crosses one: `launch`
+                # is true at every i % per == 0).  dH[i + 1], the saved activations and the per-layer dy / d[a|g] / d[q|k|v|gates] buffers are not rewritten
+                # before it (the hidden taps ride in the pull launches, which write dH[l] once)
+                pending += grp
+                if launch:
+                    hi_l = max(j for j in run_low if run_low[j] == i)
+                    self.tn_tables.append((len(L), i, hi_l, self._tn_table(L, T, pending, side=side), len(pending)))
+                    pending = []
+            else:
+                self._tn_group(L, T, grp, side=side)
             if I > 0 and i % per == 0:
                 # AdaLN conditioning weights (6d table columns per layer, 63 % of all parameters) of the layer GROUP that ends here: their table
                 # gradients are final once the group's backward is.  With the overlapped gradient exchange (dp_groups > 0) the weight / bias
@@ -962,7 +1049,8 @@ class Plan:
                 self._tn(L, I, cols, 4 * d, side=side, A=self.dtab_bf.data_ptr() + 2 * off, lda=nt3, a_cols=cols, B=self.cond, ldb=4 * d, b_cols=4 * d,
                          C=gp(f'{p}.1.to_film.weight'), ldc=4 * d)
                 w_item((lib.tfx_colsum_f32, (self.dtables.data_ptr() + 4 * off, nt3, I, cols, gp(f'{p}.1.to_film.bias'))))
-            sync('tfx_join_record', i)
+            if not run or launch:
+                sync('tfx_join_record', i)
             if self.dp_groups > 0:
                 if i % per == 0:                                     # lowest layer of a group: every gradient of layers >= i is final
                     sync('tfx_join_wait', i)
