@@ -47,7 +47,17 @@ enum { TFX_EPI_BF16 = 0, TFX_EPI_F32 = 1, TFX_EPI_SILU = 2, TFX_EPI_RESID = 3, T
  * value feature j*32 + c%32, else gate feature j*32 + c%64-32 (weights/bias shadows use the same order).
  * TFX_EPI_GEGLU (FeedForward T:845-853, GEGLU T:831-834): with a | g = acc + bias in that layout, C2 (ldc2 = dip) receives h = a gelu(g) and C (ldc = 2 dip)
  * receives what the backward needs, in the same layout: u = gelu(g) in the value slots and v = a gelu'(g) in the gate slots (round 5; the round-1..4 form
- * stored the pre-activations a | g).  TFX_EPI_GEGLU_BWD: acc = dh (N = dip), aux = that saved [u|v]; C (ldc = 2 dip) receives d[a|g] = dh u | dh v. */
+ * stored the pre-activations a | g).  TFX_EPI_GEGLU_BWD: acc = dh (N = dip), aux = that saved [u|v]; C (ldc = 2 dip) receives d[a|g] = dh u | dh v.
+ * bias: the epilogues read it as whole f32x4 groups, the ragged last group of N % 4 != 0 included (add_bias of the register-staged kernel), so it must be
+ * READABLE up to ceil(N / 4) * 4 floats and 16-byte aligned; what lies behind N is never used.  (ParamStore pads every segment to 4 floats for this.)
+ * ldc / ldc2 (and ldr, ldaux): in elements, any value >= the written width (N; 2 N for GEGLU_BWD).  Multiples of 4 keep every bf16x4 (8-byte) / f32x4
+ * (16-byte) store and side load of the epilogues naturally aligned; the staged 16-byte row stores of the LDS-DMA and 256 x 256 kernels, the persistent
+ * one-wave kernel (plan kind 7) and the fused QKV_NORM_ROPE epilogue need ldc % 8 == 0 (ldc2 likewise), N % 8 == 0 and a 16-byte aligned C - without them the
+ * launch takes the direct-store epilogue (kind 6 instead of 7; the norm as a second launch), same results.  Every other ldc, odd ones included, is inside
+ * the contract: the vector stores are then under-aligned, which global memory instructions execute correctly on gfx950, only slower.  The engine relies on
+ * it where a width is the model's to choose: the model-to-latent projections write fp32 rows of ldc = N = dim_latent, whatever dim_latent is.
+ * tests/test_gemm_elementwise_gpu.py runs ldc = N = 6 and 5 on the register-staged kernel, ldc % 4 == 2 and odd ldc on the decode, skinny, mid, LDS-DMA,
+ * ping-pong and one-wave kernels, and ldc = N + 8 everywhere else.  Nothing is written outside rows [0, M) (or the rows `rowmap` names) x the written width. */
 typedef struct {
   const tfx_bf16* A; int32_t lda;
   const tfx_bf16* A2; int32_t lda2; int32_t K1;

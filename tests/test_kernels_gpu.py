@@ -12,6 +12,7 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from transfusion_pytorch_amd import capi  # noqa: E402
+from _gemm_cases import assert_elementwise, geglu_perm, nt_ref, tol_bf16, tol_f32  # noqa: E402,F401   (per-element bounds: tests/_gemm_cases.py)
 
 DEV = 'cuda'
 BF = torch.bfloat16
@@ -58,9 +59,12 @@ def test_gemm_nt_bf16_bias(M, N, K):
     gemm_nt(A=A, lda=K, B=B, ldb=K, M=M, N=N, K=K, epi=capi.ENUMS['TFX_EPI_BF16'], C=C, ldc=N, bias=bias)
     ref = A.float() @ B.float().T + bias[:N]
     check(f'gemm_nt bf16 {M}x{N}x{K}', C, ref, 6e-3)
+    x64, E = nt_ref(A, B, bias[:N])
+    assert_elementwise(f'gemm_nt bf16 {M}x{N}x{K}', C, x64, tol_bf16(x64, E))
     C32 = torch.full((M, N), float('nan'), device=DEV)
     gemm_nt(A=A, lda=K, B=B, ldb=K, M=M, N=N, K=K, epi=capi.ENUMS['TFX_EPI_F32'], C=C32, ldc=N, bias=bias)
     check(f'gemm_nt f32 {M}x{N}x{K}', C32, ref, 1e-5 * 50)
+    assert_elementwise(f'gemm_nt f32 {M}x{N}x{K}', C32, x64, tol_f32(E))
 
 
 @pytest.mark.parametrize('M,N,K', [(64, 1024, 1024), (300, 1544, 512), (640, 5504, 1024), (4096, 512, 384), (37, 2816, 1408)])   # decode / skinny / mid / 128 x 128 kernels
@@ -174,15 +178,6 @@ def geglu_bwd_refs(dh, ag, a, g, is_gate):
     return from_saved, auto
 
 
-def geglu_perm(dip):
-    """physical column c of the interleaved layout -> (is_gate, feature)."""
-    c = torch.arange(2 * dip)
-    blk, within = c // 64, c % 64
-    is_gate = within >= 32
-    feat = blk * 32 + within % 32
-    return is_gate, feat
-
-
 @pytest.mark.parametrize('M', [300, 130, 640, 70000])  # 70000 rows: the ping-pong 256x256 kernel and its staged epilogues; 130: the split-K decode kernel (K >= 256); 640: the mid kernel
 def test_gemm_nt_geglu_fwd_bwd(M):
     torch.manual_seed(3)
@@ -223,10 +218,15 @@ def test_gemm_nt_bench_shapes_resid_skip_geglu():
     C = torch.full((M, d), float('nan'), device=DEV, dtype=BF)
     gemm_nt(A=A, lda=d, B=B, ldb=d, M=M, N=d, K=d, epi=capi.ENUMS['TFX_EPI_RESID'], C=C, ldc=d, R=R, ldr=d)
     check('bench out-proj + residual', C, A.float() @ B.float().T + R.float(), 6e-3)
+    x64, E = nt_ref(A, B, R=R)
+    assert_elementwise('bench out-proj + residual', C, x64, tol_bf16(x64, E), (256, 256))
     A2, B2 = rnd(M, d), rnd(d, 2 * d, scale=(2 * d) ** -0.5)
     C.fill_(float('nan'))
     gemm_nt(A=A, lda=d, A2=A2, lda2=d, K1=d, B=B2, ldb=2 * d, M=M, N=d, K=2 * d, epi=capi.ENUMS['TFX_EPI_RESID'], C=C, ldc=d, R=A, ldr=d)
     check('bench skip projection (split-A) + residual', C, torch.cat([A, A2], 1).float() @ B2.float().T + A.float(), 6e-3)
+    x64, E = nt_ref(torch.cat([A, A2], 1), B2, R=A)
+    assert_elementwise('bench skip projection (split-A) + residual', C, x64, tol_bf16(x64, E), (256, 256))
+    del x64, E
     del A2, B2, R
     Wa, Wg = rnd(dip, d, scale=d ** -0.5), rnd(dip, d, scale=d ** -0.5)
     ba, bg = torch.randn(dip, device=DEV), torch.randn(dip, device=DEV)

@@ -185,7 +185,8 @@ class ParamStore:
         self.offsets, off = {}, 0
         for name, shape in self.specs:
             self.offsets[name] = (off, shape)
-            off += pad_to(int(np.prod(shape)), 4)             # keep every segment 16-byte aligned
+            off += pad_to(int(np.prod(shape)), 4)             # keep every segment 16-byte aligned - and every bias readable up to ceil(N / 4) * 4 floats, as the
+                                                              # GEMM epilogues' f32x4 bias loads require (tfx.h tfx_gemm_nt_args)
         self.numel = off
         self.flat = torch.zeros(self.numel)
         self.grad = None
