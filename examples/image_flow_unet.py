@@ -6,6 +6,9 @@ strokes per image); everything else is the reference script with the import chan
 
     python examples/image_flow_unet.py --steps 300
     python examples/image_flow_unet.py --steps 300 --muon      # train_image_only.py:90: Muon over model.muon_parameters(), Adam over the rest
+    python examples/image_flow_unet.py --steps 300 --muon --atan2    # that line as written: `MuonAdamAtan2(..., lr = 8e-4)`, the Adam-atan2 rule for the rest
+    python examples/image_flow_unet.py --steps 300 --atan2     # the Adam-atan2 rule alone (optim.FusedAdamAtan2)
+(The atan2 rule is restated from its published definition - the adam_atan2_pytorch package is not vendored with the reference - and parity-unpinned.)
 """
 from __future__ import annotations
 
@@ -48,7 +51,7 @@ def synthetic_digits(n, seed=0):
     return img[:, None]
 
 
-def main(steps=300, batch_size=32, log=print, muon=False):
+def main(steps=300, batch_size=32, log=print, muon=False, atan2=False):
     torch.manual_seed(0)
     model = Transfusion(
         num_text_tokens=10, dim_latent=4, channel_first_latent=True, modality_default_shape=(14, 14),
@@ -58,7 +61,16 @@ def main(steps=300, batch_size=32, log=print, muon=False):
         transformer=dict(dim=64, depth=4, dim_head=32, heads=8)).cuda()
     ema_model = model.create_ema()
     data = synthetic_digits(2048).cuda()
-    if muon:
+    fused = muon or atan2
+    if muon and atan2:
+        # train_image_only.py:90.  The Muon share is FusedMuon's below; everything else - the rest of the flat buffer in one HIP launch, the conv pair
+        # and the positional MLP in PyTorch - takes the Adam-atan2 rule
+        from transfusion_pytorch_amd.optim import FusedMuonAdamAtan2
+        opt = FusedMuonAdamAtan2(model, lr=8e-4, muon_lr=5e-3, max_grad_norm=0.5)
+    elif atan2:
+        from transfusion_pytorch_amd.optim import FusedAdamAtan2
+        opt = FusedAdamAtan2(model, lr=8e-4, max_grad_norm=0.5)
+    elif muon:
         # one object for both rules: Muon (torch.optim.Muon's arithmetic, grouped HIP kernels) over the attention / feed-forward matrices, the fused
         # Adam over the rest of the flat buffer, a stock Adam over the conv pair and the positional MLP - all under one global clip at 0.5
         from transfusion_pytorch_amd.optim import FusedMuon
@@ -70,7 +82,7 @@ def main(steps=300, batch_size=32, log=print, muon=False):
         batch = data[torch.randint(0, data.shape[0], (batch_size,), device=data.device)]
         loss = model(batch, velocity_consistency_ema_model=ema_model)
         loss.backward()
-        if not muon:
+        if not fused:
             torch.nn.utils.clip_grad_norm_(model.parameters(), 0.5)
         opt.step()
         opt.zero_grad()
@@ -86,6 +98,7 @@ if __name__ == '__main__':
     ap = argparse.ArgumentParser()
     ap.add_argument('--steps', type=int, default=300)
     ap.add_argument('--muon', action='store_true', help='optim.FusedMuon instead of torch.optim.Adam')
+    ap.add_argument('--atan2', action='store_true', help='the Adam-atan2 rule: optim.FusedMuonAdamAtan2 with --muon, optim.FusedAdamAtan2 without')
     a = ap.parse_args()
-    losses, images = main(steps=a.steps, muon=a.muon)
+    losses, images = main(steps=a.steps, muon=a.muon, atan2=a.atan2)
     print('generated', tuple(images.shape), 'range', float(images.min()), float(images.max()))

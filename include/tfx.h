@@ -575,10 +575,39 @@ typedef struct {
 } tfx_adam_group_args;
 int tfx_adam_step_groups(const tfx_adam_group_args* a, void* stream);
 
+/* the Adam-atan2 rule over the same flat buffers (Everett et al., "Scaling Exponents Across Parameterizations and Optimizers", 2024; the defaults a = 1.27,
+ * b = 1 are the adam_atan2_pytorch package's as published).  RESTATED from the published definition and parity-unpinned: the package is not vendored with
+ * the reference (train_image_only.py:90 imports it), so no run of it stands behind these bits.  Per element, fp32, every rounding spelled out:
+ *   g = g coef;  w = p keep;  g = fma(l2, w, g) if l2 != 0;  m = fma(beta1, m, (1 - beta1) g);  v = fma(beta2, v, g ((1 - beta2) g))
+ *   p = w - (lr a) atan2f(m (1 / bc1), sqrt(v) (b / sqrt(bc2)))          bc1 = 1 - beta1^step, bc2 = 1 - beta2^step
+ * coef, keep (1 - lr wd where decoupled, else 1), l2 (wd for the L2 form, else 0) and the moment updates are tfx_adam_step_groups'; 1 / bc1,
+ * b / sqrt(bc2) and lr a are formed once per group on the host side of the launch, from the ONE `step`.  There is no eps: atan2(0, 0) = 0 (an element
+ * with zero gradient and zero state does not move), the second argument is never negative, so every element moves by at most lr a pi / 2, and the
+ * step does not change when every gradient is scaled by one factor.
+ * The struct BEGINS with the fields of tfx_adam_group_args, in its order and layout (skip, ranges, groups and the clip coefficient mean what they
+ * mean there); `eps` / `group_eps` are present and ignored.  One rule per launch: every group takes atan2.  Not built: the package's cautious_factor
+ * and regen_reg_rate, and its own Muon arithmetic (FusedMuonAdamAtan2 keeps tfx_muon_*).
+ * Supported magnitudes: g coef must be a normal fp32 number whose square is normal too, roughly 1e-18 <= |g coef| <= 1e18.  Below that v underflows to
+ * zero and the rule returns +-pi / 2 where exact arithmetic would not; above it v overflows.  Gradients behind a global clip are far inside the range.
+ * Returns non-zero, launching nothing, for atan2_a <= 0, atan2_b <= 0, step < 1 and whatever tfx_adam_step_groups rejects. */
+typedef struct {
+  float* p; const float* g; float* m; float* v; int64_t n;
+  float lr, beta1, beta2, eps, weight_decay, max_norm, grad_scale;
+  int32_t step; const float* sumsq;
+  const int64_t* skip; int32_t nskip;
+  int32_t decoupled;
+  const int64_t* ranges; int32_t nrange, ngroup;
+  float group_lr[TFX_ADAM_MAX_GROUPS], group_beta1[TFX_ADAM_MAX_GROUPS], group_beta2[TFX_ADAM_MAX_GROUPS], group_eps[TFX_ADAM_MAX_GROUPS],
+        group_weight_decay[TFX_ADAM_MAX_GROUPS];
+  int32_t group_decoupled[TFX_ADAM_MAX_GROUPS];
+  float atan2_a, atan2_b;
+} tfx_adam_atan2_args;
+int tfx_adam_atan2_step(const tfx_adam_atan2_args* a, void* stream);
+
 /* ---- Muon (torch/optim/_muon.py) ---------------------------------------------------------------
  * One optimizer step over ALL matrices of Transfusion.muon_parameters() (T:1657-1672) in a number of launches that does not depend on their count:
  *   tfx_sumsq_det (2 launches) -> tfx_muon_prep -> tfx_muon_norm -> ns_steps x { gram, poly, update: tfx_muon_gemm } -> tfx_muon_apply -> tfx_adam_step(skip)
- * No atomics, no sum whose order varies: the path is run-to-run bit-deterministic.
+ * (or tfx_adam_atan2_step(skip) at the end of the chain: the same launch count).  No atomics, no sum whose order varies: the path is run-to-run bit-deterministic.
  *
  * Orientation and padding (_muon.py:50-52): a rows x cols parameter is iterated as X, m x n with m = min, n = max (transposed when rows > cols).  The bf16
  * workspace keeps X (m_pad x n_pad) AND X^T (n_pad x m_pad), zero-padded to multiples of the 128 x 128 tile; zero rows / columns stay zero under the
@@ -659,6 +688,7 @@ enum { TFX_OP_GEMM_NT = 0, TFX_OP_GEMM_TN = 1, TFX_OP_ATTN_FWD = 2, TFX_OP_ATTN_
        TFX_OP_ATTNRES_BWD = 11, TFX_OP_RMSNORM_FWD = 12, TFX_OP_RMSNORM_BWD = 13, TFX_OP_EMBED_FWD = 14, TFX_OP_EMBED_BWD = 15,
        TFX_OP_NOISE_MIX = 16, TFX_OP_FOURIER = 17, TFX_OP_CE_FWD_BWD = 18, TFX_OP_MSE_FWD_BWD = 19, TFX_OP_CAST_ROWS = 20, TFX_OP_CAST_ROWS_T = 21,
        TFX_OP_ADAM_STEP = 22, TFX_OP_DECODE_ATTN = 23, TFX_OP_LASER_V_FWD = 24, TFX_OP_LASER_V_BWD = 25, TFX_OP_COSINE_FWD_BWD = 26,
+       TFX_OP_ADAM_ATAN2_STEP = 27,
        /* positional entry points (args = tfx_raw_args) */
        TFX_OP_OUTPUT_TO_FLOW = 32, TFX_OP_GATHER_F32 = 33, TFX_OP_ONEHOT_BF16 = 34, TFX_OP_SCATTER_ROWS_BF16 = 35, TFX_OP_F32_TO_BF16 = 36,
        TFX_OP_SILU_BWD = 37, TFX_OP_COLSUM_BF16 = 38, TFX_OP_COLSUM_F32 = 39, TFX_OP_ADD_BF16 = 40, TFX_OP_SCALE_BF16_DEV = 41, TFX_OP_CAST_BLOCK_BF16 = 42, TFX_OP_SCALE_BF16_COPY = 43, TFX_OP_ADALN_POST_PRE_FWD = 44, TFX_OP_LAYER_END_FWD = 45,

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import contextlib
 import os
+import struct
 
 import torch
 import torch.distributed as dist
@@ -139,6 +140,7 @@ class GradReducer:
 
 
 _ADAM_KEYS = ('lr', 'betas', 'eps', 'weight_decay', 'decoupled_weight_decay')
+_ATAN2_KEYS = ('lr', 'betas', 'weight_decay', 'decoupled_weight_decay')          # the Adam-atan2 rule has no eps; its a, b are optimizer-wide
 
 
 def _group_alias(key, index=0, doc=None):
@@ -182,6 +184,7 @@ class FusedAdam(torch.optim.Optimizer):
     step FusedAdam always took."""
 
     deterministic_norm = False
+    _GROUP_KEYS = _ADAM_KEYS          # what a parameter group of this rule carries
     lr, betas, eps, weight_decay = (_group_alias(k) for k in _ADAM_KEYS[:4])
 
     def __init__(self, model, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0., max_grad_norm=None, process_group=None,
@@ -209,13 +212,14 @@ class FusedAdam(torch.optim.Optimizer):
         # coefficient (their squared gradient norm is added to the flat buffer's before the fused kernel reads it)
         self.ext_params = (list(model.external_parameters()) if hasattr(model, 'external_parameters') else []) + head_params
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, decoupled_weight_decay=bool(decoupled_weight_decay))
-        super().__init__(self._resolve_groups(outer, param_groups, _other_rule_params), defaults)
+        defaults = {k: defaults[k] for k in self._GROUP_KEYS}
+        super().__init__(self._resolve_groups(outer, param_groups, _other_rule_params, self._GROUP_KEYS), defaults)
         self._ext_key, self.ext_opt = None, None
         self._sync_ext_opt()
 
     # ------------------------------------------------------------------ parameter groups
     @staticmethod
-    def _resolve_groups(model, param_groups, other_rule_params=()):
+    def _resolve_groups(model, param_groups, other_rule_params=(), keys=_ADAM_KEYS):
         """`param_groups` (parameters or names) as torch's list of group dicts over `model.parameters()`: unnamed parameters join group 0;
         `other_rule_params` (a subclass steps them by another rule) leave whatever group names them"""
         params = list(model.parameters())
@@ -231,9 +235,9 @@ class FusedAdam(torch.optim.Optimizer):
             raise ValueError(f"{len(groups)} parameter groups: the fused Adam launch takes at most {capi.ENUMS['TFX_ADAM_MAX_GROUPS']}")
         seen = set()
         for g in groups:
-            unknown = set(g) - set(_ADAM_KEYS) - {'params'}
+            unknown = set(g) - set(keys) - {'params'}
             if unknown:
-                raise ValueError(f'unknown keys in a parameter group: {sorted(unknown)} (taken: params, {", ".join(_ADAM_KEYS)})')
+                raise ValueError(f'unknown keys in a parameter group: {sorted(unknown)} (taken: params, {", ".join(keys)})')
             listed = g.get('params', [])
             listed = [listed] if torch.is_tensor(listed) or isinstance(listed, str) else list(listed)
             out = []
@@ -306,13 +310,20 @@ class FusedAdam(torch.optim.Optimizer):
             members = [(g, [p for p in g['params'] if id(p) in ext]) for g in self._adam_groups()]
             state = dict(self.ext_opt.state) if self.ext_opt is not None else {}
             self._ext_groups = [g for g, ps_ in members if ps_]
-            self.ext_opt = torch.optim.Adam([dict(params=ps_) for _, ps_ in members if ps_])
+            self.ext_opt = self._new_ext_opt([dict(params=ps_) for _, ps_ in members if ps_])
             for p, st in state.items():
                 self.ext_opt.state[p] = st
             self._ext_key = key
         for src, grp in zip(self._ext_groups, self.ext_opt.param_groups):   # a schedule that sets `opt.lr = ...` or a group's lr reaches these too
-            lr, b1, b2, eps, wd, dec = self._group_scalars(src)
-            grp['lr'], grp['betas'], grp['eps'], grp['weight_decay'], grp['decoupled_weight_decay'] = src['lr'], (b1, b2), eps, wd, bool(dec)
+            self._put_ext_scalars(src, grp)
+
+    def _new_ext_opt(self, groups):
+        """the PyTorch optimizer of the external parameters: this class's rule"""
+        return torch.optim.Adam(groups)
+
+    def _put_ext_scalars(self, src, grp):
+        lr, b1, b2, eps, wd, dec = self._group_scalars(src)
+        grp['lr'], grp['betas'], grp['eps'], grp['weight_decay'], grp['decoupled_weight_decay'] = src['lr'], (b1, b2), eps, wd, bool(dec)
 
     @contextlib.contextmanager
     def no_sync(self):
@@ -417,18 +428,26 @@ class FusedAdam(torch.optim.Optimizer):
         lr, beta1, beta2, eps, wd, decoupled = self._group_scalars(groups[0])
         common = dict(p=ps.flat, g=ps.grad, m=self.m, v=self.v, n=ps.numel, lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=wd, max_norm=max_norm,
                       grad_scale=gscale, step=self.step_count, sumsq=self.sumsq, skip=skip, nskip=nskip)
+        self._launch_rule(ps, stream, groups, decoupled, common)
+        # the master changed behind autograd's back: new weights epoch (shadows rebuilt, kept decode plans dropped)
+        ps.mark_dirty()
+
+    def _group_table(self, ps, groups):
+        """the fields of tfx_adam_group_args behind `decoupled` for more than one group: the device range table and the groups' records by value"""
+        ranges, nrange = self._range_table(ps)
+        rec = list(zip(*(self._group_scalars(g) for g in groups)))
+        return dict(ranges=ranges, nrange=nrange, ngroup=len(groups), group_lr=rec[0], group_beta1=rec[1], group_beta2=rec[2], group_eps=rec[3],
+                    group_weight_decay=rec[4], group_decoupled=rec[5])
+
+    def _launch_rule(self, ps, stream, groups, decoupled, common):
+        """the one launch over the flat buffer (a subclass with another per-element rule issues its own)"""
         if len(groups) == 1 and not decoupled:              # the launch FusedAdam always made
             capi.call('tfx_adam_step', capi.make_args('tfx_adam_args', **common), stream)
         elif len(groups) == 1:
             capi.call('tfx_adam_step_groups', capi.make_args('tfx_adam_group_args', decoupled=1, **common), stream)
         else:
-            ranges, nrange = self._range_table(ps)
-            rec = list(zip(*(self._group_scalars(g) for g in groups)))
-            a = capi.make_args('tfx_adam_group_args', decoupled=decoupled, ranges=ranges, nrange=nrange, ngroup=len(groups), group_lr=rec[0],
-                               group_beta1=rec[1], group_beta2=rec[2], group_eps=rec[3], group_weight_decay=rec[4], group_decoupled=rec[5], **common)
+            a = capi.make_args('tfx_adam_group_args', decoupled=decoupled, **self._group_table(ps, groups), **common)
             capi.call('tfx_adam_step_groups', a, stream)
-        # the master changed behind autograd's back: new weights epoch (shadows rebuilt, kept decode plans dropped)
-        ps.mark_dirty()
 
     def _step_other_rules(self, ps, stream, max_norm, gscale):
         """hook of subclasses that update part of the flat buffer by another rule, between the clip norm and the Adam launch: returns the device
@@ -451,6 +470,16 @@ class FusedAdam(torch.optim.Optimizer):
 
     def _load_other_rule_state(self, p, entry):
         return False
+
+    def _rule_keys(self, g):
+        """the scalars group `g` carries under its rule (a subclass keeps another rule's group)"""
+        return self._GROUP_KEYS
+
+    def _saved_under_this_rule(self, g, sg):
+        """a saved group is this rule's when it carries every scalar of the rule and none that only another fused rule knows (`eps` in a group of
+        the Adam-atan2 rule: Adam's)"""
+        keys, known = set(self._rule_keys(g)), set(_ADAM_KEYS) | set(_ATAN2_KEYS) | set(FusedMuon._MUON_KEYS)
+        return keys - {'decoupled_weight_decay'} <= set(sg) and not (set(sg) & known) - keys      # (torch.optim.Adam of older releases saves no decoupled_weight_decay)
 
     def _indexed_params(self):
         return [p for g in self.param_groups for p in g['params']]
@@ -511,7 +540,8 @@ class FusedAdam(torch.optim.Optimizer):
         if len(steps) > 1:
             raise ValueError(f'the loaded parameters are at different steps ({sorted(steps)}): the fused Adam launch has one bias correction for the whole buffer')
         for g, sg in zip(self.param_groups, saved):
-            g.update({k: v for k, v in sg.items() if k != 'params'})
+            if self._saved_under_this_rule(g, sg):          # a group saved under another rule (Adam <-> Adam-atan2) brings its moments, not its scalars
+                g.update({k: v for k, v in sg.items() if k != 'params'})
         ps = self.model.store
         self.step_count = int(steps.pop()) if steps else 0
         if entries or self.m is not None:
@@ -705,6 +735,9 @@ class FusedMuon(FusedAdam):
     def _adam_groups(self):
         return self.param_groups[:-1] if self._muon_group else self.param_groups
 
+    def _rule_keys(self, g):
+        return self._MUON_KEYS if self._muon_group and g is self.param_groups[-1] else super()._rule_keys(g)
+
     def _other_rule_state(self, p):
         if any(p is q for q in self.muon_params):
             return dict(momentum_buffer=self.momentum_buffer(p))
@@ -813,3 +846,120 @@ class FusedMuon(FusedAdam):
                              lr=lr, decay=1. - lr * wd)
         capi.call('tfx_muon_apply', app, stream)
         return T.skip, T.nskip
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# The Adam-atan2 rule (Everett et al., "Scaling Exponents Across Parameterizations and Optimizers", 2024): the update  a atan2(m / bc1, b sqrt(v / bc2))
+# in place of  (m / bc1) / (sqrt(v / bc2) + eps).  train_image_only.py:90 trains with `MuonAdamAtan2` of the adam_atan2_pytorch package, which is not
+# vendored with the reference: the arithmetic below and in `tfx_adam_atan2_step` is RESTATED from the published definition (the defaults a = 1.27,
+# b = 1, betas = (0.9, 0.99), lr = 1e-4 are the package's as published) and is parity-unpinned.  Not built: the package's `cautious_factor` and
+# `regen_reg_rate`, Adam and atan2 groups in one launch, the package's own Muon arithmetic.
+
+def _as_f32(x):
+    return struct.unpack('f', struct.pack('f', float(x)))[0]
+
+
+def _check_atan2_ab(a, b):
+    if not (float(a) > 0. and float(b) > 0.):
+        raise ValueError(f'the Adam-atan2 rule needs a > 0 and b > 0, got a = {a!r}, b = {b!r}')
+
+
+class AdamAtan2(torch.optim.Optimizer):
+    """The Adam-atan2 rule in fp32 PyTorch, for the parameters outside the flat buffer (FusedAdamAtan2 / FusedMuonAdamAtan2 step the external
+    parameters with it) and as the rule's reference form.  The operations of `tfx_adam_atan2_step` (include/tfx.h), with its group semantics:
+        w = p (1 - lr wd) if decoupled else p;  g += wd w for the L2 form;  m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g g
+        p = w - lr a atan2(m / bc1, b sqrt(v) / sqrt(bc2))
+    No eps; zero gradient on zero state moves nothing; every element moves by at most lr a pi / 2.  State keys are torch.optim.Adam's."""
+
+    def __init__(self, params, lr=1e-4, betas=(0.9, 0.99), a=1.27, b=1., weight_decay=0., decoupled_weight_decay=False):
+        _check_atan2_ab(a, b)
+        super().__init__(params, dict(lr=lr, betas=betas, a=a, b=b, weight_decay=weight_decay, decoupled_weight_decay=bool(decoupled_weight_decay)))
+
+    @torch.no_grad()
+    def step(self):
+        for grp in self.param_groups:
+            # the scalars as the fused launch carries them: fp32 values
+            lr, b1, b2, a, b, wd = (_as_f32(x) for x in (grp['lr'], *grp['betas'], grp['a'], grp['b'], grp['weight_decay']))
+            _check_atan2_ab(a, b)
+            dec = bool(grp.get('decoupled_weight_decay', False))
+            for p in grp['params']:
+                if p.grad is None:
+                    continue
+                st = self.state[p]
+                if not st:
+                    st['step'] = torch.tensor(0.)
+                    st['exp_avg'] = torch.zeros_like(p, dtype=torch.float32)
+                    st['exp_avg_sq'] = torch.zeros_like(p, dtype=torch.float32)
+                st['step'] += 1
+                t = int(st['step'])
+                m, v = st['exp_avg'], st['exp_avg_sq']
+                g = p.grad.float()
+                w = p.float() * (1. - lr * wd) if dec and wd != 0. else p.float()
+                if wd != 0. and not dec:
+                    g = g + wd * w
+                m.mul_(b1).add_(g, alpha=1. - b1)
+                v.mul_(b2).addcmul_(g, g, value=1. - b2)
+                theta = torch.atan2(m * (1. / (1. - b1 ** t)), v.sqrt() * (b / (1. - b2 ** t) ** 0.5))
+                p.copy_(w - (lr * a) * theta)
+
+
+class _Atan2Rule:
+    """what turns FusedAdam / FusedMuon into their Adam-atan2 forms: groups without eps, optimizer-wide `a` and `b` (re-read at every step),
+    `tfx_adam_atan2_step` as the launch over the flat buffer, AdamAtan2 for the external parameters"""
+
+    _GROUP_KEYS = _ATAN2_KEYS
+
+    @property
+    def eps(self):
+        raise AttributeError('the Adam-atan2 rule has no eps')
+
+    def _group_scalars(self, g):
+        b1, b2 = g['betas']
+        return float(g['lr']), float(b1), float(b2), 0., float(g['weight_decay']), int(bool(g.get('decoupled_weight_decay', False)))
+
+    def _new_ext_opt(self, groups):
+        return AdamAtan2(groups, a=self.a, b=self.b)
+
+    def _put_ext_scalars(self, src, grp):
+        lr, b1, b2, _, wd, dec = self._group_scalars(src)
+        grp['lr'], grp['betas'], grp['weight_decay'], grp['decoupled_weight_decay'], grp['a'], grp['b'] = src['lr'], (b1, b2), wd, bool(dec), self.a, self.b
+
+    def _launch_rule(self, ps, stream, groups, decoupled, common):
+        _check_atan2_ab(self.a, self.b)
+        table = self._group_table(ps, groups) if len(groups) > 1 else {}
+        a = capi.make_args('tfx_adam_atan2_args', decoupled=decoupled, atan2_a=float(self.a), atan2_b=float(self.b), **table, **common)
+        capi.call('tfx_adam_atan2_step', a, stream)
+
+
+class FusedAdamAtan2(_Atan2Rule, FusedAdam):
+    """FusedAdam with the Adam-atan2 rule: global-norm clip + one `tfx_adam_atan2_step` launch over the flat fp32 buffer.  Parameter groups
+    (`lr`, `betas`, `weight_decay`, `decoupled_weight_decay`; no `eps`: a group that names `eps`, `a` or `b` is a ValueError), `decay_groups`,
+    `group_ranges()`, `no_sync`, `overlap_grad_sync`, `deterministic_norm`, the gradient exchange and the `torch.optim` state format are FusedAdam's.
+    `a` and `b` are optimizer-wide attributes, re-read at every step.  The external parameters are stepped by AdamAtan2, under the same clip
+    coefficient.  The moments mean what Adam's mean: a FusedAdam / torch.optim.Adam `state_dict()` loads here and the other way round - the
+    moments and the step count carry over, the groups' scalars stay the loading optimizer's.
+    Restated from the published rule, parity-unpinned (see above); `cautious_factor`, `regen_reg_rate` and mixed rules in one launch are not built."""
+
+    def __init__(self, model, lr=1e-4, betas=(0.9, 0.99), a=1.27, b=1., weight_decay=0., max_grad_norm=None, process_group=None, average_grads=True, *,
+                 param_groups=None, decoupled_weight_decay=False):
+        _check_atan2_ab(a, b)
+        self.a, self.b = a, b
+        super().__init__(model, lr=lr, betas=betas, weight_decay=weight_decay, max_grad_norm=max_grad_norm, process_group=process_group,
+                         average_grads=average_grads, param_groups=param_groups, decoupled_weight_decay=decoupled_weight_decay)
+
+
+class FusedMuonAdamAtan2(_Atan2Rule, FusedMuon):
+    """train_image_only.py:90, `MuonAdamAtan2(model.muon_parameters(), model.parameters(), lr = 8e-4)`: FusedMuon with the Adam-atan2 rule for
+    everything Muon does not own.  The Muon share - launches, arguments, bits - is FusedMuon's (`torch.optim.Muon`'s rule, NOT the package's own
+    Muon arithmetic); `tfx_adam_atan2_step(skip)` takes the place of `tfx_adam_step(skip)` at the end of the chain, so a step has FusedMuon's
+    launch count.  Restated from the published rule, parity-unpinned."""
+
+    def __init__(self, model, lr=1e-4, betas=(0.9, 0.99), a=1.27, b=1., weight_decay=0., max_grad_norm=None, process_group=None, average_grads=True, *,
+                 muon_params=None, muon_lr=1e-3, muon_weight_decay=0.1, momentum=0.95, nesterov=True, ns_coefficients=(3.4445, -4.775, 2.0315),
+                 ns_steps=5, muon_eps=1e-7, adjust_lr_fn=None, param_groups=None, decoupled_weight_decay=False):
+        _check_atan2_ab(a, b)
+        self.a, self.b = a, b
+        super().__init__(model, lr=lr, betas=betas, weight_decay=weight_decay, max_grad_norm=max_grad_norm, process_group=process_group,
+                         average_grads=average_grads, muon_params=muon_params, muon_lr=muon_lr, muon_weight_decay=muon_weight_decay, momentum=momentum,
+                         nesterov=nesterov, ns_coefficients=ns_coefficients, ns_steps=ns_steps, muon_eps=muon_eps, adjust_lr_fn=adjust_lr_fn,
+                         param_groups=param_groups, decoupled_weight_decay=decoupled_weight_decay)
