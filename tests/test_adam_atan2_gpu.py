@@ -1,4 +1,4 @@
-"""The Adam-atan2 rule on the MI355X: `tfx_adam_atan2_step` (csrc/tokenwise.hip `adam_atan2_k`) through the C ABI, element by element against the fp64
+"""The Adam-atan2 rule on the MI355X: `tfx_adam_atan2_step` (csrc/tokenwise.hip `flat_rule_k<atan2_rule>`) through the C ABI, element by element against the fp64
 reference and the per-element bound of tests/_adam_atan2_cases.py (which derives the bound and says where the atan2f figure was read), with guard
 bands around p, m and v; then optim.FusedAdamAtan2 / FusedMuonAdamAtan2 on a small model, their checkpoints, and the example script.
 
@@ -54,23 +54,33 @@ VARIANTS = {
 
 def launch(n, p, g, m, v, step, groups, ranges, skip, max_norm, a, b, sumsq=None):
     """one tfx_adam_atan2_step over guarded copies of p, m, v: returns (p, m, v) as numpy and checks the guard bands"""
+    return launch_entry('tfx_adam_atan2_step', 'tfx_adam_atan2_args', dict(eps=123., atan2_a=a, atan2_b=b), 456., n, p, g, m, v, step, groups, ranges,
+                        skip, max_norm, sumsq)
+
+
+def launch_adam_groups(n, p, g, m, v, step, groups, ranges, skip, max_norm, eps, sumsq=None):
+    """the same for one tfx_adam_step_groups (the other rule of the kernel template), every group with `eps`"""
+    return launch_entry('tfx_adam_step_groups', 'tfx_adam_group_args', dict(eps=eps), eps, n, p, g, m, v, step, groups, ranges, skip, max_norm, sumsq)
+
+
+def launch_entry(entry, struct_, fields, group_eps, n, p, g, m, v, step, groups, ranges, skip, max_norm, sumsq):
     (wp, dp), (wm, dm), (wv, dv) = guarded(p), guarded(m), guarded(v)
     dg = torch.from_numpy(g).to(DEV)
     g0 = groups[0]
-    kw = dict(p=dp, g=dg, m=dm, v=dv, n=n, lr=g0['lr'], beta1=g0['betas'][0], beta2=g0['betas'][1], eps=123., weight_decay=g0.get('weight_decay', 0.),
-              decoupled=int(g0.get('decoupled_weight_decay', False)), max_norm=max_norm, grad_scale=1., step=step, atan2_a=a, atan2_b=b)
+    kw = dict(p=dp, g=dg, m=dm, v=dv, n=n, lr=g0['lr'], beta1=g0['betas'][0], beta2=g0['betas'][1], weight_decay=g0.get('weight_decay', 0.),
+              decoupled=int(g0.get('decoupled_weight_decay', False)), max_norm=max_norm, grad_scale=1., step=step, **fields)
     keep = [dg]
     if max_norm > 0:
         keep.append(torch.tensor([sumsq], dtype=torch.float32, device=DEV)); kw['sumsq'] = keep[-1]
     if ranges:
         keep.append(torch.tensor(ranges, dtype=torch.int64, device=DEV).reshape(-1))
         kw.update(ranges=keep[-1], nrange=len(ranges), ngroup=len(groups), group_lr=[x['lr'] for x in groups], group_beta1=[x['betas'][0] for x in groups],
-                  group_beta2=[x['betas'][1] for x in groups], group_eps=[456.] * len(groups), group_weight_decay=[x.get('weight_decay', 0.) for x in groups],
+                  group_beta2=[x['betas'][1] for x in groups], group_eps=[group_eps] * len(groups), group_weight_decay=[x.get('weight_decay', 0.) for x in groups],
                   group_decoupled=[int(x.get('decoupled_weight_decay', False)) for x in groups])
     if skip:
         keep.append(torch.tensor(skip, dtype=torch.int64, device=DEV).reshape(-1))
         kw.update(skip=keep[-1], nskip=len(skip))
-    capi.call('tfx_adam_atan2_step', capi.make_args('tfx_adam_atan2_args', **kw), stream())
+    capi.call(entry, capi.make_args(struct_, **kw), stream())
     torch.cuda.synchronize()
     for w in (wp, wm, wv):
         assert guards_intact(w, n), 'written outside the buffer'
@@ -142,6 +152,27 @@ def test_launch_is_repeatable_to_the_bit():
     runs = [launch(n, p, g, m, v, 3, C.three_groups(), ranges, C.skip_layout(n), 0.5, 1.27, 0.5, sumsq) for _ in range(2)]
     for x, y in zip(*runs):
         assert np.array_equal(x.view(np.uint32), y.view(np.uint32))
+
+
+def test_moments_are_the_same_bits_under_both_rules():
+    """the two rules are one kernel template (`flat_rule_k`) and differ in the update of p alone: over the same inputs, groups, skip table and clip,
+    tfx_adam_atan2_step and tfx_adam_step_groups leave the same bits in m and v"""
+    step, bits = 2, lambda t: t.view(np.uint32)
+    for n in SIZES:
+        p, g, m, v = C.make_inputs(n, seed=n + step, gscale=0.05, state=True)
+        groups, (ranges, _), skip = C.three_groups(), C.group_layout(n), C.skip_layout(n)
+        sumsq = float(np.float32((g.astype(np.float64) ** 2).sum()))
+        max_norm = 0.5 * float(np.sqrt(sumsq))
+        assert 0.4 < C.coef_f32(sumsq, max_norm) < 0.6                       # the clip is on
+        atan2 = launch(n, p, g, m, v, step, groups, ranges, skip, max_norm, 1.27, 0.5, sumsq)
+        adam = launch_adam_groups(n, p, g, m, v, step, groups, ranges, skip, max_norm, 1e-8, sumsq)
+        assert np.array_equal(bits(atan2[1]), bits(adam[1])) and np.array_equal(bits(atan2[2]), bits(adam[2])), n
+        assert not np.array_equal(atan2[1], m) and not np.array_equal(atan2[2], v), n
+        for s, e in skip:
+            for got in (atan2, adam):
+                for t, t0 in zip(got, (p, m, v)):
+                    assert np.array_equal(bits(t[s:e]), bits(t0[s:e])), 'a skipped element changed'
+        assert not np.array_equal(atan2[0], adam[0]), n
 
 
 # ---------------------------------------------------------------------------------------------------------------- the optimizer classes

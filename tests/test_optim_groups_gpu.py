@@ -1,4 +1,4 @@
-"""Parameter groups, decoupled weight decay and resumable state of optim.FusedAdam / FusedMuon on the MI355X (csrc/tokenwise.hip `adam_groups_k`).
+"""Parameter groups, decoupled weight decay and resumable state of optim.FusedAdam / FusedMuon on the MI355X (csrc/tokenwise.hip `flat_rule_k<adam_rule>`).
 
 Gradients are INJECTED (a seeded tensor in `model.store.grad`, `p.grad` of the external parameters): the training backward sums with fp32 atomics
 and is not repeatable to the bit, the optimizer kernels are - with the fixed-order clip norm (`deterministic_norm`) or no clip, where bits are compared.

@@ -1,5 +1,5 @@
 """Idle time BETWEEN kernels in a rocprofv3 kernel trace (csv) of bench.py on ONE stream (TFX_SIDE_STREAM=0): for the last `--steps` training
-steps (delimited by the optimizer kernel `adam_k`), wall time of the step on the GPU, sum of kernel durations, and the distribution of the gaps
+steps (delimited by the optimizer's closing launch, `adam_k` or `flat_rule_k`), wall time of the step on the GPU, sum of kernel durations, and the distribution of the gaps
 between one kernel's end and the next kernel's start.  Tells what a hipGraph replay of the training step could win at most.
     python tools/prof_gaps.py trace.csv [--steps 2]"""
 import csv
@@ -10,7 +10,7 @@ def main():
     path = sys.argv[1]
     steps = int(sys.argv[sys.argv.index('--steps') + 1]) if '--steps' in sys.argv else 2
     rows = sorted(csv.DictReader(open(path)), key=lambda r: int(r['Start_Timestamp']))
-    ends = [i for i, r in enumerate(rows) if 'adam_k' in r['Kernel_Name']]
+    ends = [i for i, r in enumerate(rows) if any(k in r['Kernel_Name'] for k in ('adam_k', 'flat_rule_k'))]
     assert len(ends) > steps, 'not enough optimizer launches in the trace'
     for s in range(steps):
         lo, hi = ends[-s - 2] + 1, ends[-s - 1]

@@ -22,10 +22,10 @@ def main():
     steps = int(sys.argv[sys.argv.index('--steps') + 1]) if '--steps' in sys.argv else 1
     rows = list(csv.DictReader(open(path)))
     if '--steady' in sys.argv:
-        # steady state only: the kernels between the first and the last optimizer launch (`adam_k` closes a training step) - model construction,
+        # steady state only: the kernels between the first and the last optimizer launch (`adam_k` or `flat_rule_k` closes a training step) - model construction,
         # warm-up allocation and the synthetic-batch generator (hundreds of tiny at:: kernels) stay out of the per-step figures
         rows.sort(key=lambda r: int(r['Start_Timestamp']))
-        marks = [i for i, r in enumerate(rows) if 'adam_k' in r['Kernel_Name']]
+        marks = [i for i, r in enumerate(rows) if any(k in r['Kernel_Name'] for k in ('adam_k', 'flat_rule_k'))]
         assert len(marks) >= 2, 'need at least two optimizer launches for --steady'
         spans = [(a + 1, b + 1) for a, b in zip(marks[:-1], marks[1:])]
         small = min(b - a for a, b in spans)

@@ -2046,25 +2046,59 @@ __global__ __launch_bounds__(256) void adam_k(tfx_adam_args p, float step_size, 
   }
 }
 
-// ---- the same step with parameter groups / decoupled decay (tfx_adam_step_groups).  adam_k stays as it is: the SLP vectoriser packs any edited form of
-// its body differently (last bits of p, m, v move - LAB_NOTEBOOK, "The Adam skip table and bit-identity").  Here every rounding is spelled out instead,
-// under `fp contract(off)`, as the operations adam_k's vector path compiles to (ISA read off the library):
-//   g  = g coef;  g = fma(wd, p, g) if wd != 0            m = fma(beta1, m, (1 - beta1) g)          v = fma(beta2, v, g ((1 - beta2) g))
-//   p -= (step_size m) / fma(sqrt(v), inv_sqrt_bc2, eps)  coef = grad_scale min(1, max_norm / fma(sqrt(sumsq), grad_scale, 1e-6))
-// so the two copies of the body below (group in SGPRs / group per thread) and adam_k agree to the bit whenever their scalars do.
-struct adam_consts {      // per group, host side of the launch: lr / bc1, 1 / sqrt(bc2), the L2 coefficient (0 where decoupled), 1 - lr wd (1 where not)
+// ---- the grouped launches over the flat buffer: one kernel template, one rule per entry point (tfx_adam_step_groups, tfx_adam_atan2_step; tfx.h has
+// the rules).  adam_k stays as it is: the SLP vectoriser packs any edited form of its body differently (last bits of p, m, v move - LAB_NOTEBOOK, "The
+// Adam skip table and bit-identity").  Here every rounding is spelled out instead, under `fp contract(off)`, as the operations adam_k's vector path
+// compiles to (ISA read off the library):
+//   g  = g coef;  w = p keep;  g = fma(l2, w, g) if l2 != 0     m = fma(beta1, m, (1 - beta1) g)          v = fma(beta2, v, g ((1 - beta2) g))
+//   p  = rule.update(w, m, v)                                   coef = grad_scale min(1, max_norm / fma(sqrt(sumsq), grad_scale, 1e-6))
+// so the two copies of the body below (group in SGPRs / group per thread) and adam_k agree to the bit whenever their scalars do, and the moments are
+// the same bits under every rule.  The kernel itself is the template: old-named kernels that only call a shared inlined body compile to another
+// control flow of the skip search (LAB_NOTEBOOK, "One kernel template for the grouped launches").
+// A rule: `consts`, the per-group records the host side of the launch fills (a kernel argument: struct of arrays, field order fixed); the scalars of one
+// group; `of(consts, group index)`; `update(w, m, v)`, the new parameter.  beta1, beta2, l2 (the L2 coefficient, 0 where decoupled) and keep (1 - lr wd
+// where decoupled, else 1) are every rule's.
+static_assert((TFX_ADAM_MAX_GROUPS & (TFX_ADAM_MAX_GROUPS - 1)) == 0, "group indices are masked into the records");
+struct adam_consts {      // step_size = lr / bc1, inv_sqrt_bc2 = 1 / sqrt(bc2)
   float step_size[TFX_ADAM_MAX_GROUPS], inv_sqrt_bc2[TFX_ADAM_MAX_GROUPS], beta1[TFX_ADAM_MAX_GROUPS], beta2[TFX_ADAM_MAX_GROUPS],
         eps[TFX_ADAM_MAX_GROUPS], l2[TFX_ADAM_MAX_GROUPS], keep[TFX_ADAM_MAX_GROUPS];
 };
-struct adam_group { float step_size, inv_sqrt_bc2, beta1, beta2, eps, l2, keep; };
-static_assert((TFX_ADAM_MAX_GROUPS & (TFX_ADAM_MAX_GROUPS - 1)) == 0, "group indices are masked into the records");
+struct atan2_consts {     // lr_a = lr a, inv_bc1 = 1 / bc1, b_inv_sqrt_bc2 = b / sqrt(bc2)
+  float lr_a[TFX_ADAM_MAX_GROUPS], inv_bc1[TFX_ADAM_MAX_GROUPS], b_inv_sqrt_bc2[TFX_ADAM_MAX_GROUPS], beta1[TFX_ADAM_MAX_GROUPS],
+        beta2[TFX_ADAM_MAX_GROUPS], l2[TFX_ADAM_MAX_GROUPS], keep[TFX_ADAM_MAX_GROUPS];
+};
 
-TFX_DEV adam_group adam_group_of(const adam_consts& c, int gi) {
-  gi &= TFX_ADAM_MAX_GROUPS - 1;                        // whatever the device table says, the read stays inside the records
-  return {c.step_size[gi], c.inv_sqrt_bc2[gi], c.beta1[gi], c.beta2[gi], c.eps[gi], c.l2[gi], c.keep[gi]};
-}
+// Adam: p = w - (step_size m) / fma(sqrt(v), inv_sqrt_bc2, eps)
+struct adam_rule {
+  using consts = adam_consts;
+  float step_size, inv_sqrt_bc2, beta1, beta2, eps, l2, keep;
+  static TFX_DEV adam_rule of(const consts& c, int gi) {
+    gi &= TFX_ADAM_MAX_GROUPS - 1;                      // whatever the device table says, the read stays inside the records
+    return {c.step_size[gi], c.inv_sqrt_bc2[gi], c.beta1[gi], c.beta2[gi], c.eps[gi], c.l2[gi], c.keep[gi]};
+  }
+  TFX_DEV float update(float w, float m, float v) const {
+#pragma clang fp contract(off)
+    return w - (step_size * m) / __builtin_fmaf(sqrtf(v), inv_sqrt_bc2, eps);
+  }
+};
 
-TFX_DEV void adam_group4(const tfx_adam_group_args& p, long long i, int cnt, float coef, const adam_group s, const f32x4 g4, const f32x4 w4, f32x4 m4, f32x4 v4) {
+// Adam-atan2: p = w - lr_a atan2f(m inv_bc1, sqrt(v) b_inv_sqrt_bc2).  atan2f is the device library's; sqrtf is correctly rounded.
+struct atan2_rule {
+  using consts = atan2_consts;
+  float lr_a, inv_bc1, b_inv_sqrt_bc2, beta1, beta2, l2, keep;
+  static TFX_DEV atan2_rule of(const consts& c, int gi) {
+    gi &= TFX_ADAM_MAX_GROUPS - 1;
+    return {c.lr_a[gi], c.inv_bc1[gi], c.b_inv_sqrt_bc2[gi], c.beta1[gi], c.beta2[gi], c.l2[gi], c.keep[gi]};
+  }
+  TFX_DEV float update(float w, float m, float v) const {
+#pragma clang fp contract(off)
+    const float theta = atan2f(m * inv_bc1, sqrtf(v) * b_inv_sqrt_bc2);
+    return w - lr_a * theta;
+  }
+};
+
+template <class Rule, class Args>
+TFX_DEV void rule_group4(const Args& p, long long i, int cnt, float coef, const Rule s, const f32x4 g4, const f32x4 w4, f32x4 m4, f32x4 v4) {
 #pragma clang fp contract(off)
   const float omb1 = 1.f - s.beta1, omb2 = 1.f - s.beta2;
   f32x4 o4;
@@ -2075,7 +2109,7 @@ TFX_DEV void adam_group4(const tfx_adam_group_args& p, long long i, int cnt, flo
     if (s.l2 != 0.f) g = __builtin_fmaf(s.l2, w, g);
     m4[e] = __builtin_fmaf(s.beta1, m4[e], omb1 * g);
     v4[e] = __builtin_fmaf(s.beta2, v4[e], g * (omb2 * g));
-    o4[e] = w - (s.step_size * m4[e]) / __builtin_fmaf(sqrtf(v4[e]), s.inv_sqrt_bc2, s.eps);
+    o4[e] = s.update(w, m4[e], v4[e]);
   }
   if (cnt == 4) { *(f32x4*)(p.m + i) = m4; *(f32x4*)(p.v + i) = v4; *(f32x4*)(p.p + i) = o4; }
   else {
@@ -2091,7 +2125,8 @@ TFX_DEV int adam_range_behind(const long long* ranges, int nrange, long long i) 
   return lo;
 }
 
-__global__ __launch_bounds__(256) void adam_groups_k(tfx_adam_group_args p, adam_consts c) {
+template <class Rule, class Args>
+__global__ __launch_bounds__(256) void flat_rule_k(Args p, typename Rule::consts c) {
   // as adam_k: 4 parameters per thread, 1024 per block
   const long long b0 = (long long)blockIdx.x * 1024, i = b0 + (long long)threadIdx.x * 4;
   if (i >= p.n) return;
@@ -2125,89 +2160,11 @@ __global__ __launch_bounds__(256) void adam_groups_k(tfx_adam_group_args p, adam
     else whole = 0;
   }
   if (whole) {
-    adam_group4(p, i, cnt, coef, adam_group_of(c, __builtin_amdgcn_readfirstlane(gi)), g4, w4, m4, v4);
+    rule_group4(p, i, cnt, coef, Rule::of(c, __builtin_amdgcn_readfirstlane(gi)), g4, w4, m4, v4);
   } else {
     const int r = adam_range_behind(ranges, p.nrange, i);
     gi = (r < p.nrange && ranges[3 * r] <= i) ? (int)ranges[3 * r + 2] : 0;
-    adam_group4(p, i, cnt, coef, adam_group_of(c, gi), g4, w4, m4, v4);
-  }
-}
-
-// ---- the Adam-atan2 rule (tfx_adam_atan2_step; tfx.h has the rule and where it is restated from).  A kernel of its own on adam_groups_k's scheme -
-// adam_k and adam_groups_k stay as they are, to the instruction (see above) - with the roundings spelled out under `fp contract(off)`:
-//   g = g coef;  w = p keep;  g = fma(l2, w, g) if l2 != 0;  m = fma(beta1, m, (1 - beta1) g);  v = fma(beta2, v, g ((1 - beta2) g))
-//   p = w - lr_a atan2f(m inv_bc1, sqrt(v) b_inv_sqrt_bc2)
-// atan2f is the device library's; sqrtf is correctly rounded.
-struct atan2_consts {     // per group, host side of the launch: lr a, 1 / bc1, b / sqrt(bc2), the L2 coefficient (0 where decoupled), 1 - lr wd (1 where not)
-  float lr_a[TFX_ADAM_MAX_GROUPS], inv_bc1[TFX_ADAM_MAX_GROUPS], b_inv_sqrt_bc2[TFX_ADAM_MAX_GROUPS], beta1[TFX_ADAM_MAX_GROUPS],
-        beta2[TFX_ADAM_MAX_GROUPS], l2[TFX_ADAM_MAX_GROUPS], keep[TFX_ADAM_MAX_GROUPS];
-};
-struct atan2_group { float lr_a, inv_bc1, b_inv_sqrt_bc2, beta1, beta2, l2, keep; };
-
-TFX_DEV atan2_group atan2_group_of(const atan2_consts& c, int gi) {
-  gi &= TFX_ADAM_MAX_GROUPS - 1;                        // whatever the device table says, the read stays inside the records
-  return {c.lr_a[gi], c.inv_bc1[gi], c.b_inv_sqrt_bc2[gi], c.beta1[gi], c.beta2[gi], c.l2[gi], c.keep[gi]};
-}
-
-TFX_DEV void adam_atan2_group4(const tfx_adam_atan2_args& p, long long i, int cnt, float coef, const atan2_group s, const f32x4 g4, const f32x4 w4, f32x4 m4, f32x4 v4) {
-#pragma clang fp contract(off)
-  const float omb1 = 1.f - s.beta1, omb2 = 1.f - s.beta2;
-  f32x4 o4;
-#pragma unroll
-  for (int e = 0; e < 4; e++) {
-    float g = g4[e] * coef;
-    const float w = w4[e] * s.keep;
-    if (s.l2 != 0.f) g = __builtin_fmaf(s.l2, w, g);
-    m4[e] = __builtin_fmaf(s.beta1, m4[e], omb1 * g);
-    v4[e] = __builtin_fmaf(s.beta2, v4[e], g * (omb2 * g));
-    const float theta = atan2f(m4[e] * s.inv_bc1, sqrtf(v4[e]) * s.b_inv_sqrt_bc2);
-    o4[e] = w - s.lr_a * theta;
-  }
-  if (cnt == 4) { *(f32x4*)(p.m + i) = m4; *(f32x4*)(p.v + i) = v4; *(f32x4*)(p.p + i) = o4; }
-  else {
-#pragma unroll
-    for (int e = 0; e < 3; e++) if (e < cnt) { p.m[i + e] = m4[e]; p.v[i + e] = v4[e]; p.p[i + e] = o4[e]; }
-  }
-}
-
-__global__ __launch_bounds__(256) void adam_atan2_k(tfx_adam_atan2_args p, atan2_consts c) {
-  // as adam_groups_k: 4 parameters per thread, 1024 per block, the skip table, the streams in front of the table search
-  const long long b0 = (long long)blockIdx.x * 1024, i = b0 + (long long)threadIdx.x * 4;
-  if (i >= p.n) return;
-  if (p.nskip > 0) {
-    int lo = 0, hi = p.nskip;
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (p.skip[2 * mid + 1] > i) hi = mid; else lo = mid + 1; }
-    if (lo < p.nskip && p.skip[2 * lo] <= i) return;
-  }
-  const int cnt = i + 4 <= p.n ? 4 : (int)(p.n - i);
-  f32x4 g4 = {0.f, 0.f, 0.f, 0.f}, w4 = g4, m4 = g4, v4 = g4;
-  if (cnt == 4) { g4 = *(const f32x4*)(p.g + i); w4 = *(const f32x4*)(p.p + i); m4 = *(const f32x4*)(p.m + i); v4 = *(const f32x4*)(p.v + i); }
-  else {
-#pragma unroll
-    for (int e = 0; e < 3; e++) if (e < cnt) { g4[e] = p.g[i + e]; w4[e] = p.p[i + e]; m4[e] = p.m[i + e]; v4[e] = p.v[i + e]; }
-  }
-  float coef;
-  {
-#pragma clang fp contract(off)
-    coef = p.grad_scale;
-    if (p.max_norm > 0.f) coef = p.grad_scale * fminf(1.f, p.max_norm / __builtin_fmaf(sqrtf(p.sumsq[0]), p.grad_scale, 1e-6f));
-  }
-  const long long* ranges = (const long long*)p.ranges;
-  int whole = 1, gi = 0;                                 // no table: one group, record 0
-  if (p.nrange > 0) {
-    const long long b1 = b0 + 1024 < p.n ? b0 + 1024 : p.n;
-    const int r = adam_range_behind(ranges, p.nrange, b0);         // the same for every thread of the block
-    if (r >= p.nrange) gi = 0;                                      // behind the last range
-    else if (ranges[3 * r] <= b0 && ranges[3 * r + 1] >= b1) gi = (int)ranges[3 * r + 2];
-    else if (ranges[3 * r] >= b1) gi = 0;                           // the block lies in a gap in front of range r
-    else whole = 0;
-  }
-  if (whole) {
-    adam_atan2_group4(p, i, cnt, coef, atan2_group_of(c, __builtin_amdgcn_readfirstlane(gi)), g4, w4, m4, v4);
-  } else {
-    const int r = adam_range_behind(ranges, p.nrange, i);
-    gi = (r < p.nrange && ranges[3 * r] <= i) ? (int)ranges[3 * r + 2] : 0;
-    adam_atan2_group4(p, i, cnt, coef, atan2_group_of(c, gi), g4, w4, m4, v4);
+    rule_group4(p, i, cnt, coef, Rule::of(c, gi), g4, w4, m4, v4);
   }
 }
 
@@ -2350,6 +2307,40 @@ __global__ __launch_bounds__(256) void mfma_peak_k(const bf16x8* ops, float* out
   float sm = 0.f;
   for (int i = 0; i < 16; i++) sm += c0[i] + c1[i] + c2[i] + c3[i];
   if (sm == 1.2345f) out[1] = sm;
+}
+
+// ---- host side of the grouped launches over the flat buffer (flat_rule_k): what tfx_adam_step_groups and tfx_adam_atan2_step share.
+// tfx_adam_atan2_args BEGINS with tfx_adam_group_args (tfx.h; the ABI tests pin the offsets), so both are read through that prefix.
+static inline bool flat_rule_refused(const tfx_adam_group_args& a) {
+  if (a.n < 0 || (((uintptr_t)a.p | (uintptr_t)a.g | (uintptr_t)a.m | (uintptr_t)a.v) & 15)) return true;
+  if (a.nskip < 0 || (a.nskip > 0 && !a.skip)) return true;
+  if (a.nrange < 0 || (a.nrange > 0 && (!a.ranges || a.ngroup < 1 || a.ngroup > TFX_ADAM_MAX_GROUPS))) return true;
+  return a.max_norm > 0.f && !a.sumsq;
+}
+struct group_record { float lr, b1, b2, eps, wd; bool dec; double bc1, bc2; float l2, keep; };
+// record g of the launch.  No table: the one group of the global fields.  Records behind ngroup repeat record 0 (a table cannot index outside the
+// records: Rule::of masks).  l2 = the L2 coefficient (0 where decoupled), keep = 1 - lr wd (1 where not)
+static inline group_record group_record_of(const tfx_adam_group_args& a, int g) {
+  const bool tab = a.nrange > 0;
+  const int k = tab && g < a.ngroup ? g : 0;
+  group_record r;
+  r.lr = tab ? a.group_lr[k] : a.lr; r.b1 = tab ? a.group_beta1[k] : a.beta1; r.b2 = tab ? a.group_beta2[k] : a.beta2;
+  r.eps = tab ? a.group_eps[k] : a.eps; r.wd = tab ? a.group_weight_decay[k] : a.weight_decay;
+  r.dec = (tab ? a.group_decoupled[k] : a.decoupled) != 0;
+  r.bc1 = 1.0 - pow((double)r.b1, (double)a.step); r.bc2 = 1.0 - pow((double)r.b2, (double)a.step);
+  r.l2 = r.dec ? 0.f : r.wd;
+  r.keep = r.dec ? (float)(1.0 - (double)r.lr * (double)r.wd) : 1.f;
+  return r;
+}
+template <class Rule, class Args, class Fill>
+static int flat_rule_launch(const Args& a, void* s, Fill fill) {
+  const tfx_adam_group_args& ga = reinterpret_cast<const tfx_adam_group_args&>(a);
+  if (ga.n == 0) return 0;
+  if (flat_rule_refused(ga)) return -1;
+  typename Rule::consts c;
+  for (int g = 0; g < TFX_ADAM_MAX_GROUPS; g++) fill(c, g, group_record_of(ga, g));
+  const long long nthr = (ga.n + 3) / 4;
+  hipLaunchKernelGGL((flat_rule_k<Rule, Args>), dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, ST(s), a, c); RET();
 }
 
 extern "C" {
@@ -2546,51 +2537,17 @@ int tfx_adam_step_groups(const tfx_adam_group_args* a, void* s) {
     b.skip = a->skip; b.nskip = a->nskip;
     return tfx_adam_step(&b, s);
   }
-  if (a->n == 0) return 0;
-  if (a->n < 0 || (((uintptr_t)a->p | (uintptr_t)a->g | (uintptr_t)a->m | (uintptr_t)a->v) & 15)) return -1;
-  if (a->nskip < 0 || (a->nskip > 0 && !a->skip)) return -1;
-  if (a->nrange < 0 || (a->nrange > 0 && (!a->ranges || a->ngroup < 1 || a->ngroup > TFX_ADAM_MAX_GROUPS))) return -1;
-  if (a->max_norm > 0.f && !a->sumsq) return -1;
-  adam_consts c;
-  for (int g = 0; g < TFX_ADAM_MAX_GROUPS; g++) {
-    // no table: the one group of the global fields.  Records behind ngroup repeat record 0 (a table cannot index outside the records: adam_group_of)
-    const int k = a->nrange > 0 && g < a->ngroup ? g : 0;
-    const bool tab = a->nrange > 0;
-    const float lr = tab ? a->group_lr[k] : a->lr, b1 = tab ? a->group_beta1[k] : a->beta1, b2 = tab ? a->group_beta2[k] : a->beta2;
-    const float wd = tab ? a->group_weight_decay[k] : a->weight_decay;
-    const bool dec = (tab ? a->group_decoupled[k] : a->decoupled) != 0;
-    const double bc1 = 1.0 - pow((double)b1, (double)a->step), bc2 = 1.0 - pow((double)b2, (double)a->step);
-    c.step_size[g] = (float)(lr / bc1); c.inv_sqrt_bc2[g] = (float)(1.0 / sqrt(bc2));
-    c.beta1[g] = b1; c.beta2[g] = b2; c.eps[g] = tab ? a->group_eps[k] : a->eps;
-    c.l2[g] = dec ? 0.f : wd;
-    c.keep[g] = dec ? (float)(1.0 - (double)lr * (double)wd) : 1.f;
-  }
-  const long long nthr = (a->n + 3) / 4;
-  hipLaunchKernelGGL(adam_groups_k, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, ST(s), *a, c); RET();
+  return flat_rule_launch<adam_rule>(*a, s, [](adam_consts& c, int g, const group_record& r) {
+    c.step_size[g] = (float)(r.lr / r.bc1); c.inv_sqrt_bc2[g] = (float)(1.0 / sqrt(r.bc2));
+    c.beta1[g] = r.b1; c.beta2[g] = r.b2; c.eps[g] = r.eps; c.l2[g] = r.l2; c.keep[g] = r.keep;
+  });
 }
 int tfx_adam_atan2_step(const tfx_adam_atan2_args* a, void* s) {
-  if (!a || !(a->atan2_a > 0.f) || !(a->atan2_b > 0.f) || a->step < 1) return -1;
-  if (a->n == 0) return 0;
-  if (a->n < 0 || (((uintptr_t)a->p | (uintptr_t)a->g | (uintptr_t)a->m | (uintptr_t)a->v) & 15)) return -1;
-  if (a->nskip < 0 || (a->nskip > 0 && !a->skip)) return -1;
-  if (a->nrange < 0 || (a->nrange > 0 && (!a->ranges || a->ngroup < 1 || a->ngroup > TFX_ADAM_MAX_GROUPS))) return -1;
-  if (a->max_norm > 0.f && !a->sumsq) return -1;
-  atan2_consts c;
-  for (int g = 0; g < TFX_ADAM_MAX_GROUPS; g++) {
-    // as tfx_adam_step_groups: no table = the one group of the global fields; records behind ngroup repeat record 0
-    const int k = a->nrange > 0 && g < a->ngroup ? g : 0;
-    const bool tab = a->nrange > 0;
-    const float lr = tab ? a->group_lr[k] : a->lr, b1 = tab ? a->group_beta1[k] : a->beta1, b2 = tab ? a->group_beta2[k] : a->beta2;
-    const float wd = tab ? a->group_weight_decay[k] : a->weight_decay;
-    const bool dec = (tab ? a->group_decoupled[k] : a->decoupled) != 0;
-    const double bc1 = 1.0 - pow((double)b1, (double)a->step), bc2 = 1.0 - pow((double)b2, (double)a->step);
-    c.lr_a[g] = (float)((double)lr * (double)a->atan2_a); c.inv_bc1[g] = (float)(1.0 / bc1); c.b_inv_sqrt_bc2[g] = (float)((double)a->atan2_b / sqrt(bc2));
-    c.beta1[g] = b1; c.beta2[g] = b2;
-    c.l2[g] = dec ? 0.f : wd;
-    c.keep[g] = dec ? (float)(1.0 - (double)lr * (double)wd) : 1.f;
-  }
-  const long long nthr = (a->n + 3) / 4;
-  hipLaunchKernelGGL(adam_atan2_k, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, ST(s), *a, c); RET();
+  if (!a || !(a->atan2_a > 0.f) || !(a->atan2_b > 0.f) || a->step < 1) return -1;     // (NaN fails the comparisons) in front of the n == 0 return
+  return flat_rule_launch<atan2_rule>(*a, s, [a](atan2_consts& c, int g, const group_record& r) {
+    c.lr_a[g] = (float)((double)r.lr * (double)a->atan2_a); c.inv_bc1[g] = (float)(1.0 / r.bc1); c.b_inv_sqrt_bc2[g] = (float)((double)a->atan2_b / sqrt(r.bc2));
+    c.beta1[g] = r.b1; c.beta2[g] = r.b2; c.l2[g] = r.l2; c.keep[g] = r.keep;
+  });
 }
 int tfx_output_to_flow(float* pred, const float* x, const float* eps, const int32_t* row_inst, const float* inst_time,
                        int32_t R, int32_t dl, float clean_eps, void* s) {

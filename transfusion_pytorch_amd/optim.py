@@ -185,6 +185,8 @@ class FusedAdam(torch.optim.Optimizer):
 
     deterministic_norm = False
     _GROUP_KEYS = _ADAM_KEYS          # what a parameter group of this rule carries
+    _RULE_LAUNCH = 'tfx_adam_step_groups', 'tfx_adam_group_args'      # the rule's entry point over the flat buffer and its args struct
+    _rule_fields = lambda self: {}    # hook: the by-value fields that struct has behind tfx_adam_group_args', checked
     lr, betas, eps, weight_decay = (_group_alias(k) for k in _ADAM_KEYS[:4])
 
     def __init__(self, model, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0., max_grad_norm=None, process_group=None,
@@ -440,14 +442,12 @@ class FusedAdam(torch.optim.Optimizer):
                     group_weight_decay=rec[4], group_decoupled=rec[5])
 
     def _launch_rule(self, ps, stream, groups, decoupled, common):
-        """the one launch over the flat buffer (a subclass with another per-element rule issues its own)"""
-        if len(groups) == 1 and not decoupled:              # the launch FusedAdam always made
-            capi.call('tfx_adam_step', capi.make_args('tfx_adam_args', **common), stream)
-        elif len(groups) == 1:
-            capi.call('tfx_adam_step_groups', capi.make_args('tfx_adam_group_args', decoupled=1, **common), stream)
-        else:
-            a = capi.make_args('tfx_adam_group_args', decoupled=decoupled, **self._group_table(ps, groups), **common)
-            capi.call('tfx_adam_step_groups', a, stream)
+        """the one launch over the flat buffer: the rule's entry point, the group table only for more than one group"""
+        entry, args = self._RULE_LAUNCH
+        fields = dict(self._rule_fields(), decoupled=decoupled, **(self._group_table(ps, groups) if len(groups) > 1 else {}))
+        if entry == 'tfx_adam_step_groups' and len(groups) == 1 and not decoupled:      # the launch FusedAdam always made
+            entry, args, fields = 'tfx_adam_step', 'tfx_adam_args', {}
+        capi.call(entry, capi.make_args(args, **fields, **common), stream)
 
     def _step_other_rules(self, ps, stream, max_norm, gscale):
         """hook of subclasses that update part of the flat buffer by another rule, between the clip norm and the Adam launch: returns the device
@@ -908,6 +908,7 @@ class _Atan2Rule:
     `tfx_adam_atan2_step` as the launch over the flat buffer, AdamAtan2 for the external parameters"""
 
     _GROUP_KEYS = _ATAN2_KEYS
+    _RULE_LAUNCH = 'tfx_adam_atan2_step', 'tfx_adam_atan2_args'
 
     @property
     def eps(self):
@@ -924,11 +925,9 @@ class _Atan2Rule:
         lr, b1, b2, _, wd, dec = self._group_scalars(src)
         grp['lr'], grp['betas'], grp['weight_decay'], grp['decoupled_weight_decay'], grp['a'], grp['b'] = src['lr'], (b1, b2), wd, bool(dec), self.a, self.b
 
-    def _launch_rule(self, ps, stream, groups, decoupled, common):
+    def _rule_fields(self):
         _check_atan2_ab(self.a, self.b)
-        table = self._group_table(ps, groups) if len(groups) > 1 else {}
-        a = capi.make_args('tfx_adam_atan2_args', decoupled=decoupled, atan2_a=float(self.a), atan2_b=float(self.b), **table, **common)
-        capi.call('tfx_adam_atan2_step', a, stream)
+        return dict(atan2_a=float(self.a), atan2_b=float(self.b))
 
 
 class FusedAdamAtan2(_Atan2Rule, FusedAdam):
