@@ -13,6 +13,7 @@ pytestmark = pytest.mark.gpu
 
 from transfusion_pytorch_amd import capi  # noqa: E402
 from _gemm_cases import assert_elementwise, geglu_perm, nt_ref, tol_bf16, tol_f32  # noqa: E402,F401   (per-element bounds: tests/_gemm_cases.py)
+import _tokenwise_cases as TW  # noqa: E402   (the token-wise kernels' float64 references and per-element bounds)
 
 DEV = 'cuda'
 BF = torch.bfloat16
@@ -699,6 +700,9 @@ def test_adaln_pre_post(T, d):
     ref = torch.where(im, xh * (tr[ii, :d] + 1) + tr[ii, d:2 * d], xh * (gr + 1))
     ref.backward(du.float())
     check(f'adaln_pre fwd d{d}', u, ref, 6e-3)
+    u64, u_tol, mean64, rstd64, _, _ = TW.pre_fwd_ref(x, tok_inst, table, gt)
+    assert_elementwise(f'adaln_pre fwd d{d}', u, u64, u_tol, tile=(4, 512))
+    assert_elementwise('adaln_pre mean', mean[None], mean64[None], TW.E(d, x.double().abs().mean(-1))[None]); assert_elementwise('adaln_pre rstd', rstd[None], rstd64[None], TW.E(d, rstd64)[None])
     check('adaln_pre dx', dx.float() - dx0, xr.grad, 1.5e-2)
     check('adaln_pre dtable', dtable, tr.grad, 5e-3)
     check('adaln_pre dgamma_text', dgt, gr.grad, 5e-3)
@@ -714,6 +718,7 @@ def test_adaln_pre_post(T, d):
     ref = x.float() + torch.where(im, yr * tr[ii, 2 * d:3 * d].sigmoid(), yr * (lr + 1))
     ref.backward(g.float())
     check('adaln_post fwd', out, ref, 6e-3)
+    assert_elementwise('adaln_post fwd', out, *TW.post_fwd_ref(x, y, tok_inst, table[:, 2 * d:3 * d], ls), tile=(4, 512))
     check('adaln_post dy', dy, yr.grad, 6e-3)
     check('adaln_post dtable', dtable2, tr.grad, 5e-3)
     check('adaln_post dlayerscale', dls, lr.grad, 5e-3)
@@ -730,6 +735,8 @@ def test_rmsnorm(T, d):
     ref = F.normalize(xr, dim=-1) * d ** 0.5 * (gr + 1)
     ref.backward(dy.float())
     check('rmsnorm fwd', y, ref, 6e-3); check('rmsnorm dx', dx, xr.grad, 1e-2); check('rmsnorm dgamma', dg, gr.grad, 5e-3)
+    y64, y_tol, dx64, dx_tol, _ = TW.rmsnorm_ref(x, gm, dy)
+    assert_elementwise('rmsnorm fwd', y, y64, y_tol, tile=(4, 512)); assert_elementwise('rmsnorm dx', dx, dx64, dx_tol, tile=(4, 512))
 
 
 @pytest.mark.parametrize('T,d,L', [(500, 512, 5), (300, 64, 3), (100, 1024, 9), (64, 256, 1)])
@@ -1207,6 +1214,10 @@ def test_attnres_pull_backward_stack(T, d, D, segs, post):
     torch.cuda.synchronize()
     for l in range(D + 1):
         check(f'pull dH[{l}] (D={D}, d={d})', dH[l], Hr.grad[l], 2e-2)
+        j0 = max(l - 1, 0)          # per element: the sources of hidden l with the saved state and <g, out + err> the kernel read (TW.pull_ref)
+        ref, tol, _, _ = TW.pull_ref(H[l], [G[j] for j in range(j0, D)], saves[j0:], l, [outs[j].double() + errs[j].double() for j in range(j0, D)],
+                                     [wtab[0, j] for j in range(j0, D)], add=extra if l == 0 else None)
+        assert_elementwise(f'pull dH[{l}] (D={D}, d={d})', dH[l], ref, tol, tile=(4, 512))
     check('pull dgamma', dgm, gr.grad, 2e-2); check('pull dpq', dpq, pr.grad, 2e-2)
     for j in (0, D - 1):
         check(f'pull dgamma layer {j}', dgm[j], gr.grad[j], 3e-2); check(f'pull dpq layer {j}', dpq[j], pr.grad[j], 3e-2)

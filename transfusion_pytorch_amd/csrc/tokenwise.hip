@@ -525,8 +525,10 @@ template <int NC> __global__ __launch_bounds__(256) void rmsnorm_bwd_k(tfx_rmsno
 #pragma unroll
       for (int e = 0; e < 8; e++) { q += x.v[i][e] * x.v[i][e]; S += (1.f + g.v[i][e]) * dy.v[i][e] * x.v[i][e]; }
     q = wave_sum(q); S = wave_sum(S);
-    const float r = sqrtf((float)d) / fmaxf(sqrtf(q), 1e-12f);
-    const float k2 = r * r * r / d * S;
+    const float nrm = sqrtf(q);
+    const float r = sqrtf((float)d) / fmaxf(nrm, 1e-12f);
+    // under the clamp the denominator is a constant: no projection term (r^3 overflows fp32 there, and inf * 0 made an all-zero row's gradient NaN)
+    const float k2 = nrm > 1e-12f ? r * r * r / d * S : 0.f;
 #pragma unroll
     for (int i = 0; i < NC; i++)
 #pragma unroll
