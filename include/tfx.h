@@ -180,7 +180,9 @@ typedef struct {
                                * against B - every q and k row of this call (KV-cache rows included) must have been produced by tfx_qk_norm_rope_fwd (or the
                                * fused projection epilogue) under the SAME gammas / scales the plan was written from.  Rows from other gains, or without
                                * QK-norm, make the polynomial diverge silently outside [-B, B]: pass NULL for such inputs.  tfx_decode_attn (the
-                               * matrix-core-free decode kernel) ignores the plan and evaluates the data-dependent form. */
+                               * matrix-core-free decode kernel) ignores the plan and evaluates the data-dependent form.  In the forward against a KV
+                               * cache (n_kv > 0) the data-dependent form decides row by row, never from the wave's other rows: with or without a plan, a
+                               * query row's out and lse bits do not depend on the rows the launch carries beside it. */
   /* forward with a KV cache, optional (compacted decode steps): sample s of the launch owns the query rows q_row0[s] .. q_row0[s] + q_cnt[s] - 1 of the
    * token arrays (q, gate, kv_end, out) instead of rows s * n .. (`n` stays the per-sample maximum and sizes the grid; q_cnt[s] = 0: nothing to do);
    * keys / values are still the sample's n_kv cache rows.  Device arrays of `b` int32 each; NULL = the dense layout. */
@@ -210,7 +212,9 @@ int tfx_attn_bwd(const tfx_attn_args* a, void* stream);   /* prep + dK/dV kernel
 
 /* decode step (reference T:2279-2349, T:2409-2419): the forward kernel addressed against a KV cache - `n` NEW query rows per
  * sample, keys / values in a per-sample buffer of `n_kv` > 0 rows, kv_end[t] = visible cache length of query row t (own prefix + the block
- * being decoded).  Fails with -10 when n_kv == 0. */
+ * being decoded).  Fails with -10 when n_kv == 0.  One or two rows per sample in the dense layout run on a matrix-core-free rows kernel; three
+ * rows and more, and every compacted call (q_row0 or q_cnt set, whatever `n` is: the rows kernel addresses rows b * n .. only), run on the
+ * tiled forward kernel exactly as tfx_attn_fwd would. */
 int tfx_decode_attn(const tfx_attn_args* a, void* stream);
 
 /* LASER value transform (reference T:979-983: softclamp T:280-281, then exp): token-wise over T rows of H heads x 64 columns.

@@ -115,6 +115,10 @@ TFX_DEV float tanh_exact(float x) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f
 TFX_DEV f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
 TFX_DEV f32x2 bc2(float v) { f32x2 r = {v, v}; return r; }
 // in place: s <- cap*log2e*tanh(s/cap) for one 32x32 accumulator block
+// ROW (the forward against a KV cache): the data-dependent form decides per QUERY ROW, not per wave.  A lane holds 16 scores of one row (lane & 31;
+// the lane 32 further up holds the row's other 16 keys of the unit), and a decode step's row shares its wave with whatever rows its plan carries:
+// a choice voted over the wave would give the same token different bits in plans of different row counts (engine.py Plan, tile_attn).
+template <bool ROW = false>
 TFX_DEV void softcap16(f32x16& s, const SoftCap& cp) {
   if (cp.mode == 0) {                                           // (scalar branch) the layer's cubic
 #pragma unroll
@@ -130,6 +134,20 @@ TFX_DEV void softcap16(f32x16& s, const SoftCap& cp) {
   float amax = 0.f;
 #pragma unroll
   for (int r = 0; r < 16; r++) amax = fmaxf(amax, fabsf(s[r]));
+  if constexpr (ROW) {                                         // the row's own largest |s| of the unit: exact form above the bound, else x^9 (per-lane branch)
+    amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
+    if (amax > c.smax) {
+#pragma unroll
+      for (int r = 0; r < 16; r++) s[r] = c.cap2 * tanh_exact(s[r] * c.icap);
+    } else {
+#pragma unroll
+      for (int r = 0; r < 16; r++) {
+        const float u = s[r] * s[r];
+        s[r] = s[r] * fmaf(u, fmaf(u, fmaf(u, fmaf(u, c.k9, c.k7), c.k5), c.k3), c.k1);
+      }
+    }
+    return;
+  }
   if (__any(amax > c.smax)) {
 #pragma unroll
     for (int r = 0; r < 16; r++) s[r] = c.cap2 * tanh_exact(s[r] * c.icap);
@@ -382,14 +400,15 @@ TFX_DEV void fwd_phase(const f32x16& s_cur, f32x16& s_nxt, u32x4 (&p_prev)[2], u
   }
 }
 
-// soft-cap of the unit (polynomial degree by the wave's largest |score|, see softcap16), mask where the unit crosses kv_end, then the phase
+// soft-cap of the unit (polynomial degree by the wave's largest |score| - ROW: by each row's own -, see softcap16), mask where the unit crosses kv_end, then the phase
+template <bool ROW>
 TFX_DEV void fwd_phase_any(f32x16& s_cur, f32x16& s_nxt, u32x4 (&p_prev)[2], u32x4 (&p_cur)[2], f32x16 (&o)[2], const bf16x8 (&qf)[4],
                            const bf16* Kt_nxt, int kb_nxt, const bf16* Vt_prev, int kb_prev, float (&lsum)[2], const SoftCap& c, int key0, int kve,
                            bool mask, unsigned long long* ts = nullptr) {
 #ifdef TFX_ATTN_TIMING
   unsigned long long t0 = __builtin_readcyclecounter();
 #endif
-  softcap16(s_cur, c);
+  softcap16<ROW>(s_cur, c);
   if (mask) {                                                       // boundary units only (one or two per wave): exp2(-inf) = 0
 #pragma unroll
     for (int r = 0; r < 16; r++) s_cur[r] = key0 + (r & 3) + 8 * (r >> 2) < kve ? s_cur[r] : -__builtin_inff();
@@ -420,7 +439,8 @@ TFX_DEV void fwd_drain(u32x4 (&p_prev)[2], f32x16 (&o)[2], const bf16* Vt_prev, 
 // last two of a causal block - stay on the C++ phases below.  The statement follows the C++ loop's tile protocol (wait + barrier at the top of a tile, then the
 // requests for K(j + 2) / V(j + 1)) and its arithmetic order: the hand-over is at a tile boundary and the outputs are bit-identical to the <false> form.
 // Training layouts only (no KV cache, no compacted rows: kv_end non-decreasing over a sample's rows), soft-cap plan modes 0 / 1.
-template <bool ASM>
+// ROW: the instance of the launches against a KV cache (n_kv > 0, dense or compacted rows) - softcap16<true>, nothing else differs.
+template <bool ASM, bool ROW = false>
 __global__ __launch_bounds__(256, 2) void attn_fwd_pipe_kernel(tfx_attn_args p) {
   __shared__ __attribute__((aligned(1024))) bf16 Ks[3][64 * 64];      // rings of LDS-DMA tiles (see swz_f): K(j), K(j+1), K(j+2) / V(j-1), V(j), V(j+1)
   __shared__ __attribute__((aligned(1024))) bf16 Vs[3][64 * 64];
@@ -554,10 +574,10 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_pipe_kernel(tfx_attn_args p) 
     // even unit u = 2j: softmax of sA -> pA; P.V of unit 2j - 1 (pB, second half of V(j - 1); p = 0 for j = 0); S of unit 2j + 1 -> sB.
     // Units past a wave's last visible key run fully masked (p = 0): no per-wave control flow around the accumulators.
     int u = 2 * j;
-    fwd_phase_any(sA, sB, pB, pA, o, qf, Ks[kslot], 1, j == 0 ? Vs[vslot] : Vs[vprev], 1, lsum, sc_, u * 32 + 4 * hi, kve, (u + 1) * 32 > kve_min TS_ARG);
+    fwd_phase_any<ROW>(sA, sB, pB, pA, o, qf, Ks[kslot], 1, j == 0 ? Vs[vslot] : Vs[vprev], 1, lsum, sc_, u * 32 + 4 * hi, kve, (u + 1) * 32 > kve_min TS_ARG);
     // odd unit u = 2j + 1: softmax of sB -> pB; P.V of unit 2j (pA, first half of V(j)); S of unit 2j + 2 -> sA (first half of K(j + 1))
     u = 2 * j + 1;
-    fwd_phase_any(sB, sA, pA, pB, o, qf, Ks[kslot1], 0, Vs[vslot], 0, lsum, sc_, u * 32 + 4 * hi, kve, (u + 1) * 32 > kve_min TS_ARG);
+    fwd_phase_any<ROW>(sB, sA, pA, pB, o, qf, Ks[kslot1], 0, Vs[vslot], 0, lsum, sc_, u * 32 + 4 * hi, kve, (u + 1) * 32 > kve_min TS_ARG);
     kslot = kslot1; vslot = vslot1;
 #ifdef TFX_ATTN_TIMING
     tprev = __builtin_readcyclecounter();
@@ -1204,6 +1224,7 @@ int attn_fwd(const tfx_attn_args& p, hipStream_t s) {
   static int use_asm = -1;
   if (use_asm < 0) { const char* e = getenv("TFX_ATTN_ASM"); use_asm = (e && e[0] == '1') ? 1 : 0; }
   if (use_asm && p.n_kv == 0 && !p.q_cnt && !p.q_row0 && p.sc_plan) hipLaunchKernelGGL(attn_fwd_pipe_kernel<true>, attn_grid(q), dim3(256), 0, s, q);
+  else if (p.n_kv > 0 || p.q_cnt || p.q_row0) hipLaunchKernelGGL((attn_fwd_pipe_kernel<false, true>), attn_grid(q), dim3(256), 0, s, q);
   else hipLaunchKernelGGL(attn_fwd_pipe_kernel<false>, attn_grid(q), dim3(256), 0, s, q);
   return (int)hipGetLastError();
 }

@@ -373,9 +373,11 @@ int tfx_decode_attn(const tfx_attn_args* a, void* s) {
   if ((long long)a->b * a->h == 0 || a->n <= 0) return 0;
   // one or two rows per sample (text steps): the multi-row kernel; from there on the tiled forward kernel with its cache addressing is the faster
   // one - both read the layer's whole KV cache and are HBM-bound (86 MB per launch at 128 cache rows x 330 keys: 21.6 us for five rows per sample
-  // here against 18.9 us there, rocprofv3 inside the continuous decode loop)
-  if (a->n == 1) return tfx::launch_decode_rows<1>(*a, (hipStream_t)s);
-  if (a->n == 2) return tfx::launch_decode_rows<2>(*a, (hipStream_t)s);
+  // here against 18.9 us there, rocprofv3 inside the continuous decode loop).  The multi-row kernel addresses the dense layout (rows b * n ..): a
+  // compacted call (q_row0 / q_cnt) goes to the tiled kernel, which takes the row ranges, whatever n is
+  const bool dense = !a->q_row0 && !a->q_cnt;
+  if (dense && a->n == 1) return tfx::launch_decode_rows<1>(*a, (hipStream_t)s);
+  if (dense && a->n == 2) return tfx::launch_decode_rows<2>(*a, (hipStream_t)s);
   return tfx::attn_fwd(*a, (hipStream_t)s);
 }
 }

@@ -201,7 +201,8 @@ class Plan:
         self.cache = cache
         # decode plans: `tile_attn` keeps the tiled forward kernel also for one or two new rows per sample (tfx_decode_attn would pick its
         # matrix-core-free kernel there) - the continuous decode schedule runs a sample's text token in plans of different row counts, and a token
-        # must come out of the same arithmetic whichever plan carried it (sample_many == per-prompt sample_one, reference tests :785-808)
+        # must come out of the same arithmetic whichever plan carried it (sample_many == per-prompt sample_one, reference tests :785-808; the kernel's
+        # cache instance takes no decision from a wave's other rows - attention.hip softcap16<ROW> - and tests/test_decode_attn_edges_gpu.py asserts the bits)
         self.tile_attn = tile_attn
         assert cache is None or not training
         self.dp_groups = dp_groups          # > 0: the backward list is cut into that many layer groups for the overlapped gradient all-reduce (optim.GradReducer)
