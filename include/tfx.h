@@ -80,7 +80,7 @@ typedef struct {
    * Fused in the 256 x 256 kernel (training shapes) and in the decode-step kernel (M <= 1024); every other shape runs as the plain projection
    * followed by tfx_qk_norm_rope_fwd inside the call - same results bit for bit. */
   int32_t qk_heads;
-  const float* qk_gamma_q; const float* qk_gamma_k;
+  const float* qk_gamma_q; const float* qk_gamma_k;   /* both NULL: no RMS normalisation (tfx_qk_norm_rope_args); one NULL and one set: -5 */
   const int32_t* qk_rot_pos; const float* qk_cos; const float* qk_sin;
   float qk_q_scale, qk_norm_scale;
   float* qk_plan; float qk_softcap;
@@ -157,7 +157,12 @@ int tfx_gemm_tn_plan(const tfx_gemm_tn_args* a, int32_t* kind, int32_t* tiles, i
 /* ---- attention ------------------------------------------------------------------------------- */
 /* q,k,v: bf16, token-major; element (token t, head h, i) at ptr[t*ld + h*64 + i]; dim_head == 64.
  * kv_end[t] (per token, relative to its sample): key j visible iff j < kv_end.  q_start[j]: first query
- * position that sees key j.  gate: logits at gate[t*ld_gate + h].  out: gated output og (bf16). */
+ * position that sees key j.  gate: logits at gate[t*ld_gate + h].  out: gated output og (bf16).
+ * gate == NULL: no value gating (reference Attention(gate_values=False), T:901-904, T:1026-1027) - sigmoid(gate) reads as exactly 1 everywhere:
+ *   forward (tfx_attn_fwd, and tfx_decode_attn on both of its kernels, dense and compacted): og = P v; under `laser`: og = log(P v')
+ *   backward prep (tfx_attn_bwd): do_eff = dout (laser: dout exp(-og)), delta as with a gate of 1; `dgate` is NOT written and may be NULL
+ * One wave-uniform branch per site.  With a gate pointer every kernel computes what it computed before NULL had a meaning, bit for bit, and a NULL
+ * call gives the bits of the same call with gate logits whose sigmoid is 1 in fp32 (tests/test_ablation_gpu.py). */
 typedef struct {
   const tfx_bf16 *q, *k, *v; int32_t ld_q, ld_k, ld_v;
   const tfx_bf16* gate; int32_t ld_gate;
@@ -172,7 +177,7 @@ typedef struct {
   const tfx_bf16* dout; int32_t ld_dout;     /* grad wrt gated output */
   tfx_bf16* do_eff; int32_t ld_do;           /* scratch: dout * sigmoid(gate) */
   float* delta;                               /* [b, h, n] */
-  tfx_bf16* dgate; int32_t ld_dgate;         /* grad wrt gate logits */
+  tfx_bf16* dgate; int32_t ld_dgate;         /* grad wrt gate logits (not written, may be NULL, when gate == NULL) */
   tfx_bf16 *dq, *dk, *dv; int32_t ld_dq, ld_dk, ld_dv;
   int32_t order;              /* set by the library (block order of the launch); callers leave it 0 */
   const float* sc_plan;       /* optional, forward and backward: the layer's soft-cap plan (tfx_qk_norm_rope_args.sc_plan); NULL = decide from the scores.
@@ -196,7 +201,8 @@ typedef struct {
    * aligned bases; nr_norm_scale 0 = 8. */
   const tfx_bf16* nr_qkv; int32_t nr_ld_qkv;
   tfx_bf16* nr_dqkv; int32_t nr_ld_dqkv;
-  const float* nr_gamma_q; const float* nr_gamma_k;
+  const float* nr_gamma_q; const float* nr_gamma_k;   /* both NULL: no RMS normalisation (tfx_qk_norm_rope_args): d q = q_scale rope^T(d q~), d k = rope^T(d k~), bit for
+                                                         * bit what tfx_qk_norm_rope_bwd writes; nr_qkv is not read, nr_dgamma_* are not touched and may be NULL */
   const int32_t* nr_rot_pos; const float* nr_cos; const float* nr_sin;
   float nr_q_scale, nr_norm_scale;
   float* nr_dgamma_q; float* nr_dgamma_k;
@@ -274,7 +280,14 @@ typedef struct {
   int32_t T, H;                               /* kernel layout: 64 columns per head; dim_head < 64 = zero columns past dim_head */
   const tfx_bf16* qkv; int32_t ld_qkv;        /* q at col h*64, k at col H*64 + h*64 (pre-norm) */
   tfx_bf16* qk; int32_t ld_qk;                /* post norm+rope(+q scale), same column layout */
-  const float* gamma_q; const float* gamma_k; /* [64] */
+  const float* gamma_q; const float* gamma_k; /* [64].  BOTH NULL: no RMS normalisation (reference Attention(qk_rmsnorm=False), T:948-952) -
+                                               *   forward  q~ = rope(q) q_scale, k~ = rope(k);   backward  dq = q_scale rope^T(dq~), dk = rope^T(dk~)
+                                               * `qkv` is not read by the backward, dgamma_* are not touched and may be NULL, norm_scale is ignored; the KV-cache
+                                               * append works as before.  A given `sc_plan` receives mode 2 with B = +inf in slot 7: nothing bounds
+                                               * unnormalised scores, so the polynomial modes are never chosen for them (the precondition of
+                                               * tfx_attn_args.sc_plan).  The token-wise kernel, the fused GEMM epilogue (tfx_gemm_nt_args.qk_gamma_*) and the
+                                               * attention backward's epilogues (tfx_attn_args.nr_gamma_*) share one spelling of the chunk (tfx_common.h) and agree
+                                               * bit for bit.  One NULL and one set is an error (-4). */
   const int32_t* rot_pos;                     /* [T] */
   const float* cos_tab; const float* sin_tab; /* [P, 32] */
   float q_scale;

@@ -266,6 +266,21 @@ TFX_DEV void wave_block_store_nr(bf16* st, const bf16x4 (&v)[2][4], const tfx_at
       const int col = db * 32 + 8 * rg + 4 * hi;
       *(bf16x4*)(st + r * 64 + (((col >> 3) ^ ((r >> 1) & 7)) << 3) + (col & 7)) = v[db][rg];
     }
+  if (!p.nr_gamma_q) {                                            // (kernel argument: uniform) no gains = no RMS normalisation (tfx.h): d q = q_scale rope^T(d q~),
+    const int last = max(rows_valid - 1, 0);                      // d k = rope^T(d k~) - tokenwise.hip's spelling (qk_rope_bwd_chunk), no raw chunk, no gain gradients
+    int pos[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) pos[q] = p.nr_rot_pos[tok + min(q * 8 + (l >> 3), last)];
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const int row = q * 8 + (l >> 3), rd = min(row, last);
+      const f32x4 cs = *(const f32x4*)(p.nr_cos + (size_t)pos[q] * 32 + ch * 4), sn = *(const f32x4*)(p.nr_sin + (size_t)pos[q] * 32 + ch * 4);
+      const bf16x8 t = *(const bf16x8*)(st + rd * 64 + ((ch ^ ((rd >> 1) & 7)) << 3));
+      const bf16x8 o = qk_rope_bwd_chunk(t, WHICH == 0 ? p.nr_q_scale : 1.f, cs, sn);
+      if (row < rows_valid) *(bf16x8*)(p.nr_dqkv + (tok + row) * p.nr_ld_dqkv + colq + ch * 8) = o;
+    }
+    return;
+  }
   const float sc = (WHICH == 0 ? p.nr_q_scale : 1.f) * (p.nr_norm_scale > 0.f ? p.nr_norm_scale : 8.f);
   const float* gmp = (WHICH == 0 ? p.nr_gamma_q : p.nr_gamma_k) + ch * 8;
   const f32x4 g0 = *(const f32x4*)gmp, g1 = *(const f32x4*)(gmp + 4);
@@ -597,7 +612,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_pipe_kernel(tfx_attn_args p) 
   float ls = lsum[0] + lsum[1];
   ls += __shfl_xor(ls, 32, 64);
   {
-    const float g = sigmoidf_(bf2f(p.gate[(tok0 + qc) * p.ld_gate + h]));
+    const float g = p.gate ? sigmoidf_(bf2f(p.gate[(tok0 + qc) * p.ld_gate + h])) : 1.f;      // (kernel argument: wave-uniform) NULL = no value gating
     bf16x4 ov[2][4];
     if (p.laser) {                                              // (kernel argument: wave-uniform) LASER: og = g log(P v'), T:1019-1022
       const float rl = __builtin_amdgcn_rcpf(ls);
@@ -624,6 +639,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_pipe_kernel(tfx_attn_args p) 
 
 // ------------------------------------------------------------------------------------------------
 // backward prep: delta = sum_d dout*og ; dgate = delta*(1-sigmoid(g)) ; do_eff = dout*sigmoid(g)
+// (gate == NULL, tfx.h: sigmoid(g) = 1 and dgate is not written)
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void attn_bwd_prep_kernel(tfx_attn_args p) {
   // 32-bit index math (the launcher checks b * n * h * 8 < 2^31): 64-bit divides by run-time values cost ~100 instructions each
@@ -635,7 +651,7 @@ __global__ __launch_bounds__(256) void attn_bwd_prep_kernel(tfx_attn_args p) {
   const unsigned t = vid / (unsigned)p.h; const int h = (int)(vid - t * p.h);
   const bf16x8 d8 = *(const bf16x8*)(p.dout + (size_t)t * p.ld_dout + h * DH + sub * 8);
   const bf16x8 o8 = *(const bf16x8*)(p.out + (size_t)t * p.ld_out + h * DH + sub * 8);
-  const float g = sigmoidf_(bf2f(p.gate[(size_t)t * p.ld_gate + h]));
+  const float g = p.gate ? sigmoidf_(bf2f(p.gate[(size_t)t * p.ld_gate + h])) : 1.f;      // (kernel argument: uniform) NULL = no value gating: g = 1, no dgate
   if (p.laser) {
     // LASER: og = g L with L = log O, O = P v'.  do_eff = dout g / O = dout g exp(-L); delta = do_eff . O = sum dout g (exact); dgate as below
     const float rg = __builtin_amdgcn_rcpf(fmaxf(g, 1e-30f));
@@ -651,7 +667,7 @@ __global__ __launch_bounds__(256) void attn_bwd_prep_kernel(tfx_attn_args p) {
     if (sub == 0) {
       const unsigned bb = t / (unsigned)p.n, i = t - bb * p.n;
       p.delta[((size_t)bb * p.h + h) * p.n + i] = ds * g;
-      p.dgate[(size_t)t * p.ld_dgate + h] = f2bf(dg * (1.f - g));
+      if (p.gate) p.dgate[(size_t)t * p.ld_dgate + h] = f2bf(dg * (1.f - g));
     }
     return;
   }
@@ -663,7 +679,7 @@ __global__ __launch_bounds__(256) void attn_bwd_prep_kernel(tfx_attn_args p) {
   if (sub == 0) {
     const unsigned bb = t / (unsigned)p.n, i = t - bb * p.n;
     p.delta[((size_t)bb * p.h + h) * p.n + i] = dl;
-    p.dgate[(size_t)t * p.ld_dgate + h] = f2bf(dl * (1.f - g));
+    if (p.gate) p.dgate[(size_t)t * p.ld_dgate + h] = f2bf(dl * (1.f - g));
   }
 }
 
@@ -779,7 +795,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(tfx_attn_args p) {
 #pragma unroll
       for (int e = 0; e < 8; e++) pg[e] = 0.f;
       wave_block_store_nr<0>((w < 2 ? Ks : Vs) + (w & 1) * 2048, ov, p, tok0 + q0 + w * 32, h * DH, n - (q0 + w * 32), pg);
-      nr_flush_dgamma(pg, sg, p.nr_dgamma_q);
+      if (p.nr_gamma_q) nr_flush_dgamma(pg, sg, p.nr_dgamma_q);
     } else
     wave_block_store((w < 2 ? Ks : Vs) + (w & 1) * 2048, ov, p.dq + (tok0 + q0 + w * 32) * p.ld_dq + h * DH, p.ld_dq, n - (q0 + w * 32));
   }
@@ -1040,7 +1056,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_pipe_kernel(tfx_attn_args 
 #pragma unroll
       for (int e = 0; e < 8; e++) pg[e] = 0.f;
       wave_block_store_nr<0>(st, ov, p, tok0 + q0 + w * 32, h * DH, n - (q0 + w * 32), pg, l);
-      nr_flush_dgamma(pg, sg, p.nr_dgamma_q, tx);
+      if (p.nr_gamma_q) nr_flush_dgamma(pg, sg, p.nr_dgamma_q, tx);
     } else
     wave_block_store(st, ov, p.dq + (tok0 + q0 + w * 32) * p.ld_dq + h * DH, p.ld_dq, n - (q0 + w * 32), l);
   }
@@ -1204,7 +1220,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(tfx_attn_args p) {
       for (int e = 0; e < 8; e++) pg[e] = 0.f;
       wave_block_store_nr<1>(st, kv, p, tok0 + k0 + w * 32, (p.h + h) * DH, rows, pg);
       wave_block_store(st, vv, p.dv + (tok0 + k0 + w * 32) * p.ld_dv + h * DH, p.ld_dv, rows);
-      nr_flush_dgamma(pg, sg, p.nr_dgamma_k);
+      if (p.nr_gamma_q) nr_flush_dgamma(pg, sg, p.nr_dgamma_k);
     } else {
       wave_block_store(st, kv, p.dk + (tok0 + k0 + w * 32) * p.ld_dk + h * DH, p.ld_dk, rows);
       wave_block_store(st, vv, p.dv + (tok0 + k0 + w * 32) * p.ld_dv + h * DH, p.ld_dv, rows);
@@ -1235,7 +1251,8 @@ int attn_bwd(const tfx_attn_args& p, hipStream_t s) {
   long long nthreads = (long long)p.b * p.n * p.h * 8;
   if (nthreads >= (1ll << 31)) return -4;
   if (p.nr_qkv) {                                               // fused QK-norm / RoPE backward: complete argument set, 16-byte rows
-    if (!p.nr_dqkv || !p.nr_gamma_q || !p.nr_gamma_k || !p.nr_rot_pos || !p.nr_cos || !p.nr_sin || !p.nr_dgamma_q || !p.nr_dgamma_k) return -5;
+    if (!p.nr_dqkv || !p.nr_gamma_q != !p.nr_gamma_k || !p.nr_rot_pos || !p.nr_cos || !p.nr_sin) return -5;
+    if (p.nr_gamma_q && (!p.nr_dgamma_q || !p.nr_dgamma_k)) return -5;      // (no gains = no RMS normalisation: the gain gradients are not touched and may be NULL)
     if (((p.nr_ld_qkv | p.nr_ld_dqkv) & 7) || (((uintptr_t)p.nr_qkv | (uintptr_t)p.nr_dqkv) & 15)) return -5;
   }
   tfx_attn_args q = p; q.order = 1;

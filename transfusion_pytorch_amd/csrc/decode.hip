@@ -252,6 +252,10 @@ __global__ __launch_bounds__(256) void decode_attn_rows_k(tfx_attn_args p) {
   __syncthreads();
   if (threadIdx.x < 8 * R && (int)(threadIdx.x >> 3) < p.n) {
     const int r = threadIdx.x >> 3, s2 = threadIdx.x & 7, t = t0 + r;
+    // (kernel argument: uniform) gate == NULL = no value gating: sigmoid(+inf) = 1 exactly.  The branch sits AHEAD of the reduction loop: behind it
+    // hipcc unrolled the loop into 288 LDS reads in flight (256 VGPRs + 48 AGPRs, one wave per SIMD instead of eight)
+    float gate = INFINITY;
+    if (p.gate) gate = bf2f(p.gate[(size_t)t * p.ld_gate + h]);
     float o[8], lt = 0.f;
 #pragma unroll
     for (int e = 0; e < 8; e++) o[e] = 0.f;
@@ -260,14 +264,14 @@ __global__ __launch_bounds__(256) void decode_attn_rows_k(tfx_attn_args p) {
       for (int e = 0; e < 8; e++) o[e] += red[r][gg][s2][e];
       lt += red[r][gg][s2][8];
     }
-    const float gate = bf2f(p.gate[(size_t)t * p.ld_gate + h]);
+    const float gs = __builtin_amdgcn_rcpf(1.f + __expf(-gate));
     bf16x8 ov;
     if (p.laser) {                                         // LASER (T:1019-1022): `v` is the side cache of v' = exp(softclamp(v)); og = g log(o / l)
-      const float gs = __builtin_amdgcn_rcpf(1.f + __expf(-gate)), rl = 1.f / lt;
+      const float rl = 1.f / lt;
 #pragma unroll
       for (int e = 0; e < 8; e++) ov[e] = f2bf(gs * __logf(o[e] * rl));
     } else {
-      const float sc = __builtin_amdgcn_rcpf(1.f + __expf(-gate)) / lt;
+      const float sc = gs / lt;
 #pragma unroll
       for (int e = 0; e < 8; e++) ov[e] = f2bf(o[e] * sc);
     }

@@ -546,9 +546,12 @@ TFX_DEV void staged_epilogue_qknr_(const GemmNT& p, f32x16 (&acc)[NI][2], int m_
       sn[k] = *(const f32x4*)(p.qk_sin + (size_t)pos[k] * 32 + ch * 4);
     }
   };
+  const bool normed = p.qk_gamma_q != nullptr;                     // (kernel argument: uniform) no gains = no RMS normalisation (tfx.h): qk_rope_chunk
   {
-    const float* gm = (which ? p.qk_gamma_k : p.qk_gamma_q) + ch * 8;
-    g0 = *(const f32x4*)gm; g1 = *(const f32x4*)(gm + 4);
+    if (normed) {
+      const float* gm = (which ? p.qk_gamma_k : p.qk_gamma_q) + ch * 8;
+      g0 = *(const f32x4*)gm; g1 = *(const f32x4*)(gm + 4);
+    }
     rs = (p.qk_norm_scale > 0.f ? p.qk_norm_scale : 8.f);
     load_pos(0, pos_a);
     load_cs(pos_a, cs_n, sn_n);                                    // step 0's rows
@@ -597,7 +600,8 @@ TFX_DEV void staged_epilogue_qknr_(const GemmNT& p, f32x16 (&acc)[NI][2], int m_
         float gm[8];
 #pragma unroll
         for (int e = 0; e < 4; e++) { gm[e] = g0[e]; gm[4 + e] = g1[e]; }
-        const bf16x8 o = qk_norm_rope_chunk(v[2 * qh + k], rs, which == 0 ? p.qk_q_scale : 1.f, gm, cs[k], sn[k]);
+        const float qs = which == 0 ? p.qk_q_scale : 1.f;
+        const bf16x8 o = normed ? qk_norm_rope_chunk(v[2 * qh + k], rs, qs, gm, cs[k], sn[k]) : qk_rope_chunk(v[2 * qh + k], qs, cs[k], sn[k]);
         const int m = row_of(s, k);
         if (!GUARD || m < p.M) *(bf16x8*)((bf16*)p.C2 + (size_t)m * p.ldc2 + n_w + ch * 8) = o;
         if constexpr (NI == 1) {
@@ -2403,7 +2407,7 @@ static bool qknr_fusable(const GemmNT& p) {
   return !p.rowmap && !p.a_rowmap && !p.bias && ((p.ldc | p.ldc2 | p.N) & 7) == 0 && (((uintptr_t)p.C | (uintptr_t)p.C2) & 15) == 0 && 2 * hd <= p.N && p.ldc2 >= 2 * hd;
 }
 static int gemm_nt_qknr(const GemmNT& p, hipStream_t s) {
-  if (p.qk_heads <= 0 || !p.C2 || !p.qk_gamma_q || !p.qk_gamma_k || !p.qk_rot_pos || !p.qk_cos || !p.qk_sin) return -5;
+  if (p.qk_heads <= 0 || !p.C2 || !p.qk_gamma_q != !p.qk_gamma_k || !p.qk_rot_pos || !p.qk_cos || !p.qk_sin) return -5;      // (both gains or neither: tfx.h)
   if (qknr_fusable(p)) {
     const NtPlan pl = nt_plan(p);
     if (pl.kind == NT_PP) { launch_pp<EPI_QKNR>(p, pl.grid, s); return (int)hipGetLastError(); }

@@ -123,9 +123,44 @@ TFX_DEV bf16x8 qk_norm_rope_chunk(const bf16x8 x, float ns, float qs, const floa
   return o;
 }
 
+// The same chunk WITHOUT the RMS normalisation (gamma_q == gamma_k == NULL in tfx.h; reference Attention(qk_rmsnorm=False), T:948-952):
+// q~ = rope(q) q_scale, k~ = rope(k) (qs = 1).  One spelling for the token-wise kernel and the fused GEMM epilogue, contraction off, explicit fma.
+TFX_DEV bf16x8 qk_rope_chunk(const bf16x8 x, float qs, const f32x4 cs, const f32x4 sn) {
+#pragma clang fp contract(off)
+  bf16x8 o;
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const float a = bf2f(x[2 * i]) * qs, b = bf2f(x[2 * i + 1]) * qs;
+    o[2 * i] = f2bf(__builtin_fmaf(a, cs[i], -(b * sn[i])));
+    o[2 * i + 1] = f2bf(__builtin_fmaf(b, cs[i], a * sn[i]));
+  }
+  return o;
+}
+// ... and its backward: dq = q_scale rope^T(dq~), dk = rope^T(dk~) (qs = 1) - one spelling for the token-wise kernel and the epilogues of the attention
+// backward (tfx_attn_args.nr_*), which therefore agree bit for bit.
+TFX_DEV bf16x8 qk_rope_bwd_chunk(const bf16x8 dy, float qs, const f32x4 cs, const f32x4 sn) {
+#pragma clang fp contract(off)
+  bf16x8 o;
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const float da = bf2f(dy[2 * i]), db = bf2f(dy[2 * i + 1]);
+    o[2 * i] = f2bf(__builtin_fmaf(db, sn[i], da * cs[i]) * qs);            // inverse rotation
+    o[2 * i + 1] = f2bf(__builtin_fmaf(-da, sn[i], db * cs[i]) * qs);
+  }
+  return o;
+}
+
 // The layer's soft-cap plan (tfx.h tfx_qk_norm_rope_args.sc_plan), written by ONE wave (all 64 lanes call; lane e holds gain e).
+// Without gains (no RMS normalisation) nothing bounds the scores: mode 2 with B = +inf - the polynomial modes are never chosen for unnormalised rows.
 TFX_DEV void softcap_plan_write(const float* gamma_q, const float* gamma_k, float norm_scale, float q_scale, float cap, float* o) {
   const int lane = threadIdx.x & 63;
+  if (!gamma_q || !gamma_k) {                                     // (kernel arguments: uniform)
+    if (lane == 0) {
+      const float L2E = 1.4426950408889634f, ic2 = 1.f / (cap * cap);
+      o[0] = 2.f; o[1] = L2E; o[2] = L2E * (-1.f / 3.f) * ic2; o[3] = 0.f; o[4] = 1.f; o[5] = -ic2; o[6] = 0.f; o[7] = INFINITY;
+    }
+    return;
+  }
   const float mq = wave_max(fabsf(1.f + gamma_q[lane])), mk = wave_max(fabsf(1.f + gamma_k[lane]));
   if (lane == 0) {
     const float ns = norm_scale > 0.f ? norm_scale : 8.f;

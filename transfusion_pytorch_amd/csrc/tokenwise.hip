@@ -1485,11 +1485,16 @@ __global__ __launch_bounds__(256) void qk_norm_rope_fwd_k(tfx_qk_norm_rope_args 
     if (cp >= 0) *(bf16x8*)(p.cache + (size_t)cp * p.ld_cache + (col - p.H * 64)) = x;
     return;
   }
-  const float* gm = (which == 0 ? p.gamma_q : p.gamma_k) + sub * 8;
   const int pos = p.rot_pos[t];
   const f32x4 cs = *(const f32x4*)(p.cos_tab + (size_t)pos * 32 + sub * 4);
   const f32x4 sn = *(const f32x4*)(p.sin_tab + (size_t)pos * 32 + sub * 4);
-  const bf16x8 o = qk_norm_rope_chunk(x, p.norm_scale > 0.f ? p.norm_scale : 8.f, which == 0 ? p.q_scale : 1.f, gm, cs, sn);
+  bf16x8 o;
+  if (p.gamma_q) {                             // (kernel argument: uniform)
+    const float* gm = (which == 0 ? p.gamma_q : p.gamma_k) + sub * 8;
+    o = qk_norm_rope_chunk(x, p.norm_scale > 0.f ? p.norm_scale : 8.f, which == 0 ? p.q_scale : 1.f, gm, cs, sn);
+  } else {                                     // no gains = no RMS normalisation (tfx.h): rotation and the q scale only
+    o = qk_rope_chunk(x, which == 0 ? p.q_scale : 1.f, cs, sn);
+  }
   *(bf16x8*)(p.qk + (size_t)t * p.ld_qk + col) = o;
   if (p.cache && which) {
     const int cp = p.cache_pos[t];
@@ -1512,8 +1517,15 @@ __global__ __launch_bounds__(1024) void qk_norm_rope_bwd_k(tfx_qk_norm_rope_args
     if (rem >= twoH) { rem -= twoH; t++; }
     const int which = rem >= p.H;
     const int col = rem * 64 + sub * 8;
-    bf16x8 x = *(const bf16x8*)(p.qkv + (size_t)t * p.ld_qkv + col);
     bf16x8 dy8 = *(const bf16x8*)(p.dqk + (size_t)t * p.ld_dqk + col);
+    if (!p.gamma_q) {                           // (kernel argument: uniform) no RMS normalisation (tfx.h): dq = q_scale rope^T(dq~), dk = rope^T(dk~); no gain gradients
+      const int pos = p.rot_pos[t];
+      const f32x4 cs = *(const f32x4*)(p.cos_tab + (size_t)pos * 32 + sub * 4);
+      const f32x4 sn = *(const f32x4*)(p.sin_tab + (size_t)pos * 32 + sub * 4);
+      *(bf16x8*)(p.dqkv + (size_t)t * p.ld_dqkv + col) = qk_rope_bwd_chunk(dy8, which == 0 ? p.q_scale : 1.f, cs, sn);
+      continue;
+    }
+    bf16x8 x = *(const bf16x8*)(p.qkv + (size_t)t * p.ld_qkv + col);
     float v[8], q = 0.f;
 #pragma unroll
     for (int e = 0; e < 8; e++) { v[e] = bf2f(x[e]); q += v[e] * v[e]; }
@@ -1544,6 +1556,7 @@ __global__ __launch_bounds__(1024) void qk_norm_rope_bwd_k(tfx_qk_norm_rope_args
     for (int e = 0; e < 8; e++) o[e] = f2bf(dyn[e] * inv - v[e] * k);
     *(bf16x8*)(p.dqkv + (size_t)t * p.ld_dqkv + col) = o;
   }
+  if (!p.gamma_q) return;                       // (uniform) no gains, no gain gradients: dgamma_* are not touched and may be NULL
   // the 8 lanes of a wave that own the same 8 columns (lane & 7) are summed with three cross-lane exchanges, the four waves through plain LDS
   // stores: 16 LDS float atomics per thread with 8 lanes on every address were a ~10 us tail on a 100 us launch (ds_add_f32 with conflicts
   // runs at hundreds of clocks per instruction - measured for the AttentionResidual backward earlier this round)
@@ -2428,11 +2441,13 @@ int tfx_embed_fwd(const tfx_embed_args* a, void* s) { DISPATCH_NC(a->d, hipLaunc
 int tfx_embed_bwd(const tfx_embed_args* a, void* s) { DISPATCH_NC(a->d, hipLaunchKernelGGL(embed_bwd_k<NC>, dim3(grid_tokens(a->T)), dim3(256), 0, ST(s), *a)); RET(); }
 
 int tfx_qk_norm_rope_fwd(const tfx_qk_norm_rope_args* a, void* s) {
+  if (!a->gamma_q != !a->gamma_k) return -4;               // both gains, or neither (no RMS normalisation, tfx.h)
   long long nthreads = (long long)a->T * (a->cache ? 3 : 2) * a->H * 8;
   if (nthreads >= (1ll << 31)) return -3;
   hipLaunchKernelGGL(qk_norm_rope_fwd_k, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, ST(s), *a); RET();
 }
 int tfx_qk_norm_rope_bwd(const tfx_qk_norm_rope_args* a, void* s) {
+  if (!a->gamma_q != !a->gamma_k) return -4;
   long long nthreads = (long long)a->T * 2 * a->H * 8;
   if (nthreads >= (1ll << 31)) return -3;
   // 1024-thread blocks, at most one per CU: every block ends in 128 global atomics onto the SAME 128 gamma-gradient addresses, and same-address
@@ -2589,6 +2604,6 @@ int tfx_laser_v_bwd(const tfx_laser_v_args* a, void* s) {
   if (nch >= (1ll << 31)) return -4;
   hipLaunchKernelGGL(laser_v_bwd_k, dim3((unsigned)((nch + 255) / 256)), dim3(256), 0, ST(s), *a, (unsigned)nch); RET();
 }
-const char* tfx_version(void) { return "tfx-hip gfx950 r5-laser-muon-selfflow-adamgroups-oderk-tntable-atan2"; }
+const char* tfx_version(void) { return "tfx-hip gfx950 r5-laser-muon-selfflow-adamgroups-oderk-tntable-atan2-ablate"; }
 
 }  // extern "C"

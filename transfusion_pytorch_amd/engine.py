@@ -285,7 +285,8 @@ class Plan:
         self.cos_tab = self.sin_tab = None
         # per layer: the soft-cap plan tfx_qk_norm_rope_fwd derives from the layer's QK-RMSNorm gains (tfx.h) and its attention kernels - forward
         # and, later, backward - read: polynomial degree and coefficients from the BOUND on the scores, no look at the data.  TFX_SC_PLAN=0: decide from the scores
-        self.sc_plan = z(D, 8, dtype=torch.float32)
+        # Without QK-RMSNorm (md.qk_norm False) nothing bounds the scores: no plan, the attention kernels take their data-dependent form
+        self.sc_plan = z(D, 8, dtype=torch.float32) if md.qk_norm else None
         # LASER attention (md.laser = its softclamp value; T:979-983): the attention reads v' = exp(c tanh(v / c)), written by tfx_laser_v_fwd behind the
         # projection.  Training plans keep v' per layer ([T, heads 64] bf16: 64 MiB per layer at 65 536 tokens x 512), so the backward reads the forward's
         # v' instead of recomputing it; inference plans without a cache share one buffer across layers (`li`).  Decode plans keep a side cache of v' beside
@@ -529,7 +530,7 @@ class Plan:
             else:
                 L.append(('tfx_adaln_pre_fwd', a_pre_attn))
                 self._hbm(L, 2, 8 * T)                                  # x in, u out, mean / rstd out
-            gam = (lambda nm: S[f'g{nm}{i}']) if md.dim_head != 64 else (lambda nm: pp(f'{p}.1.fn.{nm}_norm.gamma'))
+            gam = self._gains(i)
             plan_kw = dict(sc_plan=self.sc_plan[i], softcap=50.0) if self.sc_plan is not None else {}
             # decode plans (round 4): the same epilogue in the decode-step GEMM kernel, with the KV-cache append (`qk_cache`): one launch per layer
             # less in a step that is nothing but ~225 dependent launches.  Training plans keep the token-wise launch: fused there the projection grows from 150 to
@@ -662,6 +663,16 @@ class Plan:
             a.prefetch = nxt.B
             a.prefetch_bytes = int(nxt.N) * int(nxt.ldb) * 2
 
+    def _gains(self, i):
+        """layer i's QK-RMSNorm gains as the kernels take them (name 'q' / 'k' -> tensor or address); NULL without QK-RMSNorm (md.qk_norm False,
+        Transformer(qk_rmsnorm=False)): tfx.h reads two NULL gains as "no RMS normalisation" - rotation and the q scale only"""
+        md, S, p = self.md, self.ps.shadows, f'transformer.layers.{i}'
+        if not md.qk_norm:
+            return lambda nm: 0
+        if md.dim_head != 64:
+            return lambda nm: S[f'g{nm}{i}']
+        return lambda nm: self.ps.ptr(f'{p}.1.fn.{nm}_norm.gamma')
+
     def _qknr_separate(self, L, i, li, lkv, gam, plan_kw):
         """QK-RMSNorm + RoPE as its own token-wise launch behind the plain projection, then the attention launch (decode plans; TFX_QKNR=0)"""
         md, T, H, hd, ldq = self.md, self.T, self.md.heads, self.md.hdk, self.md.ldq
@@ -726,10 +737,11 @@ class Plan:
             a[2] = None if mode == 'model' else self.noise_args[t].eps
 
     def _attn_kw(self, i, bwd=False):
+        # without value gating (md.gates False) the [q | k | v] rows carry no gate columns (md.ldq = 3 heads 64): gate = dgate = NULL (tfx.h tfx_attn_args)
         md, hd, ldq = self.md, self.md.hdk, self.md.ldq
         li, lkv = self._li(i), self._lkv(i)
         kw = dict(q=self.qkr[lkv], k=_p(self.qkr, lkv) + 2 * hd, v=_p(self.qkvg, lkv) + 2 * 2 * hd, ld_q=2 * hd, ld_k=2 * hd, ld_v=ldq,
-                  gate=_p(self.qkvg, lkv) + 2 * 3 * hd, ld_gate=ldq, kv_end=self.kv_end, q_start=self.q_start, out=self.og[li], ld_out=hd,
+                  gate=_p(self.qkvg, lkv) + 2 * 3 * hd if md.gates else 0, ld_gate=ldq, kv_end=self.kv_end, q_start=self.q_start, out=self.og[li], ld_out=hd,
                   lse=self.lse[li], b=self.units[0] if self.units else self.b, h=md.heads, n=self.units[1] if self.units else self.n, softcap=50.0)
         if self.units:
             kw.update(q_row0=self.unit_row0, q_cnt=self.unit_cnt)
@@ -743,7 +755,7 @@ class Plan:
         if bwd:
             dqkvg = self.dqkvg_p[self._bwd_slot(i)]
             kw.update(dout=self.dog, ld_dout=hd, do_eff=self.do_eff, ld_do=hd, delta=self.delta,
-                      dgate=dqkvg.data_ptr() + 2 * 3 * hd, ld_dgate=ldq, dq=self.dqk if self.dqk is not None else 0,
+                      dgate=dqkvg.data_ptr() + 2 * 3 * hd if md.gates else 0, ld_dgate=ldq, dq=self.dqk if self.dqk is not None else 0,
                       dk=self.dqk.data_ptr() + 2 * hd if self.dqk is not None else 0,
                       dv=dqkvg.data_ptr() + 2 * 2 * hd, ld_dq=2 * hd, ld_dk=2 * hd, ld_dv=ldq)
         return kw
@@ -978,13 +990,15 @@ class Plan:
             self._raw(L, lib.tfx_adaln_pre_post_bwd, ctypes.addressof(a_pref), ctypes.addressof(a_posta))
             self._hbm(L, 6)                                             # du, x in, residual gradient in / out, y in, dy out
             self._nt(L, algo_n=md.hd, A=dy_a, lda=d, B=S[f'out_t{i}'], ldb=d, M=T, N=hd, K=d, epi=E['TFX_EPI_BF16'], C=self.dog, ldc=hd)
-            gam = (lambda nm: S[f'g{nm}{i}']) if md.dim_head != 64 else (lambda nm: pp(f'{p}.1.fn.{nm}_norm.gamma'))
+            gam = self._gains(i)
+            # (without QK-RMSNorm the gain gradients are never written: the unread q_norm / k_norm gammas keep a zero gradient)
+            dgam = lambda pre: {f'{pre}dgamma_{nm}': gp(f'{p}.1.fn.{nm}_norm.gamma') if md.qk_norm else 0 for nm in 'qk'}
             if os.environ.get('TFX_ATTN_QKNR', '1') != '0':
                 # round 5: the backward of QK-RMSNorm + RoPE rides in the epilogues of the dQ and dK/dV kernels (tfx.h tfx_attn_args.nr_*): d q~ | d k~ are never
                 # written out and read back, and the token-wise launch below drops out of the layer
                 self._k(L, 'tfx_attn_bwd', 'tfx_attn_args', **self._attn_kw(i, bwd=True), nr_qkv=self.qkvg[i], nr_ld_qkv=ldq, nr_dqkv=dqkvg, nr_ld_dqkv=ldq,
                         nr_gamma_q=gam('q'), nr_gamma_k=gam('k'), nr_rot_pos=self.rot_pos, nr_cos=0, nr_sin=0, nr_q_scale=md.dim_head ** -0.5,
-                        nr_norm_scale=md.dim_head ** 0.5, nr_dgamma_q=gp(f'{p}.1.fn.q_norm.gamma'), nr_dgamma_k=gp(f'{p}.1.fn.k_norm.gamma'))
+                        nr_norm_scale=md.dim_head ** 0.5, **dgam('nr_'))
                 # (per-block partial rows + a reduction launch instead of the 64 same-address atomics per block measured SLOWER in round 5 - 4.19 vs 4.05 ms -
                 # and were removed in round 6)
                 self._rope_attn_args = getattr(self, '_rope_attn_args', []) + [L[-1][1]]
@@ -992,7 +1006,7 @@ class Plan:
                 self._k(L, 'tfx_attn_bwd', 'tfx_attn_args', **self._attn_kw(i, bwd=True))
                 self._k(L, 'tfx_qk_norm_rope_bwd', 'tfx_qk_norm_rope_args', T=T, H=H, qkv=self.qkvg[i], ld_qkv=ldq, gamma_q=gam('q'),
                         gamma_k=gam('k'), rot_pos=self.rot_pos, cos_tab=0, sin_tab=0, q_scale=md.dim_head ** -0.5, norm_scale=md.dim_head ** 0.5,
-                        dqk=self.dqk, ld_dqk=2 * hd, dqkv=dqkvg, ld_dqkv=ldq, dgamma_q=gp(f'{p}.1.fn.q_norm.gamma'), dgamma_k=gp(f'{p}.1.fn.k_norm.gamma'))
+                        dqk=self.dqk, ld_dqk=2 * hd, dqkv=dqkvg, ld_dqkv=ldq, **dgam(''))
                 self._rope_args = getattr(self, '_rope_args', []) + [L[-1][1]]
                 L.meta = L.meta or {}
                 L.meta[len(L) - 1] = ('hbm', 3 * 2 * T * hd * 2)                # q, k (raw) in; d q~, d k~ in; d q, d k out

@@ -39,6 +39,10 @@ class ModelDims:
     pos_types: tuple = ()                 # modality types whose tokens get an additive axial positional embedding (T:1384-1403): rows computed by the host MLP
     ext_types: tuple = ()                 # modality types whose latent <-> model maps are user modules (`pre_post_transformer_enc_dec`, T:1451-1494):
                                           # their token rows come in from / their embedding rows go out to PyTorch; no projection parameters here
+    gates: bool = True                    # per-head sigmoid gate on the attention output (T:901-904, T:1026-1027); False = Transformer(attn_kwargs=dict(gate_values=False)):
+                                          # no `to_gates` parameter, no gate rows in the fused projection, the kernels get gate = NULL (tfx.h tfx_attn_args)
+    qk_norm: bool = True                  # QK-RMSNorm in the attention (T:948-952); False = Transformer(qk_rmsnorm=False): q~ = rope(q) q_scale, k~ = rope(k).  The
+                                          # q_norm / k_norm gammas stay parameters, as in the reference - never read, their gradient stays zero
     laser: float = 0.                     # LASER attention (Transformer(attn_laser=True), T:979-983, T:1019-1022): the softclamp value c of v' = exp(c tanh(v / c)); 0 = off
 
     @property
@@ -54,11 +58,13 @@ class ModelDims:
     @property
     def vp(self): return pad_to(self.vocab, 64)
     @property
-    def nq(self): return 3 * self.hd + self.heads            # q | k | v | gate logits (rows of the fused projection, T:877-916)
+    def ng(self): return self.heads if self.gates else 0      # gate logits per token
+    @property
+    def nq(self): return 3 * self.hd + self.ng               # q | k | v | gate logits (rows of the fused projection, T:877-916)
     @property
     def hdk(self): return self.heads * 64                     # KERNEL layout: 64 columns per head; dim_head < 64 leaves zero columns
     @property
-    def nqk(self): return 3 * self.hdk + self.heads           # q | k | v | gate logits in the kernel layout
+    def nqk(self): return 3 * self.hdk + self.ng              # q | k | v | gate logits in the kernel layout
     @property
     def ldq(self): return pad_to(self.nqk, 64)
     @property
@@ -71,7 +77,7 @@ class ModelDims:
 
 def param_specs(md: ModelDims):
     """ordered (name, shape) list in FLAT-BUFFER order.  Groups that one GEMM treats as a single matrix are
-    laid out contiguously: all AdaLN conditioning weights ([depth*2*3d, 4d]) and, per layer, to_qk|to_v|to_gates."""
+    laid out contiguously: all AdaLN conditioning weights ([depth*2*3d, 4d]) and, per layer, to_qk|to_v|to_gates (to_qk|to_v without value gating)."""
     d, hd, h, di, D = md.dim, md.hd, md.heads, md.di, md.depth
     specs = []
     for i in range(D):
@@ -87,7 +93,9 @@ def param_specs(md: ModelDims):
         p = f'transformer.layers.{i}'
         if md.has_skip(i):
             specs.append((f'{p}.0.weight', (d, 2 * d)))
-        specs += [(f'{p}.1.fn.to_qk.0.weight', (2 * hd, d)), (f'{p}.1.fn.to_v.0.weight', (hd, d)), (f'{p}.1.fn.to_gates.0.weight', (h, d))]
+        specs += [(f'{p}.1.fn.to_qk.0.weight', (2 * hd, d)), (f'{p}.1.fn.to_v.0.weight', (hd, d))]
+        if md.gates:                                                                # (the reference has no `to_gates` module without value gating, T:901-904)
+            specs.append((f'{p}.1.fn.to_gates.0.weight', (h, d)))
         specs += [(f'{p}.1.fn.to_out.1.weight', (d, hd)),
                   (f'{p}.1.fn.q_norm.gamma', (md.dim_head,)), (f'{p}.1.fn.k_norm.gamma', (md.dim_head,)),
                   (f'{p}.1.layernorm_gamma', (d,)), (f'{p}.1.layerscale', (d,)),
@@ -167,13 +175,13 @@ def geglu_phys_to_ref_rows(di: int, dip: int) -> np.ndarray:
     return np.where(feat < di, ref, -1).astype(np.int32)
 
 
-def head_phys_to_ref_rows(heads: int, dim_head: int) -> np.ndarray:
+def head_phys_to_ref_rows(heads: int, dim_head: int, gates: bool = True) -> np.ndarray:
     """row of the fused [q | k | v | gates] projection (3 * heads * dim_head + heads rows) for each row of the kernel layout
-    (64 columns per head, 3 * heads * 64 + heads rows); -1 = zero padding."""
+    (64 columns per head, 3 * heads * 64 + heads rows); -1 = zero padding.  Without value gating both lose their trailing `heads` rows."""
     c = np.arange(3 * heads * 64)
     part, h, e = c // (heads * 64), (c // 64) % heads, c % 64
     ref = np.where(e < dim_head, part * heads * dim_head + h * dim_head + e, -1)
-    return np.concatenate([ref, 3 * heads * dim_head + np.arange(heads)]).astype(np.int32)
+    return np.concatenate([ref, 3 * heads * dim_head + np.arange(heads if gates else 0)]).astype(np.int32)
 
 
 class ParamStore:
@@ -364,7 +372,7 @@ class ParamStore:
         gmap = self._map('geglu', geglu_phys_to_ref_rows(di, dip))
         dh = md.dim_head
         if dh != 64:
-            qmap = self._map('heads', head_phys_to_ref_rows(md.heads, dh))
+            qmap = self._map('heads', head_phys_to_ref_rows(md.heads, dh, md.gates))
             gam_map = self._map('gamma', np.where(np.arange(64) < dh, np.arange(64), -1))
         for i in range(D):
             p = f'transformer.layers.{i}'

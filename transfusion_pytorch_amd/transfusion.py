@@ -179,17 +179,23 @@ class Transformer:
     def __init__(self, dim, *, depth, dim_head=64, heads=8, dropout=0., ff_expansion_factor=4, attn_kwargs: dict = dict(),
                  ff_kwargs: dict = dict(), attn_laser=False, unet_skips=True, use_flex_attn=False, qk_rmsnorm=True, use_value_residual=False):
         # use_flex_attn only selects the reference's attention BACKEND (same scores, same mask, T:998-1027): accepted, the native kernel runs
-        # attn_laser (T:979-983, T:1019-1022) runs natively; of the attention's keyword arguments only its softclamp value (T:866) is taken
+        # qk_rmsnorm=False (T:948-952: attention without QK-RMSNorm) runs natively: the kernels take NULL gains (include/tfx.h)
+        # attn_laser (T:979-983, T:1019-1022) runs natively; of the attention's keyword arguments its softclamp value (T:866) and `gate_values` (T:864,
+        # T:901-904, T:1026-1027: False = no sigmoid gate on the attention output, no `to_gates` parameter) are taken
         attn_kwargs = dict(attn_kwargs)
         laser_c = attn_kwargs.pop('laser_softclamp_value', 15.)
+        gate_values = attn_kwargs.pop('gate_values', True)
         unsupported = dict(dropout=dropout != 0., attn_kwargs=bool(attn_kwargs), ff_kwargs=bool(ff_kwargs),
-                           unet_skips=not unet_skips, qk_rmsnorm=not qk_rmsnorm, use_value_residual=use_value_residual)
+                           unet_skips=not unet_skips, use_value_residual=use_value_residual)
         bad = [k for k, v in unsupported.items() if v]
         if bad:
             raise NotImplementedError(f'Transformer options not supported by the native MI355X path: {bad}')
         if not (isinstance(laser_c, (int, float)) and laser_c > 0):
             raise ValueError(f'laser_softclamp_value must be a positive number, got {laser_c!r}')
-        self.attn_laser, self.laser_softclamp_value = bool(attn_laser), float(laser_c)
+        if not isinstance(gate_values, bool):
+            raise ValueError(f'gate_values must be a bool, got {gate_values!r}')
+        self.attn_laser, self.laser_softclamp_value, self.gate_values = bool(attn_laser), float(laser_c), gate_values
+        self.qk_rmsnorm = bool(qk_rmsnorm)
         if dim_head > 64 or dim_head % 2 or dim_head < 2:
             raise NotImplementedError('the native attention kernels hold 64 columns per head: dim_head must be even and <= 64 '
                                       '(smaller heads run zero-padded)')
@@ -353,7 +359,7 @@ class Transfusion(nn.Module):
 
         self.md = ModelDims(num_text_tokens=num_text_tokens, dim=dim, depth=transformer.depth, heads=transformer.heads,
                             dim_head=transformer.dim_head, dim_latents=tuple(self.dim_latents), ff_expansion_factor=transformer.ff_expansion_factor, model_output_clean=bool(model_output_clean), clean_eps=float(eps),
-                            laser=transformer.laser_softclamp_value if transformer.attn_laser else 0.,
+                            laser=transformer.laser_softclamp_value if transformer.attn_laser else 0., gates=transformer.gate_values, qk_norm=transformer.qk_rmsnorm,
                             pos_types=tuple(t for t, f in enumerate(self.add_pos_emb) if f), ext_types=tuple(sorted(ext_modules)))
         self.store = ParamStore(self.md, self)
         if ext_modules:       # the reference's attribute names: latent_to_model_projs[t] / model_to_latent_projs[t] ARE the user's modules (T:1493-1494)
@@ -424,7 +430,7 @@ class Transfusion(nn.Module):
     def muon_parameters(self):                                        # T:1657-1672
         """the matrices the reference hands to Muon (train_image_only.py:90), in its order: per layer the attention's `to_v` and `to_out` weights
         and the feed-forward's two weights.  They are views into the flat parameter buffer (`to_v` is the middle slice of the fused
-        to_qk | to_v | to_gates block) - the very objects `named_parameters()` yields, so `optim.FusedMuon` and `torch.optim.Muon` both take them.
+        to_qk | to_v | to_gates block, whether or not the model has value gates) - the very objects `named_parameters()` yields, so `optim.FusedMuon` and `torch.optim.Muon` both take them.
         The reference walks `self.modules()` and so also collects `Attention` / `FeedForward` instances inside user encoder / decoder modules;
         native user modules are plain PyTorch modules that cannot contain those classes, so nothing of theirs is ever in this list."""
         prm = self.store.params
