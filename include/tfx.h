@@ -519,7 +519,7 @@ int tfx_ode_rk_update(float* y, float* k, const float* ctl, int32_t B, int32_t L
 /* dst[r][c] (bf16, ld_dst, Rd rows, Cd cols) = src[rowmap ? rowmap[r] : r][c] or 0 when out of range / map < 0 */
 typedef struct { const float* src; int32_t ld_src, Rs, Cs; const int32_t* rowmap; tfx_bf16* dst; int32_t ld_dst, Rd, Cd; } tfx_cast_args;
 int tfx_cast_rows(const tfx_cast_args* a, void* stream);
-/* dst[c][r] = src[rowmap ? rowmap[r] : r][c]  (transposed shadow for the dX GEMMs) */
+/* dst[c][r] = src[rowmap ? rowmap[r] : r][c]  (transposed shadow for the dX GEMMs).  Both return 0 without a launch when Rd == 0 or ld_dst == 0. */
 int tfx_cast_rows_t(const tfx_cast_args* a, void* stream);
 /* all shadows in one launch: `jobs_dev` is a DEVICE array of n_jobs jobs sorted by first_block; job j owns blocks
  * [first_block, first_block + nb) with nb = ceil(Rd*ld_dst/2048) (plain) or ceil(ld_dst/64)*ceil(Rd/64) (transposed);
@@ -538,7 +538,12 @@ int tfx_f32_to_bf16(const float* src, tfx_bf16* dst, int64_t n, void* stream);
 int tfx_cast_block_bf16(const float* src, int32_t ld_src, tfx_bf16* dst, int32_t ld_dst, int32_t R, int32_t C, void* stream);
 /* dst(bf16) = a(bf16) * silu'(pre(bf16))  (time-MLP backward) */
 int tfx_silu_bwd(const tfx_bf16* dy, const tfx_bf16* pre, tfx_bf16* dx, int64_t n, void* stream);
-/* column sums: out[c] += sum_r src[r][c]  (bias gradients); src bf16 or fp32 */
+/* column sums: out[c] += sum_r src[r][c]  (bias gradients); src bf16 or fp32.  tfx_colsum_bf16 takes two optional maps:
+ *   rowmap [R]: row r of the sum is src[rowmap[r]]; an entry below 0 names no row and adds nothing (as in tfx_cast_rows, tfx_scatter_rows_bf16 and
+ *               tfx_gather_f32); rows may repeat, and then count as often
+ *   colmap [C]: column c is added to out[colmap[c]]; an entry below 0 drops the column; several columns may share one output, which receives their sum
+ * A column whose sum is exactly zero does not touch `out`.  C % 8 == 0 && ld % 8 == 0 takes the 16-byte-load kernel (src 16-byte aligned), anything else the
+ * scalar one.  R == 0 or C == 0 returns 0 and writes nothing. */
 int tfx_colsum_bf16(const tfx_bf16* src, int32_t ld, int32_t R, int32_t C, const int32_t* colmap, const int32_t* rowmap, float* out, void* stream);
 int tfx_colsum_f32(const float* src, int32_t ld, int32_t R, int32_t C, float* out, void* stream);
 int tfx_add_bf16(const tfx_bf16* a, const tfx_bf16* b, tfx_bf16* out, int64_t n, void* stream);
@@ -550,7 +555,8 @@ int tfx_scale_bf16_dev(tfx_bf16* x, int64_t n, const float* scale, void* stream)
 int tfx_scale_bf16_copy(const tfx_bf16* src, tfx_bf16* dst, int64_t n, float scale, void* stream);
 
 /* fused global-norm clip + Adam over flat fp32 buffers   train_toy.py:55-57
- * sumsq[0] must hold the sum of squared gradients (tfx_sumsq accumulates into it; zero it first). */
+ * sumsq[0] must hold the sum of squared gradients (tfx_sumsq accumulates into it; zero it first).  g must be 16-byte aligned (16-byte loads): tfx_sumsq
+ * returns -1 otherwise, as tfx_sumsq_det and tfx_ema_update do; n == 0 returns 0 and writes nothing. */
 int tfx_sumsq(const float* g, int64_t n, float* sumsq, void* stream);
 typedef struct {
   float* p; const float* g; float* m; float* v; int64_t n;
@@ -631,7 +637,8 @@ int tfx_adam_atan2_step(const tfx_adam_atan2_args* a, void* stream);
  * iteration.  The "straight" copy has the parameter's own orientation (X when rows <= cols, else X^T), the "transposed" copy the other one. */
 enum { TFX_SUMSQ_DET_PARTIALS = 1024 };
 /* sumsq[0] = sum of g[i]^2 (overwritten, not accumulated) in a fixed order; partials: TFX_SUMSQ_DET_PARTIALS floats of scratch.  The clip norm of the Muon step
- * (clip_grad_norm_, train_toy.py:55): tfx_sumsq's atomic sum changes in the last bits from run to run */
+ * (clip_grad_norm_, train_toy.py:55): tfx_sumsq's atomic sum changes in the last bits from run to run.  n == 0 stores 0; g not 16-byte aligned returns -1.
+ * tfx_muon_prep / _apply with nblk == 0 and tfx_muon_norm with nmat == 0 return 0 and write nothing. */
 int tfx_sumsq_det(const float* g, int64_t n, float* partials, float* sumsq, void* stream);
 /* host only: what a rows x cols parameter becomes - flip (rows > cols), m <= n, their padded sizes, output tiles of its gram / poly product (m_pad x m_pad)
  * and of its update product (n_pad x m_pad), 64 x 64 blocks of tfx_muon_prep / _apply.  Any output pointer may be NULL. */
@@ -647,7 +654,8 @@ typedef struct {
   float lr_ratio;              /* _adjust_lr's ratio for this shape (_muon.py:65-77) */
 } tfx_muon_mat;
 /* momentum, Nesterov mix, bf16 X0 in both orientations, per-block sums of squares (_muon.py:280-282): block b works on matrix blk_mat[b].
- * g is scaled by grad_scale x the clip coefficient of tfx_adam_step (sumsq, max_norm) before it enters the momentum.  X0 is stored UNNORMALISED; tfx_muon_norm
+ * g is scaled by grad_scale x the clip coefficient of tfx_adam_step (sumsq, max_norm) before it enters the momentum - the
+ * product is rounded to fp32 on its own, as clip_grad_norm_ leaves it, so that `buf` stays within 2 ulp of torch.lerp on the same operands.  X0 is stored UNNORMALISED; tfx_muon_norm
  * turns the partials into 1 / max(|u|, eps) and its square per matrix, which the first gram product and the first update carry (scale_acc / scale_z).
  * Supported magnitudes: the first gram product sums u_i u_j in fp32 BEFORE 1 / |u|^2 is applied, so the products square the range: elements of u
  * below about 1e-19 in magnitude underflow there (contribute zero) and elements above about 1e19 overflow, where torch - which divides first - is

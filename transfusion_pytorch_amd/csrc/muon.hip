@@ -173,7 +173,13 @@ __global__ __launch_bounds__(256) void muon_prep_kernel(tfx_muon_prep_args a) {
     float u = 0.f;
     if (r < mt.rows && c < mt.cols) {
       const size_t idx = (size_t)mt.off + (size_t)r * mt.cols + c;
-      const float g = a.g[idx] * coef;
+      // rounded to fp32 BEFORE the mix, as clip_grad_norm_ leaves it for torch.lerp: contracted into the `g - b` below, the unrounded product moves a
+      // cancelling lerp by thousands of ulp of its result (tests/test_param_kernels_gpu.py)
+      float g;
+      {
+#pragma clang fp contract(off)
+        g = a.g[idx] * coef;
+      }
       float b = a.buf[idx];
       // torch.lerp(start, end, w): w < 0.5 ? start + w (end - start) : end - (end - start) (1 - w)
       b = w1 < 0.5f ? b + w1 * (g - b) : g - (g - b) * (1.f - w1);

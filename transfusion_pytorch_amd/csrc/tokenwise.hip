@@ -1954,7 +1954,10 @@ template <typename T> __global__ __launch_bounds__(256) void colsum_k(const T* s
   const int c = blockIdx.x * 64 + cx;
   const int rbeg = blockIdx.y * rows_per_block, rend = min(R, rbeg + rows_per_block);
   float a = 0.f;
-  if (c < C) for (int r = rbeg + ry; r < rend; r += 4) a += (float)src[(size_t)(rowmap ? rowmap[r] : r) * ld + c];
+  if (c < C) for (int r = rbeg + ry; r < rend; r += 4) {
+    const int rs = rowmap ? rowmap[r] : r;               // a map entry below 0 names no row: it adds nothing (tfx.h)
+    if (rs >= 0) a += (float)src[(size_t)rs * ld + c];
+  }
   s[ry][cx] = a;
   __syncthreads();
   if (ry == 0 && c < C) {
@@ -1979,14 +1982,21 @@ __global__ __launch_bounds__(512) void colsum8_k(const bf16* src, int ld, int R,
     for (; r + 56 < rend; r += 64) {
       bf16x8 v[8];
 #pragma unroll
-      for (int u = 0; u < 8; u++) v[u] = *(const bf16x8*)(src + (size_t)(rowmap ? rowmap[r + 8 * u] : r + 8 * u) * ld + c0);
+      for (int u = 0; u < 8; u++) {
+        const int rs = rowmap ? rowmap[r + 8 * u] : r + 8 * u;       // a map entry below 0 names no row: it adds nothing (tfx.h)
+#pragma unroll
+        for (int e = 0; e < 8; e++) v[u][e] = f2bf(0.f);
+        if (rs >= 0) v[u] = *(const bf16x8*)(src + (size_t)rs * ld + c0);
+      }
 #pragma unroll
       for (int u = 0; u < 8; u++)
 #pragma unroll
         for (int e = 0; e < 8; e++) a[e] += bf2f(v[u][e]);
     }
     for (; r < rend; r += 8) {
-      bf16x8 v = *(const bf16x8*)(src + (size_t)(rowmap ? rowmap[r] : r) * ld + c0);
+      const int rs = rowmap ? rowmap[r] : r;
+      if (rs < 0) continue;
+      bf16x8 v = *(const bf16x8*)(src + (size_t)rs * ld + c0);
 #pragma unroll
       for (int e = 0; e < 8; e++) a[e] += bf2f(v[e]);
     }
@@ -2483,6 +2493,7 @@ int tfx_cast_rows(const tfx_cast_args* a, void* s) {
   hipLaunchKernelGGL(cast_rows_k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ST(s), *a); RET();
 }
 int tfx_cast_rows_t(const tfx_cast_args* a, void* s) {
+  if ((long long)a->Rd * a->ld_dst == 0) return 0;
   hipLaunchKernelGGL(cast_rows_t_k, dim3((a->ld_dst + 31) / 32, (a->Rd + 31) / 32), dim3(256), 0, ST(s), *a); RET();
 }
 int tfx_cast_batch(const tfx_cast_job* jobs_dev, int32_t n_jobs, int32_t n_blocks, void* s) {
@@ -2535,6 +2546,7 @@ int tfx_colsum_f32(const float* src, int32_t ld, int32_t R, int32_t C, float* ou
 }
 int tfx_sumsq(const float* g, int64_t n, float* out, void* s) {
   if (n == 0) return 0;
+  if (((uintptr_t)g) & 15) return -1;                      // the kernel issues 16-byte loads
   long long blocks = (n / 4 + 255) / 256; if (blocks > 2048) blocks = 2048; if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL(sumsq_k, dim3((unsigned)blocks), dim3(256), 0, ST(s), g, (long long)n, out); RET();
 }
