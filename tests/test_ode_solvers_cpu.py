@@ -66,7 +66,7 @@ def test_schedule_shape_times_and_weights(method, S):
 @pytest.mark.parametrize('S', [2, 3, 4, 8, 16, 31])
 def test_midpoint_schedule_is_the_list_the_midpoint_loops_build(S):
     ts = torch.linspace(0, 1, S)
-    evals = []                                               # as Sampler._loop_continuous builds it for the midpoint kernels
+    evals = []                                               # the list the midpoint kernels were written against; ode.ode_control / sampling._ode_solve read it off the schedule
     for k in range(S - 1):
         t0, dt = float(ts[k]), float(ts[k + 1] - ts[k])
         evals += [(t0, dt * 0.5, 1), (t0 + dt * 0.5, dt, 2)]

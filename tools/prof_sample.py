@@ -1,6 +1,6 @@
 """one `sample_many` run of SURVEY 8(d) config 5 (forced modality at the start) for a rocprofv3 kernel trace of the decode loop.
     (cd /tmp && rocprofv3 --kernel-trace --output-format csv -d /tmp/ps -o p -- python $R/tools/prof_sample.py [max_length])
-    python tools/prof_summary.py /tmp/ps/p_kernel_trace.csv --steps <global steps printed by TFX_SAMPLE_TIMING=1>"""
+    python tools/prof_summary.py /tmp/ps/p_kernel_trace.csv --steps <global steps of the run>"""
 import os
 import sys
 import time

@@ -12,9 +12,11 @@ SURVEY Appendix D).  The grid is `t = linspace(0, 1, modality_steps)` itself; on
 """
 from __future__ import annotations
 
+import functools
 from collections import namedtuple
 from fractions import Fraction as Fr
 
+import numpy as np
 import torch
 
 MAX_STAGES = 4                                               # == TFX_ODE_MAX_STAGES (include/tfx.h)
@@ -63,6 +65,11 @@ def _f32(x) -> float:
 def ode_schedule(method: str, modality_steps: int):
     """the flat evaluation list of one solve over `modality_steps` grid points: stages x (modality_steps - 1) entries, in the order the decode loops
     walk them.  For `midpoint` the times and the coefficients `w[q]` are the numbers the midpoint loops form themselves (t0, t0 + dt / 2; dt / 2, dt)."""
+    return list(_schedule(method, int(modality_steps)))
+
+
+@functools.lru_cache(maxsize=64)                             # (exact fractions, one fp32 rounding per weight: ~1 ms at 16 grid points, paid once)
+def _schedule(method, modality_steps):
     tab = TABLEAUS[method]
     ts = torch.linspace(0, 1, modality_steps)
     n = len(tab.c)
@@ -75,4 +82,25 @@ def ode_schedule(method: str, modality_steps: int):
             last = q == n - 1
             t = t1 if tab.c[q] == 1 else t0 + float(tab.c[q]) * dt
             out.append(Eval(t, q, last, scale(tab.A[q]), wb[:q + 1] if last else scale(tab.A[q + 1]), wb))
-    return out
+    return tuple(out)
+
+
+# what the continuous decode loop uploads per evaluation (the solver control block of a mixed step, one column per evaluation):
+#   times   the evaluation times (a tuple of Python floats)  modes   fp32: 1 = a stage, 2 = the evaluation that ends its step
+#   rows    fp32 [1, n] for `midpoint` - the coefficient of tfx_ode_update; [8, n] for the tableau rules - the stage index, the 3 weights of the
+#           evaluation's input, the 4 weights of the step's update (tfx_ode_rk_stage / tfx_ode_rk_update)
+Control = namedtuple('Control', 'times modes rows')
+
+
+@functools.lru_cache(maxsize=64)                             # (shared between calls: the arrays are read-only)
+def ode_control(method: str, modality_steps: int) -> Control:
+    sched = ode_schedule(method, modality_steps)
+    modes = np.array([2 if e.last else 1 for e in sched], np.float32)
+    if method == 'midpoint':
+        rows = np.array([[e.w[e.q] for e in sched]], np.float32)
+    else:
+        rows = np.zeros((8, len(sched)), np.float32)
+        for n, e in enumerate(sched):
+            rows[0, n] = e.q; rows[1:1 + e.q, n] = e.wa; rows[4:4 + len(e.wb), n] = e.wb
+    modes.flags.writeable = rows.flags.writeable = False
+    return Control(tuple(e.t for e in sched), modes, rows)

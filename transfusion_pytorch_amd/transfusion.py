@@ -1736,7 +1736,7 @@ class Transfusion(nn.Module):
         text token (T:1917-1924) and per ODE evaluation (T:1998-2006, T:2021-2029), with (`cache_kv=True`) or without the kv cache it returns.
         `sample_one` itself runs the batched KV-cached decoder; this loop exists so that the contract has a caller (the reference's
         cache-equivalence tests go through it, tests/test_transfusion.py:578-662) - tests/test_decode_contract_gpu.py compares the three."""
-        from .sampling import Sampler, _sample_text_token, _ode_axpy, _ode_rk_solve
+        from .sampling import Sampler, _sample_text_token, _ode_solve
         was_training = self.training
         self.eval()
         try:
@@ -1796,16 +1796,8 @@ class Transfusion(nn.Module):
                     fu = flow(t, yy, uncond_hist, uncond_cache)[0] if use_cfg else None
                     return fc, fu
 
-                ts = torch.linspace(0, 1, modality_steps)
-                if self.ode_method != 'midpoint':                                    # the other tableaus (ode.py): one tfx_ode_rk_axpy per evaluation;
-                    y = _ode_rk_solve(self.ode_method, modality_steps, y, velocity, cfg_scale, stream)   # new_cache: the last evaluation's, as below
-                else:
-                    for k in range(modality_steps - 1):                              # torchdiffeq fixed-grid midpoint
-                        t0, dt = float(ts[k]), float(ts[k + 1] - ts[k])
-                        fc, fu = velocity(t0, y)
-                        y_mid = _ode_axpy(y.contiguous(), fc.contiguous(), fu, cfg_scale, dt * 0.5, stream)
-                        fc, fu = velocity(t0 + dt * 0.5, y_mid)
-                        y = _ode_axpy(y.contiguous(), fc.contiguous(), fu, cfg_scale, dt, stream)
+                # torchdiffeq fixed-grid semantics (ode.py); new_cache: the last evaluation's
+                y = _ode_solve(self.ode_method, modality_steps, y, velocity, cfg_scale, stream)
                 sample.append((ty, y))
                 sample.append(torch.tensor([self.eom_ids[ty]], device=dev))
                 st.curr_seq = [self.eom_ids[ty]]
