@@ -242,6 +242,21 @@ int tfx_laser_v_fwd(const tfx_laser_v_args* a, void* stream);
 int tfx_laser_v_bwd(const tfx_laser_v_args* a, void* stream);
 
 /* ---- token-wise kernels ---------------------------------------------------------------------- */
+/* NULL parameter-gradient outputs (frozen parameters: `requires_grad_(False)` on the Python side).  The column sums these kernels add into a parameter's
+ * gradient may be switched off one by one by passing NULL for the output:
+ *   tfx_adaln_pre_args.dgamma_text, .dtable            tfx_adaln_pre_bwd, tfx_adaln_pre_post_bwd (per-token and segment forms)
+ *   tfx_adaln_post_args.dlayerscale, .dbias, .dtable   tfx_adaln_post_bwd, tfx_adaln_pre_post_bwd, tfx_attnres_pull_bwd's wrapper side (per-token and segment forms)
+ *   tfx_rmsnorm_args.dgamma                   tfx_rmsnorm_bwd
+ *   tfx_attnres_args.dgamma, .dpq             tfx_attnres_bwd (push form)
+ *   tfx_attnres_src.dgamma, .dpq              tfx_attnres_finish (pull form; the d w accumulator src.dw is always formed)
+ * NULL means: the block-level reduction of that sum is not formed and no atomic is issued for it.  Every other output of the call is bit-identical to the
+ * same call with the pointer (rows, stored table gradients; atomically accumulated sums agree as two runs of one call do), and with the pointer the kernel
+ * computes what it computed before NULL had a meaning.  Each pointer is independent.  One block-uniform branch per site (the pointer is a kernel argument).
+ * `dtable` NULL: neither the per-token atomics nor the segment forms' stores of that side's table gradient are issued (in tfx_adaln_pre_post_bwd the two
+ * sides' pointers are independent); the engine passes it when no trainable parameter sits behind the AdaLN tables (to_film.*, to_ada_ln_zero.*,
+ * to_time_cond.*).
+ * NOT NULL-able: ONE of dgamma_q / dgamma_k of the QK-norm kernels and attention epilogues (both NULL with both gains NULL only): the engine points a
+ * frozen gain's sum at a 64-float scratch row. */
 typedef struct {
   int32_t T, d;
   const tfx_bf16* x; tfx_bf16* u;            /* [T,d] */

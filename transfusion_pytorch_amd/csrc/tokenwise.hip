@@ -81,7 +81,10 @@ template <int NC> TFX_DEV void widen(Row<NC>& o, const RowRaw<NC>& r) {
     for (int e = 0; e < 8; e++) o.v[i][e] = bf2f(r.v[i][e]);
 }
 // block-level reduction of per-lane column partials over the block's waves, then global atomics
+// out == NULL (a frozen parameter's gradient, tfx.h "NULL parameter-gradient outputs"): the sum is not formed and nothing is added - `out` is a
+// kernel argument, so the branch is uniform over the block and no wave misses a barrier
 template <int NC> TFX_DEV void flush_col_partials(const Row<NC>& part, float* out, int d, float* smem /* [WAVES][NC*512] */) {
+  if (!out) return;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
   for (int i = 0; i < NC; i++)
@@ -183,7 +186,7 @@ template <int NC> __global__ __launch_bounds__(256) void adaln_pre_bwd_k(tfx_ada
         float xh = (x.v[i][e] - mean) * rstd;
         float dg = du.v[i][e] * xh;
         if (inst < 0) pg.v[i][e] += dg;
-        else {
+        else if (p.dtable) {                       // (NULL: no trainable parameter behind the AdaLN tables - uniform, a kernel argument)
           atomicAdd(p.dtable + (size_t)inst * p.ld_table + c * 8 + e, dg);
           atomicAdd(p.dtable + (size_t)inst * p.ld_table + d + c * 8 + e, du.v[i][e]);
         }
@@ -305,7 +308,7 @@ template <int NC> __global__ __launch_bounds__(256) void adaln_post_bwd_k(tfx_ad
         float gy = g.v[i][e] * y.v[i][e];
         float sc;
         if (inst < 0) { sc = 1.f + s.v[i][e]; pl.v[i][e] += gy; }
-        else { sc = sigmoidf_(s.v[i][e]); atomicAdd(p.dtable + (size_t)inst * p.ld_table + 2 * d + c * 8 + e, gy * sc * (1.f - sc)); }
+        else { sc = sigmoidf_(s.v[i][e]); if (p.dtable) atomicAdd(p.dtable + (size_t)inst * p.ld_table + 2 * d + c * 8 + e, gy * sc * (1.f - sc)); }
         g.v[i][e] *= sc; pb.v[i][e] += g.v[i][e];
       }
     }
@@ -397,7 +400,7 @@ template <int NC> __global__ __launch_bounds__(512) void adaln_pre_bwd_seg_k(tfx
       for (int i = 0; i < NC; i++)
 #pragma unroll
         for (int e = 0; e < 8; e++) pg.v[i][e] += ag.v[i][e];
-    } else {
+    } else if (p.dtable) {
       float* dt = p.dtable + (size_t)inst * p.ld_table;
 #pragma unroll
       for (int i = 0; i < NC; i++) {
@@ -461,7 +464,7 @@ template <int NC> __global__ __launch_bounds__(512) void adaln_post_bwd_seg_k(tf
       for (int i = 0; i < NC; i++)
 #pragma unroll
         for (int e = 0; e < 8; e++) pl.v[i][e] += az.v[i][e];
-    } else {
+    } else if (p.dtable) {
       float* dt = p.dtable + (size_t)inst * p.ld_table + 2 * d;
 #pragma unroll
       for (int i = 0; i < NC; i++) {
@@ -903,9 +906,11 @@ template <int NC> __global__ __launch_bounds__(512) void adaln_pre_post_bwd_seg_
           z0[e] = az.v[i][e] * sc.v[i][e] * (1.f - sc.v[i][e]);
           z1[e] = az.v[i][4 + e] * sc.v[i][4 + e] * (1.f - sc.v[i][4 + e]);
         }
-        *(f32x4*)(dt + c * 8) = a0; *(f32x4*)(dt + c * 8 + 4) = a1;
-        *(f32x4*)(dt + d + c * 8) = b0; *(f32x4*)(dt + d + c * 8 + 4) = b1;
-        *(f32x4*)(dz + c * 8) = z0; *(f32x4*)(dz + c * 8 + 4) = z1;
+        if (p.dtable) {                              // (each side's table gradient may be NULL on its own)
+          *(f32x4*)(dt + c * 8) = a0; *(f32x4*)(dt + c * 8 + 4) = a1;
+          *(f32x4*)(dt + d + c * 8) = b0; *(f32x4*)(dt + d + c * 8 + 4) = b1;
+        }
+        if (q.dtable) { *(f32x4*)(dz + c * 8) = z0; *(f32x4*)(dz + c * 8 + 4) = z1; }
       }
     }
   }
@@ -1082,7 +1087,7 @@ template <int NC, int NJ, bool DB> __global__ __launch_bounds__(512) void attnre
           for (int e = 0; e < 8; e++) {
             const float sce = e < 4 ? s0[e & 3] : s1[e & 3];
             const float gy = G.v[i][e] * yy.v[i][e];
-            if (tok_mode && inst >= 0) atomicAdd(q.dtable + (size_t)inst * q.ld_table + 2 * d + c * 8 + e, gy * sce * (1.f - sce));
+            if (tok_mode && inst >= 0) { if (q.dtable) atomicAdd(q.dtable + (size_t)inst * q.ld_table + 2 * d + c * 8 + e, gy * sce * (1.f - sce)); }
             else az.v[i][e] += gy;
             G.v[i][e] *= sce; if constexpr (DB) pb.v[i][e] += G.v[i][e];
           }
@@ -1096,7 +1101,7 @@ template <int NC, int NJ, bool DB> __global__ __launch_bounds__(512) void attnre
         for (int i = 0; i < NC; i++)
 #pragma unroll
           for (int e = 0; e < 8; e++) pl.v[i][e] += az.v[i][e];
-      } else if (!tok_mode) {
+      } else if (!tok_mode && q.dtable) {
         float* dt = q.dtable + (size_t)inst * q.ld_table + 2 * d;
 #pragma unroll
         for (int i = 0; i < NC; i++) {
@@ -1378,7 +1383,7 @@ __global__ __launch_bounds__(512) void attnres_pull_dma_k(tfx_attnres_pull_args 
 #pragma unroll
           for (int e = 0; e < 8; e++) {
             const float gy = G.v[i][e] * yy.v[i][e];
-            if (tok_mode && inst >= 0) atomicAdd(q.dtable + (size_t)inst * q.ld_table + 2 * d + c * 8 + e, gy * sc.v[i][e] * (1.f - sc.v[i][e]));
+            if (tok_mode && inst >= 0) { if (q.dtable) atomicAdd(q.dtable + (size_t)inst * q.ld_table + 2 * d + c * 8 + e, gy * sc.v[i][e] * (1.f - sc.v[i][e])); }
             else az.v[i][e] += gy;
             G.v[i][e] *= sc.v[i][e]; pb.v[i][e] += G.v[i][e];
           }
@@ -1392,7 +1397,7 @@ __global__ __launch_bounds__(512) void attnres_pull_dma_k(tfx_attnres_pull_args 
         for (int i = 0; i < NC; i++)
 #pragma unroll
           for (int e = 0; e < 8; e++) pl.v[i][e] += az.v[i][e];
-      } else if (!tok_mode) {
+      } else if (!tok_mode && q.dtable) {
         float* dt = q.dtable + (size_t)inst * q.ld_table + 2 * d;
 #pragma unroll
         for (int i = 0; i < NC; i++) {
@@ -1431,7 +1436,11 @@ __global__ __launch_bounds__(256) void attnres_prep_k(const tfx_attnres_src* src
 __global__ __launch_bounds__(256) void attnres_finish_k(const tfx_attnres_src* src, int d) {
   const tfx_attnres_src sj = src[blockIdx.y];
   const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c < d) { const float dw = sj.dw[c]; sj.dgamma[c] += dw * sj.pq[c]; sj.dpq[c] += dw * (1.f + sj.gamma[c]); }
+  if (c < d) {
+    const float dw = sj.dw[c];
+    if (sj.dgamma) sj.dgamma[c] += dw * sj.pq[c];              // (NULL: that parameter is frozen - uniform over the block, the record is per blockIdx.y)
+    if (sj.dpq) sj.dpq[c] += dw * (1.f + sj.gamma[c]);
+  }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2616,6 +2625,6 @@ int tfx_laser_v_bwd(const tfx_laser_v_args* a, void* s) {
   if (nch >= (1ll << 31)) return -4;
   hipLaunchKernelGGL(laser_v_bwd_k, dim3((unsigned)((nch + 255) / 256)), dim3(256), 0, ST(s), *a, (unsigned)nch); RET();
 }
-const char* tfx_version(void) { return "tfx-hip gfx950 r5-laser-muon-selfflow-adamgroups-oderk-tntable-atan2-ablate"; }
+const char* tfx_version(void) { return "tfx-hip gfx950 r5-laser-muon-selfflow-adamgroups-oderk-tntable-atan2-ablate-frozen"; }
 
 }  // extern "C"

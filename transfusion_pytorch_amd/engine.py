@@ -307,7 +307,7 @@ class Plan:
         self.fwd, self.bwd = LaunchList(), LaunchList()
         self.noise_args = {}
         self.loaded_structure = None
-        self._seg_args = []
+        self._seg_args, self._n_seg = [], 0
         self.seg_start = z(max(T, 1), dtype=torch.int32); self.seg_len = z(max(T, 1), dtype=torch.int32)
         # AttentionResidual backward in pull form (tfx_attnres_pull_bwd): every layer's depth softmax is kept per token by the forward;
         # TFX_ATTNRES_PULL=0 keeps the push form (tfx_attnres_bwd: one read-modify-write sweep over all earlier hiddens per layer; A/B)
@@ -343,7 +343,11 @@ class Plan:
             self.dtables = z(I1, nt3, dtype=torch.float32); self.dtab_bf = e(I1, nt3)
             self.dcond = e(I1, 4 * d); self.dpre = e(I1, 4 * d)
             self.onehot = e(T, md.vp)
+            self.gsink = z(64, dtype=torch.float32)          # where a frozen q_norm / k_norm gain's gradient goes (the attention epilogues take no NULL for one gain alone)
+            self.rows_in = False                             # this step hands rows of d loss / d x_0 back to PyTorch (user encoders, positional embeddings): set by the model
+            self._frozen, self._bwd_sets, self._src_tab = frozenset(), {}, None
             self._build_backward()
+            self._bwd_sets[self._frozen] = {k: getattr(self, k) for k in self._BWD_STATE}
 
     # ------------------------------------------------------------------------------------ helpers
     def _nt(self, lst, algo_n=None, algo_k=None, **kw):
@@ -774,6 +778,7 @@ class Plan:
     def set_segments(self, seg_start, seg_len):
         n_seg = int(seg_start.numel())
         self.seg_start[:n_seg].copy_(seg_start); self.seg_len[:n_seg].copy_(seg_len)
+        self._n_seg = n_seg
         for a in self._seg_args:
             a.n_seg = n_seg
 
@@ -845,6 +850,15 @@ class Plan:
         pp, gp = ps.ptr, ps.grad_ptr
         lib = capi.lib()
         gmap = ps._maps['geglu']
+        # frozen parameters (`requires_grad_(False)`, select_frozen): `tr(name)` - the parameter trains; `gpn` - its gradient's address, or NULL, which the
+        # token-wise kernels read as "this sum is not formed" (tfx.h).  A weight-gradient product whose target is frozen is not in the list at all.
+        fz = self._frozen
+        tr = lambda name: name not in fz
+        gpn = lambda name: gp(name) if name not in fz else None
+        low, self.bwd_end = self._lowest_consumer()
+        ada = self._time_cond_trains() or any(tr(n) for n in ps.params if '.to_film.' in n or '.to_ada_ln_zero.' in n)
+        if low == 'none':
+            self.bwd_end = 0
         # model-space `model_output_clean`: pred = (W embed - W proj) s, so the (already s-scaled) seed also flows, negated, through q = W proj:
         #   d proj = -(dpred W)  ->  latent_to_model weight / bias gradients;   dW += (-dpred)^T proj.   Run before the main list when the mode is 'model'.
         self.clean_bwd = LaunchList()
@@ -854,17 +868,43 @@ class Plan:
                 if t in self.ext:
                     continue
                 dl = md.dim_latents[t]; dlp = pad_to(dl, 64); lt = self.lat[t]
-                lt['ndpred'] = torch.zeros(r, dlp, device=self.ps.device, dtype=BF16)
+                w_out, w_in, b_in = tr(f'model_to_latent_projs.{t}.weight'), dl != d and tr(f'latent_to_model_projs.{t}.weight'), dl != d and tr(f'latent_to_model_projs.{t}.bias')
+                if not (w_out or w_in or b_in):
+                    continue
+                if 'ndpred' not in lt:                                   # (one buffer for the lists of every frozen set)
+                    lt['ndpred'] = torch.zeros(r, dlp, device=self.ps.device, dtype=BF16)
                 self._raw(C, lib.tfx_scale_bf16_copy, lt['dpred'].data_ptr(), lt['ndpred'].data_ptr(), r * dlp, -1.0)
-                self._tn(C, r, dl, d, A=lt['ndpred'], lda=dlp, a_cols=dlp, B=lt['proj'], ldb=lt['proj'].shape[1], b_cols=d,
-                         C=gp(f'model_to_latent_projs.{t}.weight'), ldc=d)
-                if dl != d:
-                    lt['dpx'] = torch.empty(r, d, device=self.ps.device, dtype=BF16)
+                if w_out:
+                    self._tn(C, r, dl, d, A=lt['ndpred'], lda=dlp, a_cols=dlp, B=lt['proj'], ldb=lt['proj'].shape[1], b_cols=d,
+                             C=gp(f'model_to_latent_projs.{t}.weight'), ldc=d)
+                if w_in or b_in:
+                    if 'dpx' not in lt:
+                        lt['dpx'] = torch.empty(r, d, device=self.ps.device, dtype=BF16)
                     self._nt(C, algo_k=dl, A=lt['ndpred'], lda=dlp, B=S[f'outp_t{t}'], ldb=dlp, M=r, N=d, K=dlp, epi=E['TFX_EPI_BF16'], C=lt['dpx'], ldc=d)
-                    self._tn(C, r, d, dl, A=lt['dpx'], lda=d, a_cols=d, B=lt['xt'], ldb=dlp, b_cols=dlp, C=gp(f'latent_to_model_projs.{t}.weight'), ldc=dl)
-                    self._raw(C, lib.tfx_colsum_bf16, lt['dpx'].data_ptr(), d, r, d, None, None, gp(f'latent_to_model_projs.{t}.bias'))
+                    if w_in:
+                        self._tn(C, r, d, dl, A=lt['dpx'], lda=d, a_cols=d, B=lt['xt'], ldb=dlp, b_cols=dlp, C=gp(f'latent_to_model_projs.{t}.weight'), ldc=dl)
+                    if b_in:
+                        self._raw(C, lib.tfx_colsum_bf16, lt['dpx'].data_ptr(), d, r, d, None, None, gp(f'latent_to_model_projs.{t}.bias'))
+        def head_tn(t=None):
+            if t is None:
+                if tr('to_text_logits.weight'):
+                    self._tn(L, T, md.vocab, d, A=self.dlogits, lda=md.vp, a_cols=md.vp, B=self.embed, ldb=d, b_cols=d, C=gp('to_text_logits.weight'), ldc=d)
+            elif tr(f'model_to_latent_projs.{t}.weight'):
+                dl = md.dim_latents[t]; dlp = pad_to(dl, 64)
+                self._tn(L, self.R[t], dl, d, A=self.lat[t]['dpred'], lda=dlp, a_cols=dlp, B=self.embed, ldb=d, b_cols=d, b_rowmap=self.row_gat[t],
+                         C=gp(f'model_to_latent_projs.{t}.weight'), ldc=d)
+        if fz:
+            # with a frozen set the heads' weight gradients come FIRST, so that a backward with nothing trainable below the heads is this prefix of the
+            # list (`bwd_end`); with nothing frozen the list keeps the order it always had
+            head_tn()
+            for t in self.R:
+                if t not in self.ext:
+                    head_tn(t)
+            if low == 'heads':
+                self.bwd_end = len(L)
         self._nt(L, algo_k=md.vocab, A=self.dlogits, lda=md.vp, B=S['logits_t'], ldb=md.vp, M=T, N=d, K=md.vp, epi=E['TFX_EPI_BF16'], C=self.dembed, ldc=d)
-        self._tn(L, T, md.vocab, d, A=self.dlogits, lda=md.vp, a_cols=md.vp, B=self.embed, ldb=d, b_cols=d, C=gp('to_text_logits.weight'), ldc=d)
+        if not fz:
+            head_tn()
         for t, r in self.R.items():
             dl = md.dim_latents[t]; dlp = pad_to(dl, 64); lt = self.lat[t]
             if t in self.ext:     # d loss / d (embedding rows handed to the user's decoder), from autograd: dembed[row_tok] += gemb
@@ -873,12 +913,14 @@ class Plan:
                 continue
             self._nt(L, algo_k=dl, A=lt['dpred'], lda=dlp, B=S[f'outp_t{t}'], ldb=dlp, M=r, N=d, K=dlp, epi=E['TFX_EPI_RESID'], C=self.dembed, ldc=d,
                      R=self.dembed, ldr=d, resid_mapped=1, rowmap=self.row_tok[t])
-            self._tn(L, r, dl, d, A=lt['dpred'], lda=dlp, a_cols=dlp, B=self.embed, ldb=d, b_cols=d, b_rowmap=self.row_gat[t],
-                     C=gp(f'model_to_latent_projs.{t}.weight'), ldc=d)
+            if not fz:
+                head_tn(t)
         self.tap_final = len(L)               # hidden tap depth + 1 (the final norm's output): its gradient joins `dembed` in front of this launch (run_bwd)
         self._k(L, 'tfx_rmsnorm_bwd', 'tfx_rmsnorm_args', T=T, d=d, x=self.xres[D], gamma=pp('transformer.norm.gamma'), dy=self.dembed,
-                dx=self.gfin, dgamma=gp('transformer.norm.gamma'))
+                dx=self.gfin, dgamma=gpn('transformer.norm.gamma'))
         self._hbm(L, 3)
+        if low == 'norm':
+            self.bwd_end = len(L)
         src = skip_sources(md)
         pushed = set(src.values())
         g = self.gfin
@@ -890,27 +932,30 @@ class Plan:
         if pull:
             # pull-form AttentionResidual backward: one source record per layer (device array, lowest layer first) - the FINAL gradient of the
             # layer's AttentionResidual output (the backward's last write to that buffer), its saved softmax state, its w = (1 + gamma) pq
-            self.dsum = torch.empty(D, T, device=ps.device, dtype=torch.float32)
-            self.wtab = torch.empty(2, D, d, device=ps.device, dtype=torch.float32)          # w rows | d w accumulators
-            self.nbytes += self.dsum.numel() * 4 + self.wtab.numel() * 4
+            if not hasattr(self, 'dsum'):                                                        # (shared by the lists of every frozen set: one runs at a time)
+                self.dsum = torch.empty(D, T, device=ps.device, dtype=torch.float32)
+                self.wtab = torch.empty(2, D, d, device=ps.device, dtype=torch.float32)          # w rows | d w accumulators
+                self.nbytes += self.dsum.numel() * 4 + self.wtab.numel() * 4
             SRC = capi.STRUCTS['tfx_attnres_src']
             recs = (SRC * D)()
             for j in range(D):
                 pj = f'transformer.layers.{j}.3'
                 gj = self.gfin if j == D - 1 else (self.gx[j + 1] if md.has_skip(j + 1) else self.dH[j + 2])
                 for k, v in dict(g=gj, save=self.arsave[j], dsum=self.dsum[j], w=self.wtab[0, j], dw=self.wtab[1, j], gamma=pp(f'{pj}.norm_keys.gamma'),
-                                 pq=pp(f'{pj}.pseudo_queries'), dgamma=gp(f'{pj}.norm_keys.gamma'), dpq=gp(f'{pj}.pseudo_queries'), L=j + 2).items():
+                                 pq=pp(f'{pj}.pseudo_queries'), dgamma=gpn(f'{pj}.norm_keys.gamma'), dpq=gpn(f'{pj}.pseudo_queries'), L=j + 2).items():
                     setattr(recs[j], k, v.data_ptr() if hasattr(v, 'data_ptr') else v)
             raw = torch.frombuffer(bytearray(ctypes.string_at(ctypes.addressof(recs), ctypes.sizeof(recs))), dtype=torch.uint8)
             self._src_tab = raw.to(ps.device)
             self._src_size = ctypes.sizeof(SRC)
             self._raw(L, lib.tfx_attnres_prep, self._src_tab.data_ptr(), D, d)
         self._pull_args = {}                  # hidden index -> its pull launch's args (hidden taps 1 .. depth set their `add` operand, set_taps)
-        def pull_launch(l, out_own, add, dh, post):
+        def pull_launch(l, out_own, add, dh, post, j0=None, lst=None):
             """gradient of hidden l from the layers j >= max(l - 1, 0) that mixed it (+ the output side `post` of the wrapper that produced the hidden).
             d w of those layers accumulates inside the launch for few narrow sources; otherwise the launch exports the per-token coefficients and
             one weight-gradient GEMM K1^T . h adds them (rows j0.. of the d w table are contiguous)"""
-            j0 = max(l - 1, 0)
+            tail = j0 is not None              # (`ar_tail` below: only the d w of the sources j0 .. D - 1 is wanted, into the list `lst`)
+            lst = L if lst is None else lst
+            j0 = max(l - 1, 0) if j0 is None else j0
             ns = D - j0
             export = ns > 8 or d > 512
             if export and not hasattr(self, 'k1buf'):
@@ -919,12 +964,13 @@ class Plan:
                                out_own=out_own, out_err=self.arerr[l - 1] if out_own is not None else None, add=add, dh=dh,
                                seg_start=self.seg_start, seg_len=self.seg_len, n_seg=0, k1=self.k1buf if export else None, ld_k1=32)
             self._seg_args.append(a)
-            self._pull_args[l] = a
+            if not tail:
+                self._pull_args[l] = a
             self._keep = getattr(self, '_keep', []) + [a, post]
-            self._raw(L, lib.tfx_attnres_pull_bwd, ctypes.addressof(a), ctypes.addressof(post) if post is not None else None)
-            self._hbm(L, ns + 6 if post is not None else ns + 4, 12 * ns * T)     # n_src gradient rows + h, out, err in, dh out (+ g, y in, dy out of the wrapper side); saved softmax state
+            self._raw(lst, lib.tfx_attnres_pull_bwd, ctypes.addressof(a), ctypes.addressof(post) if post is not None else None)
+            self._hbm(lst, ns + 6 if post is not None else ns + 4, 12 * ns * T)     # n_src gradient rows + h, out, err in, dh out (+ g, y in, dy out of the wrapper side); saved softmax state
             if export:
-                self._tn(L, T, ns, d, A=self.k1buf, lda=32, a_cols=32, B=self.hid[l], ldb=d, b_cols=d, C=self.wtab[1, j0], ldc=d)
+                self._tn(lst, T, ns, d, A=self.k1buf, lda=32, a_cols=32, B=self.hid[l], ldb=d, b_cols=d, C=self.wtab[1, j0], ldc=d)
         run, pending = self.tn_run, []
         run_low = {}                          # layer -> lowest layer of its run (where the run's table launch sits and its join event is recorded)
         if run:
@@ -932,11 +978,15 @@ class Plan:
             for j in range(D - 1, -1, -1):
                 top = min((j // per_g + 1) * per_g, D) - 1
                 run_low[j] = max(top - ((top - j) // run + 1) * run + 1, j // per_g * per_g)
+                if isinstance(low, int) and j >= low:
+                    run_low[j] = max(run_low[j], low)               # the products of the layers above a frozen stack launch where the truncated backward ends
         for i in range(D - 1, -1, -1):
             p = f'transformer.layers.{i}'
             x_in = self.xres[i]
             x_a = self.xa[i] if md.has_skip(i) else x_in
             (ta, dta), (tf, dtf) = self._tab(i, 0), self._tab(i, 1)
+            if not ada:
+                dta = dtf = None                    # no trainable parameter behind the AdaLN tables: their gradient is not formed (tfx.h: dtable NULL)
             par = self._bwd_slot(i)
             dy_f, dy_a, dag, dqkvg = self.dy_f[par], self.dy_a[par], self.dag_p[par], self.dqkvg_p[par]
             if not run and i + 2 <= D - 1:
@@ -945,8 +995,8 @@ class Plan:
                 sync('tfx_join_wait', run_low[i + len(self.dag_p)])      # ... of layer i + (number of buffers): the table launch of that layer's run
             G = self.dH[i + 1]
             a_postf = capi.make_args('tfx_adaln_post_args', T=T, d=d, y=self.yf[i], tok_inst=self.tok_inst, table=tf, ld_table=nt3,
-                                     layerscale=pp(f'{p}.2.layerscale'), g=G, dy=dy_f, dtable=dtf, dlayerscale=gp(f'{p}.2.layerscale'),
-                                     seg_start=self.seg_start, seg_len=self.seg_len, n_seg=0, dbias=gp(f'{p}.2.fn.net.3.bias'))   # ff2 bias gradient = column sums of dy
+                                     layerscale=pp(f'{p}.2.layerscale'), g=G, dy=dy_f, dtable=dtf, dlayerscale=gpn(f'{p}.2.layerscale'),
+                                     seg_start=self.seg_start, seg_len=self.seg_len, n_seg=0, dbias=gpn(f'{p}.2.fn.net.3.bias'))   # ff2 bias gradient = column sums of dy
             self._seg_args.append(a_postf)
             if pull:
                 # dH[i+1] = gradient of hidden i + 1 from the AttentionResiduals of layers i .. D-1 (all final), formed ONCE; the feed-forward
@@ -956,7 +1006,7 @@ class Plan:
                 g2 = self.dskip[i + 1] if (i + 1) in pushed else None
                 self._k(L, 'tfx_attnres_bwd', 'tfx_attnres_args', T=T, d=d, L=i + 2, hiddens=self.hid, stride_h=T * d,
                         gamma=pp(f'{p}.3.norm_keys.gamma'), pq=pp(f'{p}.3.pseudo_queries'), g=g, g2=capi.ptr(g2), dhiddens=self.dH, stride_dh=T * d,
-                        first=1 if i == D - 1 else 0, dgamma=gp(f'{p}.3.norm_keys.gamma'), dpq=gp(f'{p}.3.pseudo_queries'))
+                        first=1 if i == D - 1 else 0, dgamma=gpn(f'{p}.3.norm_keys.gamma'), dpq=gpn(f'{p}.3.pseudo_queries'))
                 # ---- feedforward wrapper
                 L.append(('tfx_adaln_post_bwd', a_postf))
             self._nt(L, algo_n=di, A=dy_f, lda=d, B=S[f'ff2_t{i}'], ldb=d, M=T, N=dip, K=d, epi=E['TFX_EPI_GEGLU_BWD'], C=dag, ldc=2 * dip,
@@ -969,20 +1019,25 @@ class Plan:
             # launch (158 vs 145 us, profiles/r05_shapes.txt) - and with its scale row in LDS the pull kernel no longer spills WITH the bias partials)
             ff_grp = [(d, di, dict(A=dy_f, lda=d, a_cols=d, B=self.hm[i], ldb=dip, b_cols=dip, C=gp(f'{p}.2.fn.net.3.weight'), ldc=di)),
                       (2 * dip, d, dict(algo_n=2 * di, A=dag, lda=2 * dip, a_cols=2 * dip, B=self.uf[i], ldb=d, b_cols=d, rowmap=gmap,
-                                        C=gp(f'{p}.2.fn.net.0.weight'), ldc=d, colsum=gp(f'{p}.2.fn.net.0.bias')))]
+                                        C=gp(f'{p}.2.fn.net.0.weight'), ldc=d, colsum=gpn(f'{p}.2.fn.net.0.bias')))]
+            if fz:
+                ff_grp = [m for m, nm in zip(ff_grp, ('net.3', 'net.0')) if tr(f'{p}.2.fn.{nm}.weight')]
+                if tr(f'{p}.2.fn.net.0.bias') and not tr(f'{p}.2.fn.net.0.weight'):
+                    # a trainable bias behind a frozen weight: its column sums of d[a|g] without the product they used to ride in
+                    self._raw(L, lib.tfx_colsum_bf16, dag.data_ptr(), 2 * dip, T, 2 * dip, gmap.data_ptr(), None, gp(f'{p}.2.fn.net.0.bias'))
             # (one launch per LAYER - these two waiting for the attention wrapper's products - measured 4.21 -> 3.97 ms on the family and nothing on the overlapped
             #  step, profiles/r05b_ab_tn_layer_group.txt: removed in round 6)
             if run:
                 pending += ff_grp
-            else:
+            elif ff_grp:
                 self._tn_group(L, T, ff_grp, side=side)
             self._nt(L, algo_k=2 * di, A=dag, lda=2 * dip, B=S[f'ff1_t{i}'], ldb=2 * dip, M=T, N=d, K=2 * dip, epi=E['TFX_EPI_BF16'], C=self.du, ldc=d)
             a_pref = capi.make_args('tfx_adaln_pre_args', T=T, d=d, x=self.xb[i], tok_inst=self.tok_inst, table=tf, ld_table=nt3,
                                     gamma_text=pp(f'{p}.2.layernorm_gamma'), mean=_p(self.stats, 2, i), rstd=_p(self.stats, 3, i), du=self.du, dx=G,
-                                    dtable=dtf, dgamma_text=gp(f'{p}.2.layernorm_gamma'), seg_start=self.seg_start, seg_len=self.seg_len, n_seg=0)
+                                    dtable=dtf, dgamma_text=gpn(f'{p}.2.layernorm_gamma'), seg_start=self.seg_start, seg_len=self.seg_len, n_seg=0)
             # ---- attention wrapper
             a_posta = capi.make_args('tfx_adaln_post_args', T=T, d=d, y=self.ya[i], tok_inst=self.tok_inst, table=ta, ld_table=nt3,
-                                     layerscale=pp(f'{p}.1.layerscale'), g=G, dy=dy_a, dtable=dta, dlayerscale=gp(f'{p}.1.layerscale'),
+                                     layerscale=pp(f'{p}.1.layerscale'), g=G, dy=dy_a, dtable=dta, dlayerscale=gpn(f'{p}.1.layerscale'),
                                      seg_start=self.seg_start, seg_len=self.seg_len, n_seg=0)
             self._seg_args += [a_pref, a_posta]
             # input side of the feed-forward wrapper + output side of the attention wrapper: the residual-gradient row is written once, not read back
@@ -992,7 +1047,9 @@ class Plan:
             self._nt(L, algo_n=md.hd, A=dy_a, lda=d, B=S[f'out_t{i}'], ldb=d, M=T, N=hd, K=d, epi=E['TFX_EPI_BF16'], C=self.dog, ldc=hd)
             gam = self._gains(i)
             # (without QK-RMSNorm the gain gradients are never written: the unread q_norm / k_norm gammas keep a zero gradient)
-            dgam = lambda pre: {f'{pre}dgamma_{nm}': gp(f'{p}.1.fn.{nm}_norm.gamma') if md.qk_norm else 0 for nm in 'qk'}
+            # (a frozen gain's sum goes to the plan's 64-float sink: the attention epilogues take NULL for both gains - no RMS normalisation - not for one)
+            dgam = lambda pre: {f'{pre}dgamma_{nm}': (gp(f'{p}.1.fn.{nm}_norm.gamma') if tr(f'{p}.1.fn.{nm}_norm.gamma') else self.gsink.data_ptr()) if md.qk_norm else 0
+                                for nm in 'qk'}
             if os.environ.get('TFX_ATTN_QKNR', '1') != '0':
                 # round 5: the backward of QK-RMSNorm + RoPE rides in the epilogues of the dQ and dK/dV kernels (tfx.h tfx_attn_args.nr_*): d q~ | d k~ are never
                 # written out and read back, and the token-wise launch below drops out of the layer
@@ -1020,7 +1077,7 @@ class Plan:
             # (pull form: the gradient a U-Net skip hands to this layer's input joins here, so that G ends up as the TOTAL gradient of xres[i])
             self._k(L, 'tfx_adaln_pre_bwd', 'tfx_adaln_pre_args', T=T, d=d, x=x_a, tok_inst=self.tok_inst, table=ta, ld_table=nt3,
                     gamma_text=pp(f'{p}.1.layernorm_gamma'), mean=_p(self.stats, 0, i), rstd=_p(self.stats, 1, i), du=self.du, dx=G,
-                    dtable=dta, dgamma_text=gp(f'{p}.1.layernorm_gamma'), seg_start=self.seg_start, seg_len=self.seg_len, n_seg=0,
+                    dtable=dta, dgamma_text=gpn(f'{p}.1.layernorm_gamma'), seg_start=self.seg_start, seg_len=self.seg_len, n_seg=0,
                     dx_add=self.dskip[i] if (pull and i in pushed) else None)
             self._hbm(L, 4 + (1 if (pull and i in pushed) else 0))          # du, x in; residual gradient in / out (+ the U-Net skip's share)
             self._seg_args.append(L[-1][1])
@@ -1033,7 +1090,9 @@ class Plan:
                                 k_group=0 if md.dim_head == 64 else md.dim_head)),
                    (md.nqk, d, dict(algo_n=md.nq, A=dqkvg, lda=ldq, a_cols=ldq, B=self.ua[i], ldb=d, b_cols=d, C=gp(f'{p}.1.fn.to_qk.0.weight'), ldc=d,
                                     rowmap=ps._maps['heads'] if md.dim_head != 64 else None))]
-            if md.has_skip(i):
+            if fz:
+                grp = self._frozen_attn_group(grp, p)
+            if md.has_skip(i) and tr(f'{p}.0.weight'):
                 sk = self.xres[src[i]]
                 # d W_skip [d, 2 d] = G^T [x | skip]: two members of the layer's group (as ONE split-B product it measured 117.6 us against 2 x 64 us,
                 # profiles/r05b_ab_skip_tn_split.txt: the split-B form was removed in round 6)
@@ -1045,31 +1104,49 @@ class Plan:
                 # is true at every i % per == 0).  dH[i + 1], the saved activations and the per-layer dy / d[a|g] / d[q|k|v|gates] buffers are not rewritten
                 # before it (the hidden taps ride in the pull launches, which write dH[l] once)
                 pending += grp
-                if launch:
+                if launch and len(pending) == 1:                     # (a frozen set left one product of the run: the plain launch)
+                    self._tn_group(L, T, pending, side=side)
+                    pending = []
+                elif launch and pending:
                     hi_l = max(j for j in run_low if run_low[j] == i)
                     self.tn_tables.append((len(L), i, hi_l, self._tn_table(L, T, pending, side=side), len(pending)))
                     pending = []
-            else:
+            elif grp:
                 self._tn_group(L, T, grp, side=side)
-            if I > 0 and i % per == 0:
+            # (a frozen stack below layer `low`: the group that holds `low` forms its products there, where the truncated backward ends, and the group
+            #  bases under it have nothing left to form)
+            if I > 0 and (i % per == 0 or i == low) and not (isinstance(low, int) and i < low):
                 # AdaLN conditioning weights (6d table columns per layer, 63 % of all parameters) of the layer GROUP that ends here: their table
                 # gradients are final once the group's backward is.  With the overlapped gradient exchange (dp_groups > 0) the weight / bias
                 # gradients are formed group by group, so that the gradient buffer completes back to front and a group's all-reduce can start
                 # during the backward; one GEMM per group (>= 768 tiles: no split, every block reduces all I instances).  Without an exchange
                 # (dp_groups == 0: one GPU, or one all-reduce after the backward) the "group" is the whole stack: ONE GEMM after layer 0
-                hi = min(i + per, D)
+                hi = min((i // per + 1) * per, D)
                 off, cols = i * 2 * 3 * d, (hi - i) * 2 * 3 * d
                 w_item = lambda it: L.append(Side(it) if side else it)
-                w_item((lib.tfx_cast_block_bf16, (self.dtables.data_ptr() + 4 * off, nt3, self.dtab_bf.data_ptr() + 2 * off, nt3, I, cols)))
-                self._tn(L, I, cols, 4 * d, side=side, A=self.dtab_bf.data_ptr() + 2 * off, lda=nt3, a_cols=cols, B=self.cond, ldb=4 * d, b_cols=4 * d,
-                         C=gp(f'{p}.1.to_film.weight'), ldc=4 * d)
-                w_item((lib.tfx_colsum_f32, (self.dtables.data_ptr() + 4 * off, nt3, I, cols, gp(f'{p}.1.to_film.bias'))))
+                # (frozen sets: the table columns of the group's trainable to_film / to_ada_ln_zero weights and biases, as runs of adjacent columns - with
+                #  nothing frozen one run each, the launches the list always held; the bf16 cast also feeds the time conditioning's backward)
+                w_runs, b_runs = self._adaln_runs(i, hi)
+                if w_runs or self._time_cond_trains():
+                    w_item((lib.tfx_cast_block_bf16, (self.dtables.data_ptr() + 4 * off, nt3, self.dtab_bf.data_ptr() + 2 * off, nt3, I, cols)))
+                g0 = ps.grad.data_ptr() + 4 * ps.offsets['transformer.layers.0.1.to_film.weight'][0]
+                b0 = ps.grad.data_ptr() + 4 * ps.offsets['transformer.layers.0.1.to_film.bias'][0]
+                for c0, nc in w_runs:
+                    self._tn(L, I, nc, 4 * d, side=side, A=self.dtab_bf.data_ptr() + 2 * c0, lda=nt3, a_cols=nc, B=self.cond, ldb=4 * d, b_cols=4 * d,
+                             C=g0 + 4 * c0 * 4 * d, ldc=4 * d)
+                for c0, nc in b_runs:
+                    w_item((lib.tfx_colsum_f32, (self.dtables.data_ptr() + 4 * c0, nt3, I, nc, b0 + 4 * c0)))
             if not run or launch:
                 sync('tfx_join_record', i)
             if self.dp_groups > 0:
                 if i % per == 0:                                     # lowest layer of a group: every gradient of layers >= i is final
                     sync('tfx_join_wait', i)
                     self.bwd_cuts.append((len(L), i, min(i + per, D) - 1))
+            if low == i and fz:
+                # nothing below this layer trains: a backward without another consumer of the data gradient (rows PyTorch receives, hidden taps) ends
+                # here, behind a join of its own (the list's last one is further down)
+                sync('tfx_join', 62)
+                self.bwd_end = len(L)
             if md.has_skip(i):
                 st = S[f'skip_t{i}']
                 self._nt(L, A=G, lda=d, B=st, ldb=d, M=T, N=d, K=d, epi=E['TFX_EPI_RESID'], C=self.gx[i], ldc=d, R=G, ldr=d)
@@ -1086,31 +1163,142 @@ class Plan:
             self._raw(L, lib.tfx_add_bf16, g.data_ptr(), self.dH[0].data_ptr(), self.dx0.data_ptr(), T * d)
             if 0 in pushed:
                 self._raw(L, lib.tfx_add_bf16, self.dx0.data_ptr(), self.dskip[0].data_ptr(), self.dx0.data_ptr(), T * d)
-        self._raw(L, lib.tfx_onehot_bf16, self.text_ids.data_ptr(), self.tok_inst.data_ptr(), self.onehot.data_ptr(), T, md.vp)
+        self.ar_tail = None
+        if fz and pull and isinstance(low, int) and any('.3.' in n for n in ps.params if n.startswith('transformer.layers.') and tr(n)):
+            # the backward ends at layer `low` (bwd_end), but d pseudo_queries / d norm_keys.gamma of a layer j sum over EVERY hidden 0 .. j + 1: the terms of
+            # hiddens 0 .. low, which the pull launches below `low` would have added on their way, come from launches of their own behind the truncated list -
+            # the trainable sources low .. D - 1 only, no wrapper side, the hidden's gradient into the (then unused) x_0 gradient buffer - and the closing
+            # tfx_attnres_finish.  A backward that runs the whole list (rows for PyTorch, hidden taps) does not run these.
+            A = self.ar_tail = LaunchList()
+            for l in range(low, -1, -1):
+                pull_launch(l, None, None, self.dx0, None, j0=low, lst=A)
+            self._raw(A, lib.tfx_attnres_finish, self._src_tab.data_ptr(), D, d)
+        if tr('text_embed.weight'):
+            self._raw(L, lib.tfx_onehot_bf16, self.text_ids.data_ptr(), self.tok_inst.data_ptr(), self.onehot.data_ptr(), T, md.vp)
         self._x0_param_grads(L, self.dx0)
-        if I > 0:
+        if I > 0 and self._time_cond_trains():
             # (dtab_bf = bf16 table gradients, cast layer by layer above - the join before this point covers the side stream)
             self._nt(L, A=self.dtab_bf, lda=nt3, B=S['ada_t'], ldb=nt3, M=I, N=4 * d, K=nt3, epi=E['TFX_EPI_BF16'], C=self.dcond, ldc=4 * d)
             self._raw(L, lib.tfx_silu_bwd, self.dcond.data_ptr(), self.pre.data_ptr(), self.dpre.data_ptr(), I * 4 * d)
-            self._tn(L, I, 4 * d, d + 1, A=self.dpre, lda=4 * d, a_cols=4 * d, B=self.fe, ldb=md.kf, b_cols=md.kf,
-                     C=gp('transformer.to_time_cond.1.weight'), ldc=d + 1)
-            self._raw(L, lib.tfx_colsum_bf16, self.dpre.data_ptr(), 4 * d, I, 4 * d, None, None, gp('transformer.to_time_cond.1.bias'))
+            if tr('transformer.to_time_cond.1.weight'):
+                self._tn(L, I, 4 * d, d + 1, A=self.dpre, lda=4 * d, a_cols=4 * d, B=self.fe, ldb=md.kf, b_cols=md.kf,
+                         C=gp('transformer.to_time_cond.1.weight'), ldc=d + 1)
+            if tr('transformer.to_time_cond.1.bias'):
+                self._raw(L, lib.tfx_colsum_bf16, self.dpre.data_ptr(), 4 * d, I, 4 * d, None, None, gp('transformer.to_time_cond.1.bias'))
 
     def _x0_param_grads(self, L, dx0):
         """from `dx0` = a gradient wrt the transformer input x_0 ([T, d] bf16): the gradients of the parameters that produced x_0 - the text embedding
         (one-hot GEMM; `onehot` is written by the backward list) and every native type's latent_to_model weight and bias"""
         md, T, d = self.md, self.T, self.md.dim
         gp, lib = self.ps.grad_ptr, capi.lib()
-        self._tn(L, T, md.vocab, d, A=self.onehot, lda=md.vp, a_cols=md.vp, B=dx0, ldb=d, b_cols=d, C=gp('text_embed.weight'), ldc=d)
+        tr = lambda name: name not in self._frozen
+        if tr('text_embed.weight'):
+            self._tn(L, T, md.vocab, d, A=self.onehot, lda=md.vp, a_cols=md.vp, B=dx0, ldb=d, b_cols=d, C=gp('text_embed.weight'), ldc=d)
         for t, r in self.R.items():
             dl = md.dim_latents[t]; dlp = pad_to(dl, 64); lt = self.lat[t]
             if dl == d or t in self.ext:
                 continue                                   # Identity latent_to_model / the user's encoder: no parameters here (`dx0` rows go back through autograd)
-            self._tn(L, r, d, dl, A=dx0, lda=d, a_cols=d, a_rowmap=self.row_gat[t], B=lt['xt'], ldb=dlp, b_cols=dlp,
-                     C=gp(f'latent_to_model_projs.{t}.weight'), ldc=dl)
+            if tr(f'latent_to_model_projs.{t}.weight'):
+                self._tn(L, r, d, dl, A=dx0, lda=d, a_cols=d, a_rowmap=self.row_gat[t], B=lt['xt'], ldb=dlp, b_cols=dlp,
+                         C=gp(f'latent_to_model_projs.{t}.weight'), ldc=dl)
+            if not tr(f'latent_to_model_projs.{t}.bias'):
+                continue
             cs = [dx0.data_ptr(), d, int(self.noise_args[t].R), d, None, self.row_tok[t].data_ptr(), gp(f'latent_to_model_projs.{t}.bias')]      # (mutable: the row count follows the step)
             self._rows_dep[t].append((cs, 2))
             L.append((lib.tfx_colsum_bf16, cs))
+
+    # ------------------------------------------------------------------------------------ frozen parameters
+    # what a backward list owns: one set of these per frozen set (select_frozen)
+    _BWD_STATE = ('bwd', 'bwd_cuts', 'bwd_end', 'tn_tables', 'clean_bwd', 'tap_final', 'tap0', '_pull_args', '_src_tab', 'ar_tail')
+    _BWD_SETS = 4               # backward lists kept per plan beside the one with nothing frozen
+
+    def select_frozen(self, frozen: frozenset):
+        """make the backward list of the frozen set `frozen` (names of `ParamStore.params` with `requires_grad` False) the plan's current one.  A list
+        is built on the first use of its set and kept under it - `_BWD_SETS` of them, the least recently used goes first; the list with nothing frozen
+        is the one the constructor built and always stays.  Buffers are shared: the lists differ in what they launch and where it is written."""
+        if frozen == self._frozen:
+            return
+        sets = self._bwd_sets
+        st = sets.pop(frozen, None)
+        if st is None:
+            while len(sets) > self._BWD_SETS:
+                sets.pop(next(k for k in sets if k))
+            self._frozen = frozen
+            self.bwd, self.bwd_cuts, self.tn_tables, self.tap0 = LaunchList(), [], [], None
+            self._build_backward()
+            st = {k: getattr(self, k) for k in self._BWD_STATE}
+            # what the loaded batch structure set in the args of the lists that existed then (a caller that meets the same structure again does not reload it)
+            if self.cos_tab is not None:
+                self.set_rope_tables(self.cos_tab, self.sin_tab)
+            for a in self._seg_args:
+                a.n_seg = self._n_seg
+        sets[frozen] = st                                               # (re-)insert at the most recent position
+        self._frozen = frozen
+        for k, v in st.items():
+            setattr(self, k, v)
+
+    def _time_cond_trains(self):
+        return not {'transformer.to_time_cond.1.weight', 'transformer.to_time_cond.1.bias'} <= self._frozen
+
+    def _lowest_consumer(self):
+        """where the data-gradient chain may stop for the current frozen set when nothing else consumes it: 'x0' (it runs to the transformer input), the
+        index of the lowest layer with a trainable parameter, 'norm' (the final norm's gain), 'heads' (only output projections train) or 'none'.
+        Second value: the list index that prefix ends at, None = the whole list (filled in by _build_backward as it passes the place)."""
+        fz, md = self._frozen, self.md
+        if not fz:
+            return 'x0', None
+        train = [n for n in self.ps.params if n not in fz]
+        native = [t for t in self.R if t not in self.ext]
+        x0 = 'text_embed.weight' in train or any(f'latent_to_model_projs.{t}.{k}' in train for t in native for k in ('weight', 'bias'))
+        # (the pull-form AttentionResidual backward forms d pseudo_queries / d norm_keys.gamma of layer j from every hidden 0 .. j + 1: what the launches
+        #  below the stop would have added comes from `ar_tail`)
+        if x0 or (self.I > 0 and self._time_cond_trains()):
+            return 'x0', None
+        layers = [int(n.split('.')[2]) for n in train if n.startswith('transformer.layers.') and not (self.I == 0 and ('.to_film.' in n or '.to_ada_ln_zero.' in n))]
+        if layers:
+            return min(layers), None
+        if 'transformer.norm.gamma' in train:
+            return 'norm', None
+        if 'to_text_logits.weight' in train or any(f'model_to_latent_projs.{t}.weight' in train for t in native):
+            return 'heads', None
+        return 'none', None
+
+    def _adaln_runs(self, lo, hi):
+        """table columns of layers lo .. hi - 1 whose to_film / to_ada_ln_zero weight (first list) or bias (second) trains, as [first column, columns] runs
+        of adjacent columns.  Column c of the AdaLN tables is row c of the [nt3, 4 d] weight block and element c of the bias block (params.param_specs)."""
+        d, runs = self.md.dim, ([], [])
+        for j in range(lo, hi):
+            for w in (1, 2):
+                c = (j * 2 + w - 1) * 3 * d
+                for nm, c0, nc in (('to_film', c, 2 * d), ('to_ada_ln_zero', c + 2 * d, d)):
+                    for r, kind in zip(runs, ('weight', 'bias')):
+                        if f'transformer.layers.{j}.{w}.{nm}.{kind}' in self._frozen:
+                            continue
+                        if r and r[-1][0] + r[-1][1] == c0:
+                            r[-1][1] += nc
+                        else:
+                            r.append([c0, nc])
+        return runs
+
+    def _frozen_attn_group(self, grp, p):
+        """the attention wrapper's weight-gradient products [to_out, to_qk | to_v | to_gates] under a frozen set: a frozen to_out leaves; the fused
+        projection keeps the rows of its trainable members through the product's `rowmap` (-1 = the row is not written), or leaves with all of them"""
+        md, fz = self.md, self._frozen
+        out = [grp[0]] if f'{p}.1.fn.to_out.1.weight' not in fz else []
+        hd = md.hd
+        parts = [('to_qk', 0, 2 * hd), ('to_v', 2 * hd, 3 * hd)] + ([('to_gates', 3 * hd, 3 * hd + md.heads)] if md.gates else [])
+        dead = [(a, b) for nm, a, b in parts if f'{p}.1.fn.{nm}.0.weight' in fz]
+        if len(dead) == len(parts):
+            return out
+        if dead:
+            from .params import head_phys_to_ref_rows
+            key = 'heads_fz' + ''.join(str(a) + '_' for a, _ in dead)
+            rows = head_phys_to_ref_rows(md.heads, md.dim_head, md.gates).copy()       # (dim_head 64: the identity over the md.nq rows)
+            for a, b in dead:
+                rows[(rows >= a) & (rows < b)] = -1
+            N, K, kw = grp[1]
+            grp = [grp[0], (N, K, dict(kw, rowmap=self.ps._map(key, rows)))]
+        return out + [grp[1]]
 
     # ------------------------------------------------------------------------------------ hidden taps
     def set_taps(self, grads: dict, n_true: int):
@@ -1167,7 +1355,16 @@ class Plan:
     def run_bwd(self, stream, lo=0, hi=None):
         """replay bwd[lo:hi]; a tap at the final norm's output adds its gradient to dembed at its place in the list, a tap at x_0 runs its
         weight-gradient launches behind the list"""
-        hi = len(self.bwd) if hi is None else hi
+        # a frozen set may end the list early (`bwd_end`: nothing below trains) - unless this step has another consumer of the data gradient: rows that
+        # go back to PyTorch (`rows_in`) or a hidden tap
+        whole = self.bwd_end is None or bool(self.taps) or self.rows_in
+        end = len(self.bwd) if whole else self.bwd_end
+        want = len(self.bwd) if hi is None else hi
+        hi = min(want, end)
+        if not whole and self.ar_tail is not None and lo < end <= want:      # the call that reaches the stop also runs what belongs behind it
+            Plan.run(self.bwd, stream, lo, hi, graph='auto')
+            Plan.run(self.ar_tail, stream)
+            return
         taps = self.taps
         pos = self.tap_final
         if self.md.depth + 1 in taps and lo <= pos < hi:

@@ -179,6 +179,10 @@ class FusedAdam(torch.optim.Optimizer):
     L2 form (g += wd p).  One group with the L2 form is the launch FusedAdam always made (`tfx_adam_step`); anything else goes through
     `tfx_adam_step_groups` with `group_ranges()` as a device table: one launch either way, one step count, one clip coefficient over everything.
 
+    Frozen parameters (`p.requires_grad_(False)` on views into the flat buffer; groups may hold them, a group of only frozen parameters is legal): their
+    element ranges (`frozen_ranges()`) join whatever another rule owns in the launch's `skip` table, re-read at every step - value, moments and weight
+    decay leave them alone bit for bit; their gradient segments are zero (engine), so the clip norm is `clip_grad_norm_`'s over the trainable parameters.
+
     `deterministic_norm` (class default False, True in FusedMuon; may be set on an instance): take the clip norm as a fixed-order sum (`tfx_sumsq_det`)
     instead of `tfx_sumsq`'s atomic one, whose last bits - and with them the clip coefficient of every element - change from run to run.  False is the
     step FusedAdam always took."""
@@ -425,7 +429,8 @@ class FusedAdam(torch.optim.Optimizer):
                 g.mul_(coef)
             self._sync_ext_opt()
             self.ext_opt.step()
-        skip, nskip = self._step_other_rules(ps, stream, max_norm, gscale)
+        self._step_other_rules(ps, stream, max_norm, gscale)
+        skip, nskip = self._skip_table(ps)
         groups = self._adam_groups()
         lr, beta1, beta2, eps, wd, decoupled = self._group_scalars(groups[0])
         common = dict(p=ps.flat, g=ps.grad, m=self.m, v=self.v, n=ps.numel, lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=wd, max_norm=max_norm,
@@ -450,9 +455,47 @@ class FusedAdam(torch.optim.Optimizer):
         capi.call(entry, capi.make_args(args, **fields, **common), stream)
 
     def _step_other_rules(self, ps, stream, max_norm, gscale):
-        """hook of subclasses that update part of the flat buffer by another rule, between the clip norm and the Adam launch: returns the device
-        table of element ranges Adam then leaves alone and its length (tfx_adam_args.skip / nskip)"""
-        return None, 0
+        """hook of subclasses that update part of the flat buffer by another rule, between the clip norm and the Adam launch; what they own there
+        they name in `_other_rule_ranges`"""
+
+    def _other_rule_ranges(self):
+        """hook of subclasses: sorted, disjoint [start, end) element ranges (multiples of 4) another rule owns - Adam leaves them alone"""
+        return []
+
+    def frozen_ranges(self):
+        """sorted, merged [start, end) element ranges of the flat buffer that belong to parameters with `requires_grad` False (multiples of 4: a
+        segment's padding belongs to it).  No rule touches them: value, `exp_avg` / `exp_avg_sq`, Muon momentum and weight decay all stay, bit for bit."""
+        return self.model.store.frozen_ranges()
+
+    @staticmethod
+    def merge_ranges(*lists):
+        """the union of sorted range lists as one sorted list of disjoint [start, end) ranges (touching ranges merge)"""
+        out = []
+        for a, b in sorted(r for l in lists for r in l):
+            if out and out[-1][1] >= a:
+                out[-1][1] = max(out[-1][1], b)
+            else:
+                out.append([a, b])
+        return [tuple(r) for r in out]
+
+    def skip_table(self):
+        """host form of tfx_adam_args.skip: what another rule owns merged with `frozen_ranges()`"""
+        return self.merge_ranges(self._other_rule_ranges(), self.frozen_ranges())
+
+    def _skip_table(self, ps):
+        """the device skip table of the Adam launch and its length (None, 0 when nothing is skipped: the launch FusedAdam always made); rebuilt when the
+        flat buffer moves or the frozen set changes"""
+        key = (ps.flat.data_ptr(), str(ps.flat.device), ps.frozen_names(), self._skip_key())
+        if self._skip_tab is None or self._skip_tab[0] != key:
+            host = self.skip_table()
+            dev = torch.tensor(host, dtype=torch.int64, device=ps.flat.device).reshape(-1) if host else None
+            self._skip_tab = (key, dev, len(host))
+        return self._skip_tab[1], self._skip_tab[2]
+
+    _skip_tab = None
+
+    def _skip_key(self):
+        return None
 
     def _ensure_state(self, ps):
         """the moments and the clip norm's scalar, on the flat buffer's device (moments that exist move with it: a loaded state is not lost)"""
@@ -788,6 +831,18 @@ class FusedMuon(FusedAdam):
         """kernel launches of one step's optimizer share (clip norm, Muon chain, Adam) - independent of the number of matrices"""
         return capi.lib().tfx_muon_step_launches(int(self.ns_steps), len(self.muon_params))
 
+    def _active_segments(self):
+        """`muon_segments()` without the frozen matrices: those leave the Muon tables - no orthogonalisation, no apply, momentum untouched"""
+        ps = self.model.store
+        frozen = {ps.offsets[n][0] for n in ps.frozen_names()}
+        return [s for s in self.muon_segments() if s[0] not in frozen]
+
+    def _other_rule_ranges(self):
+        return self.adam_skip_table()
+
+    def _skip_key(self):
+        return tuple(id(p) for p in self.muon_params)
+
     def skip_ranges(self):
         """sorted [start, end) element ranges of the flat buffer that Muon owns and Adam skips (adjacent matrices merged)"""
         out = []
@@ -815,18 +870,16 @@ class FusedMuon(FusedAdam):
     def host_tables(self):
         """the step's tables as host data (no device needed): matrix descriptors and the problems of the grouped products, with workspace OFFSETS
         (elements) where the device tables carry pointers"""
-        return _muon_host_tables(self.muon_segments(), self.adjust_lr_fn)
+        return _muon_host_tables(self._active_segments(), self.adjust_lr_fn)
 
     def _tables(self, ps):
         # (the parameters are views into `flat`: they move only with it - `reflatten` - and a re-assigned `.data` is copied back and re-pointed by
         #  the forward's `params_version()`; the fused kernels read the flat buffer either way, as FusedAdam's do)
-        key = (ps.flat.data_ptr(), str(ps.flat.device), self.adjust_lr_fn)
+        key = (ps.flat.data_ptr(), str(ps.flat.device), self.adjust_lr_fn, ps.frozen_names())
         if self._tab is None or self._tab.key != key:
-            self._tab = _muon_device_tables(self.host_tables(), ps.flat.device)
-            self._tab.key = key
-            skip = self.adam_skip_table()
-            self._tab.nskip = len(skip)
-            self._tab.skip = torch.tensor(skip, dtype=torch.int64, device=ps.flat.device).reshape(-1)
+            H = self.host_tables()
+            self._tab = _muon_device_tables(H, ps.flat.device) if H['mats'] else _MuonTables()      # (every matrix frozen: no Muon launch at all)
+            self._tab.key, self._tab.nmat = key, len(H['mats'])
         return self._tab
 
     def momentum_buffer(self, p):
@@ -840,12 +893,13 @@ class FusedMuon(FusedAdam):
     def _step_other_rules(self, ps, stream, max_norm, gscale):
         ns = int(self.ns_steps)
         T = self._tables(ps)
+        if not T.nmat:
+            return
         _muon_orthogonalize(T, ps.grad, self.m, self.sumsq, max_norm, gscale, self.momentum, self.nesterov, self.muon_eps, self.ns_coefficients, ns, stream)
         lr, wd = float(self.muon_lr), float(self.muon_weight_decay)
         app = capi.make_args('tfx_muon_apply_args', mats=T.mats, blk_mat=T.blk_mat, nmat=T.nmat, nblk=T.nblk, p=ps.flat, ws=T.wsx[ns & 1],
                              lr=lr, decay=1. - lr * wd)
         capi.call('tfx_muon_apply', app, stream)
-        return T.skip, T.nskip
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------

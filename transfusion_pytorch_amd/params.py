@@ -244,6 +244,8 @@ class ParamStore:
         self._maps = {}
         self._jobs, self._job_table = [], None
         self._exp_ptrs = None
+        self._frozen_cache = (None, frozenset())
+        self._grad_written = set()              # segments of the gradient buffer a backward may have written since the last whole-buffer fill
         self.device = torch.device('cpu')
 
     # ------------------------------------------------------------------ flat <-> views
@@ -274,6 +276,7 @@ class ParamStore:
                 self.params[name].grad = None
         self.flat = flat
         self.grad = torch.zeros(self.numel, device=device) if device.type == 'cuda' else None
+        self._grad_written = set()
         self.device = device
         self.shadows = {}
         self._shadow_version = None
@@ -309,16 +312,50 @@ class ParamStore:
             ver += prm._version
         return ver
 
-    def ensure_grad_views(self):
-        """(re)attach `.grad` views; zero the segments whose grad was None (fresh accumulation)."""
-        fresh = [n for n, p in self.params.items() if p.grad is None]
-        if len(fresh) == len(self.params):
-            self.grad.zero_()
+    def frozen_names(self):
+        """names of the parameters with `requires_grad` False, read at every training forward next to the version walk: one tuple of flags, the
+        frozenset of names cached per tuple (freezing is rare, the walk is per step)"""
+        flags = tuple(p.requires_grad for p in self.params.values())
+        if self._frozen_cache[0] != flags:
+            self._frozen_cache = (flags, frozenset(n for n, f in zip(self.params, flags) if not f))
+        return self._frozen_cache[1]
+
+    def frozen_ranges(self, frozen=None):
+        """sorted, merged [start, end) element ranges of the flat buffers that belong to frozen parameters; a segment's padding (to a multiple of 4
+        elements) belongs to it, so every bound is a multiple of 4"""
+        frozen = self.frozen_names() if frozen is None else frozen
+        out = []
+        for name, shape in self.specs:
+            if name not in frozen:
+                continue
+            a = self.offsets[name][0]
+            b = a + pad_to(int(np.prod(shape)), 4)
+            if out and out[-1][1] == a:
+                out[-1][1] = b
+            else:
+                out.append([a, b])
+        return [tuple(r) for r in out]
+
+    def ensure_grad_views(self, frozen=frozenset()):
+        """(re)attach `.grad` views; zero the segments whose grad was None (fresh accumulation).  Parameters of `frozen` get no view: their `.grad`
+        is None after the backward and their segment reads all-zero bits - the backward list of that set writes nothing there, and what an earlier
+        step with the parameter trainable left is cleared here."""
+        live = [(n, p) for n, p in self.params.items() if n not in frozen]
+        fresh = [n for n, p in live if p.grad is None]
+        if len(fresh) == len(live):
+            self.grad.zero_()                                 # every trainable segment starts over: one fill covers the frozen ones too
+            self._grad_written = set()
         else:
             for n in fresh:
                 self.grad_view(n).zero_()
+            for n in frozen & self._grad_written:
+                self.grad_view(n).zero_()
+            self._grad_written -= frozen
+        for n in frozen:
+            self.params[n].grad = None
         for n in fresh:
             self.params[n].grad = self.grad_view(n)
+        self._grad_written.update(n for n, _ in live)
 
     # ------------------------------------------------------------------ shadows
     def _map(self, key, arr):

@@ -254,6 +254,7 @@ class _NativeLoss(torch.autograd.Function):
             plan.set_taps(taps, ctx.n_true)
             if grad_loss is None:                         # only the hiddens were used: the loss seeds carry nothing
                 grad_loss = torch.zeros((), device=plan.dembed.device)
+        plan.rows_in = bool(spec['in'])                   # rows of d loss / d x_0 go back to PyTorch: the chain runs to x_0 whatever is frozen
         model._native_backward(grad_loss, ctx.step_id)
         back = [plan.dx0.index_select(0, plan.row_tok[t].long().clamp(min=0)).float() for _, t in spec['in']]
         if spec.get('hid') and 0 in plan.taps:            # a tap at x_0 reaches the rows PyTorch produced directly
@@ -658,6 +659,9 @@ class Transfusion(nn.Module):
             while self._plans and sum(p.nbytes for p in self._plans.values()) + plan.nbytes > budget:
                 self._plans.pop(next(iter(self._plans)))
         self._plans[key] = plan                                      # (re-)insert at the most recent position
+        if training:
+            # `p.requires_grad_(False)` on native parameters: the backward list of the current frozen set (built on first use, a few kept per plan)
+            plan.select_frozen(self.store.frozen_names())
         return plan
 
     def _structure(self, key, build):
@@ -1621,7 +1625,9 @@ class Transfusion(nn.Module):
                                'forward (call forward again; retain_graph is not supported)')
         self._consumed = step_id
         ps = self.store
-        ps.ensure_grad_views()
+        ps.ensure_grad_views(plan._frozen)                    # (the frozen set the forward built this step's backward list for)
+        if plan.bwd_end == 0 and not plan.taps and not plan.rows_in and not (self.md.model_output_clean and plan.clean_mode == 'model' and len(plan.clean_bwd)):
+            return                                            # every native parameter is frozen and nothing else consumes the data gradient: no launch
         go = grad_out.reshape(()).to(torch.float32)           # d(total)/d(loss): scales the loss seeds (everything downstream is linear)
         if self._bwd_scale is not None:
             go = go * self._bwd_scale                         # forward_text: 1 / #valid labels, known on the device only
