@@ -717,6 +717,54 @@ int tfx_allreduce_init(int32_t rank, int32_t world, const void* unique_id128);
 int tfx_allreduce_run(float* buf, int64_t count, void* stream);
 int tfx_allreduce_destroy(void);
 
+/* ---- LoRA adapters (transfusion_pytorch_amd/lora.py; csrc/lora.hip) ----------------------------------------
+ * An adapted nn.Linear weight reads W_eff = W + s B A (A [r, d_in], B [d_out, r], fp32 parameters outside the flat buffer).
+ *
+ * tfx_lora_merge: Weff[n][k] = W[n][k] + s sum_j B[n][j] A[j][k], fp32 from fp32 operands, j ascending in one fma chain per element (no atomics,
+ * no split): bit-identical from run to run.  An element whose low-rank sum is exactly zero (B = 0, r = 0) receives the bits of W.  r == 0 (A, B may
+ * be NULL) is a plain copy.  Weff may not alias W.  The bf16 shadow casts of an adapted matrix then read Weff: one rounding, as for a trained master. */
+typedef struct {
+  const float* W; int32_t ldw;
+  const float* B; int32_t ldb;          /* [N, r] */
+  const float* A; int32_t lda;          /* [r, K] */
+  float* Weff; int32_t ldo;
+  int32_t N, K, r;
+  float s;
+} tfx_lora_merge_args;
+int tfx_lora_merge(const tfx_lora_merge_args* a, void* stream);
+
+/* tfx_lora_down: P[M, r_pad] = Q[M, K] . R[r_pad, K]^T, bf16 operands, fp32 accumulation on the matrix cores, bf16 P.  r_pad = 32 or 64 (rows of R past the
+ * adapter's rank are zeros); K % 8 == 0, ldq % 8 == 0, ldr % 8 == 0, 16-byte aligned bases (columns from K on are never read); any ldp >= r_pad.  Q is read once:
+ * a block owns 128 rows of Q and all of R's rows. */
+typedef struct {
+  const tfx_bf16* Q; int32_t ldq;
+  const tfx_bf16* R; int32_t ldr;
+  tfx_bf16* P; int32_t ldp;
+  int32_t M, K, r_pad;
+} tfx_lora_down_args;
+int tfx_lora_down(const tfx_lora_down_args* a, void* stream);
+
+/* tfx_lora_grad: G[j][k] (+)= alpha sum_m P[m][j] Q[m][k] for j < r, k < K: the skinny weight-gradient product of an adapter (P = the down projection of the
+ * other operand, r <= r_pad in {32, 64} columns).  The M rows are cut into `chunks` runs (multiples of 64 rows); a block forms one (128-column, chunk) partial on
+ * the matrix cores and writes it with plain stores into `partials` ([chunks, r_pad, ceil(K / 128) 128] fp32, owned by the caller: tfx_lora_grad_plan gives its
+ * size); a second kernel adds the chunks in one fixed order (eight interleaved ascending chains, closed as a fixed tree), applies alpha and stores (accumulate == 0) or adds to (accumulate != 0) G.  No atomics: the result
+ * is bit-identical from run to run.  The element (j, k) lands at G[j * g_row_stride + c * g_col_stride], c = colmap ? colmap[k] : k, columns with c < 0 are
+ * dropped (physical operand layout -> the parameter's own order, and the transposed form dB [d_out, r] through g_row_stride = 1, g_col_stride = r).
+ * K % 8 == 0, ldq % 8 == 0, 16-byte aligned Q; any ldp >= r_pad. */
+typedef struct {
+  const tfx_bf16* P; int32_t ldp;
+  const tfx_bf16* Q; int32_t ldq;
+  float* G; int64_t g_row_stride, g_col_stride;
+  const int32_t* colmap;
+  float* partials;
+  int32_t M, K, r, r_pad;
+  int32_t accumulate;
+  float alpha;
+} tfx_lora_grad_args;
+int tfx_lora_grad(const tfx_lora_grad_args* a, void* stream);
+/* what tfx_lora_grad would launch, without launching (host logic only): row chunks, blocks of the product kernel, floats of `partials` it needs */
+int tfx_lora_grad_plan(const tfx_lora_grad_args* a, int32_t* chunks, int32_t* grid, int64_t* partial_floats);
+
 /* ---- launch lists ------------------------------------------------------------------------------
  * The step is a STATIC list of launches over persistent buffers (engine.Plan), so the host replays it with ONE call instead of one
  * FFI round trip per kernel: `tfx_run_list` walks `n` items in order on `stream` (or the side stream, per item) and stops at the first non-zero return code
@@ -728,7 +776,7 @@ enum { TFX_OP_GEMM_NT = 0, TFX_OP_GEMM_TN = 1, TFX_OP_ATTN_FWD = 2, TFX_OP_ATTN_
        TFX_OP_ATTNRES_BWD = 11, TFX_OP_RMSNORM_FWD = 12, TFX_OP_RMSNORM_BWD = 13, TFX_OP_EMBED_FWD = 14, TFX_OP_EMBED_BWD = 15,
        TFX_OP_NOISE_MIX = 16, TFX_OP_FOURIER = 17, TFX_OP_CE_FWD_BWD = 18, TFX_OP_MSE_FWD_BWD = 19, TFX_OP_CAST_ROWS = 20, TFX_OP_CAST_ROWS_T = 21,
        TFX_OP_ADAM_STEP = 22, TFX_OP_DECODE_ATTN = 23, TFX_OP_LASER_V_FWD = 24, TFX_OP_LASER_V_BWD = 25, TFX_OP_COSINE_FWD_BWD = 26,
-       TFX_OP_ADAM_ATAN2_STEP = 27,
+       TFX_OP_ADAM_ATAN2_STEP = 27, TFX_OP_LORA_MERGE = 28, TFX_OP_LORA_DOWN = 29, TFX_OP_LORA_GRAD = 30,
        /* positional entry points (args = tfx_raw_args) */
        TFX_OP_OUTPUT_TO_FLOW = 32, TFX_OP_GATHER_F32 = 33, TFX_OP_ONEHOT_BF16 = 34, TFX_OP_SCATTER_ROWS_BF16 = 35, TFX_OP_F32_TO_BF16 = 36,
        TFX_OP_SILU_BWD = 37, TFX_OP_COLSUM_BF16 = 38, TFX_OP_COLSUM_F32 = 39, TFX_OP_ADD_BF16 = 40, TFX_OP_SCALE_BF16_DEV = 41, TFX_OP_CAST_BLOCK_BF16 = 42, TFX_OP_SCALE_BF16_COPY = 43, TFX_OP_ADALN_POST_PRE_FWD = 44, TFX_OP_LAYER_END_FWD = 45,

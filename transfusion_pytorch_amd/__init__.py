@@ -18,6 +18,7 @@ from .transfusion import (
 from .ema import EMA
 from .self_flow import SelfMaskedRepTraining, default_rep_loss_fn
 from .optim import FusedAdamAtan2, FusedMuonAdamAtan2, AdamAtan2
+from .lora import add_lora_, lora_parameters, merge_lora_, remove_lora_
 
 __all__ = ['Transfusion', 'Transformer', 'LossBreakdown', 'print_modality_sample', 'create_dataloader', 'EMA', 'SelfMaskedRepTraining', 'default_rep_loss_fn',
-           'FusedAdamAtan2', 'FusedMuonAdamAtan2', 'AdamAtan2']
+           'FusedAdamAtan2', 'FusedMuonAdamAtan2', 'AdamAtan2', 'add_lora_', 'lora_parameters', 'merge_lora_', 'remove_lora_']

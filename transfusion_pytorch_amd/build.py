@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIB = os.path.join(LIBDIR, 'libtfx_hip.so')
-SOURCES = ['gemm.hip', 'attention.hip', 'tokenwise.hip', 'decode.hip', 'collective.hip', 'muon.hip', 'runner.hip']
+SOURCES = ['gemm.hip', 'attention.hip', 'tokenwise.hip', 'decode.hip', 'collective.hip', 'muon.hip', 'lora.hip', 'runner.hip']
 HEADERS = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(('.h', '.inc'))] + [os.path.join(os.path.dirname(HERE), 'include', 'tfx.h')]   # incl. the generated asm loops
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-munsafe-fp-atomics', '-Wno-unused-result'] + os.environ.get('TFX_HIPCC_EXTRA', '').split()   # e.g. -DTFX_PP_TIMING (tools/pp_timing.py)
 

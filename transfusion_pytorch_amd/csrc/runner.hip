@@ -41,6 +41,9 @@ inline int run_one(const tfx_launch& l, void* s) {
     case TFX_OP_LASER_V_BWD:      return tfx_laser_v_bwd(static_cast<const tfx_laser_v_args*>(a), s);
     case TFX_OP_COSINE_FWD_BWD:   return tfx_cosine_fwd_bwd(static_cast<const tfx_cosine_args*>(a), s);
     case TFX_OP_ADAM_ATAN2_STEP:  return tfx_adam_atan2_step(static_cast<const tfx_adam_atan2_args*>(a), s);
+    case TFX_OP_LORA_MERGE:       return tfx_lora_merge(static_cast<const tfx_lora_merge_args*>(a), s);
+    case TFX_OP_LORA_DOWN:        return tfx_lora_down(static_cast<const tfx_lora_down_args*>(a), s);
+    case TFX_OP_LORA_GRAD:        return tfx_lora_grad(static_cast<const tfx_lora_grad_args*>(a), s);
     // positional entry points: pointers p0.., integers i0.., floats f0 in declaration order
     case TFX_OP_OUTPUT_TO_FLOW:
       return tfx_output_to_flow((float*)r->p0, (const float*)r->p1, (const float*)r->p2, (const int32_t*)r->p3, (const float*)r->p4,
@@ -224,6 +227,9 @@ inline size_t struct_bytes(int op) {
     case TFX_OP_ADAM_ATAN2_STEP: return sizeof(tfx_adam_atan2_args);
     case TFX_OP_LASER_V_FWD: case TFX_OP_LASER_V_BWD: return sizeof(tfx_laser_v_args);
     case TFX_OP_COSINE_FWD_BWD: return sizeof(tfx_cosine_args);
+    case TFX_OP_LORA_MERGE: return sizeof(tfx_lora_merge_args);
+    case TFX_OP_LORA_DOWN: return sizeof(tfx_lora_down_args);
+    case TFX_OP_LORA_GRAD: return sizeof(tfx_lora_grad_args);
     default: return op >= TFX_OP_OUTPUT_TO_FLOW ? sizeof(tfx_raw_args) : 0;
   }
 }

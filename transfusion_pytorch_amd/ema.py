@@ -17,6 +17,8 @@ from . import capi
 class EMA(nn.Module):
     def __init__(self, model, beta=0.9999, update_after_step=100, update_every=10, inv_gamma=1.0, power=2 / 3, min_value=0.0,
                  forward_method_names=()):
+        from .lora import require_no_lora
+        require_no_lora(model, 'EMA(...)')            # the copy and the update run over the flat buffer: adapters would be left out
         super().__init__()
         self.beta, self.update_after_step, self.update_every = beta, update_after_step, update_every
         self.inv_gamma, self.power, self.min_value = inv_gamma, power, min_value

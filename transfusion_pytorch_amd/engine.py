@@ -346,6 +346,7 @@ class Plan:
             self.gsink = z(64, dtype=torch.float32)          # where a frozen q_norm / k_norm gain's gradient goes (the attention epilogues take no NULL for one gain alone)
             self.rows_in = False                             # this step hands rows of d loss / d x_0 back to PyTorch (user encoders, positional embeddings): set by the model
             self._frozen, self._bwd_sets, self._src_tab = frozenset(), {}, None
+            self._lora, self._lora_ws = (), {}               # LoRA adapters that train (ParamStore.lora.key(), select_frozen) and the workspace their launches share
             self._build_backward()
             self._bwd_sets[self._frozen] = {k: getattr(self, k) for k in self._BWD_STATE}
 
@@ -1031,6 +1032,9 @@ class Plan:
                 pending += ff_grp
             elif ff_grp:
                 self._tn_group(L, T, ff_grp, side=side)
+            # LoRA adapters of the feed-forward matrices: where their weight-gradient products stand or would stand (dy_f, d[a|g] and the saved inputs are final)
+            self._lora_launches(L, i, 'net.3', self.hm[i], dip, dy_f, d)
+            self._lora_launches(L, i, 'net.0', self.uf[i], d, dag, 2 * dip)
             self._nt(L, algo_k=2 * di, A=dag, lda=2 * dip, B=S[f'ff1_t{i}'], ldb=2 * dip, M=T, N=d, K=2 * dip, epi=E['TFX_EPI_BF16'], C=self.du, ldc=d)
             a_pref = capi.make_args('tfx_adaln_pre_args', T=T, d=d, x=self.xb[i], tok_inst=self.tok_inst, table=tf, ld_table=nt3,
                                     gamma_text=pp(f'{p}.2.layernorm_gamma'), mean=_p(self.stats, 2, i), rstd=_p(self.stats, 3, i), du=self.du, dx=G,
@@ -1081,6 +1085,10 @@ class Plan:
                     dx_add=self.dskip[i] if (pull and i in pushed) else None)
             self._hbm(L, 4 + (1 if (pull and i in pushed) else 0))          # du, x in; residual gradient in / out (+ the U-Net skip's share)
             self._seg_args.append(L[-1][1])
+            # LoRA adapters of the attention matrices (dy_a and d[q|k|v|gates] are final; to_v reads its columns of the fused gradient)
+            self._lora_launches(L, i, 'to_out', self.og[i], hd, dy_a, d)
+            self._lora_launches(L, i, 'to_qk', self.ua[i], d, dqkvg, ldq)
+            self._lora_launches(L, i, 'to_v', self.ua[i], d, dqkvg.data_ptr() + 2 * 2 * hd, ldq)
             # weight gradients of the attention wrapper (dy_a, d[q|k|v|gates] and G = dH[i+1] are final) on the side stream
             per = -(-D // self.dp_groups) if self.dp_groups > 0 else D
             launch = bool(run) and run_low[i] == i             # lowest layer of a run: runs count down from the top of an exchange group and end with it
@@ -1207,23 +1215,64 @@ class Plan:
             self._rows_dep[t].append((cs, 2))
             L.append((lib.tfx_colsum_bf16, cs))
 
+    # ------------------------------------------------------------------------------------ LoRA adapters
+    def _lora_launches(self, L, i, target, X, ldx, dY, ldy):
+        """gradients of the adapter on (layer i, target), if it trains (lora.py; tfx.h "LoRA adapters"): with X [T, K] and dY [T, N] the operands of the
+        matrix's weight-gradient product dW = dY^T X, in the kernels' physical layouts,
+            U  = X A_phys^T   [T, r_pad]      dB^T += s U^T  dY
+            dU = dY B_phys    [T, r_pad]      dA   += s dU^T X
+        (`tfx_lora_down`, `tfx_lora_grad`); the gradient stores map the physical columns back to the parameter's own order and accumulate into the
+        persistent buffers `.grad` views.  On the caller's stream: U, dU and the partial sums are one workspace for every adapter of the plan, and the
+        operands are rewritten by later layers of the same stream only."""
+        ls = self.ps.lora
+        if not self._lora or not ls:
+            return
+        a = ls.get(i, target)
+        if a is None or not any(k[1] == a.uid for k in self._lora):
+            return
+        T, ws = self.T, self._lora_ws
+        if not ws:
+            md = self.md
+            need = 0
+            for K in {md.dim, md.hdk, 2 * md.hdk, md.dip, 2 * md.dip}:
+                q = capi.make_args('tfx_lora_grad_args', M=T, K=K, r=64, r_pad=64, ldp=64, ldq=K)
+                fl = ctypes.c_int64(0)
+                capi.check(capi.lib().tfx_lora_grad_plan(ctypes.byref(q), None, None, ctypes.byref(fl)), 'tfx_lora_grad_plan')
+                need = max(need, fl.value)
+            ws['U'] = torch.zeros(T, 64, device=self.ps.device, dtype=BF16)
+            ws['dU'] = torch.zeros(T, 64, device=self.ps.device, dtype=BF16)
+            ws['part'] = torch.zeros(need, device=self.ps.device, dtype=torch.float32)
+            self.nbytes += 2 * T * 64 * 2 + need * 4
+        common = dict(M=T, r_pad=a.r_pad)
+        grad = dict(partials=ws['part'], r=a.r, accumulate=1, alpha=a.s, ldp=64, **common)
+        if a.B.requires_grad:
+            self._k(L, 'tfx_lora_down', 'tfx_lora_down_args', Q=X, ldq=ldx, R=a.A_phys, ldr=a.k_phys, P=ws['U'], ldp=64, K=a.k_phys, **common)
+            self._k(L, 'tfx_lora_grad', 'tfx_lora_grad_args', P=ws['U'], Q=dY, ldq=ldy, K=a.n_phys, G=a.gB, g_row_stride=1, g_col_stride=a.r,
+                    colmap=a.out_map, **grad)
+        if a.A.requires_grad:
+            self._k(L, 'tfx_lora_down', 'tfx_lora_down_args', Q=dY, ldq=ldy, R=a.BT_phys, ldr=a.n_phys, P=ws['dU'], ldp=64, K=a.n_phys, **common)
+            self._k(L, 'tfx_lora_grad', 'tfx_lora_grad_args', P=ws['dU'], Q=X, ldq=ldx, K=a.k_phys, G=a.gA, g_row_stride=a.d_in, g_col_stride=1,
+                    colmap=a.in_map, **grad)
+
     # ------------------------------------------------------------------------------------ frozen parameters
     # what a backward list owns: one set of these per frozen set (select_frozen)
     _BWD_STATE = ('bwd', 'bwd_cuts', 'bwd_end', 'tn_tables', 'clean_bwd', 'tap_final', 'tap0', '_pull_args', '_src_tab', 'ar_tail')
     _BWD_SETS = 4               # backward lists kept per plan beside the one with nothing frozen
 
-    def select_frozen(self, frozen: frozenset):
+    def select_frozen(self, frozen: frozenset, lora: tuple = ()):
         """make the backward list of the frozen set `frozen` (names of `ParamStore.params` with `requires_grad` False) the plan's current one.  A list
         is built on the first use of its set and kept under it - `_BWD_SETS` of them, the least recently used goes first; the list with nothing frozen
-        is the one the constructor built and always stays.  Buffers are shared: the lists differ in what they launch and where it is written."""
-        if frozen == self._frozen:
+        is the one the constructor built and always stays.  Buffers are shared: the lists differ in what they launch and where it is written.
+        `lora`: the adapted, trainable matrices (`LoraSet.key()`) - part of the key: their launches stand in the list (_lora_launches)."""
+        if frozen == self._frozen and lora == self._lora:
             return
         sets = self._bwd_sets
-        st = sets.pop(frozen, None)
+        key = (frozen, lora) if lora else frozen
+        st = sets.pop(key, None)
         if st is None:
             while len(sets) > self._BWD_SETS:
                 sets.pop(next(k for k in sets if k))
-            self._frozen = frozen
+            self._frozen, self._lora = frozen, lora
             self.bwd, self.bwd_cuts, self.tn_tables, self.tap0 = LaunchList(), [], [], None
             self._build_backward()
             st = {k: getattr(self, k) for k in self._BWD_STATE}
@@ -1232,8 +1281,8 @@ class Plan:
                 self.set_rope_tables(self.cos_tab, self.sin_tab)
             for a in self._seg_args:
                 a.n_seg = self._n_seg
-        sets[frozen] = st                                               # (re-)insert at the most recent position
-        self._frozen = frozen
+        sets[key] = st                                                  # (re-)insert at the most recent position
+        self._frozen, self._lora = frozen, lora
         for k, v in st.items():
             setattr(self, k, v)
 
@@ -1255,6 +1304,7 @@ class Plan:
         if x0 or (self.I > 0 and self._time_cond_trains()):
             return 'x0', None
         layers = [int(n.split('.')[2]) for n in train if n.startswith('transformer.layers.') and not (self.I == 0 and ('.to_film.' in n or '.to_ada_ln_zero.' in n))]
+        layers += [int(k[0].split('.')[2]) for k in self._lora]            # a layer with a trainable LoRA adapter consumes the data gradient
         if layers:
             return min(layers), None
         if 'transformer.norm.gamma' in train:

@@ -756,7 +756,10 @@ class FusedMuon(FusedAdam):
         muon = list(model.muon_parameters() if muon_params is None else muon_params)
         if not muon:
             raise ValueError('FusedMuon needs at least one matrix (use FusedAdam otherwise)')
+        lora = {id(p) for p in model.store.lora.parameters()} if getattr(getattr(model, 'store', None), 'lora', None) else set()
         for p in muon:
+            if id(p) in lora:
+                raise NotImplementedError('LoRA adapter parameters in a Muon group are not supported: they are stepped by the Adam share (external parameters)')
             if p.ndim != 2:
                 raise ValueError(f'Muon parameters must be 2-D matrices, got shape {tuple(p.shape)}')
         # the Adam share takes groups as FusedAdam does (the matrices leave whatever group lists them: `decay_groups(model, ...)` may be passed

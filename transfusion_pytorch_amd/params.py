@@ -246,6 +246,7 @@ class ParamStore:
         self._exp_ptrs = None
         self._frozen_cache = (None, frozenset())
         self._grad_written = set()              # segments of the gradient buffer a backward may have written since the last whole-buffer fill
+        self.lora = None                        # lora.LoraSet while adapters are attached (lora.add_lora_): parameters outside the flat buffer
         self.device = torch.device('cpu')
 
     # ------------------------------------------------------------------ flat <-> views
@@ -281,6 +282,8 @@ class ParamStore:
         self.shadows = {}
         self._shadow_version = None
         self._maps = {}
+        if self.lora:
+            self.lora.to(device)
 
     def mark_dirty(self):
         """the master buffer changed behind autograd's back (fused optimizer / EMA kernels): rebuild the bf16 shadows on next use, and move
@@ -310,6 +313,8 @@ class ParamStore:
                 prm.data = v
                 self._shadow_version = None
             ver += prm._version
+        if self.lora:                                                # an optimizer step or `p.copy_()` on an adapter refreshes the shadows too
+            ver += self.lora.version()
         return ver
 
     def frozen_names(self):
@@ -378,7 +383,7 @@ class ParamStore:
 
     def _launch_casts(self, stream):
         """all recorded shadow jobs in one tfx_cast_batch launch; the device job table is cached per flat-buffer address."""
-        key = (self.flat.data_ptr(), len(self._jobs))
+        key = (self.flat.data_ptr(), len(self._jobs), self.lora.epoch if self.lora else 0)      # (adapters re-point jobs at their W_eff scratches)
         if self._job_table is None or self._job_table[0] != key:
             J = capi.STRUCTS['tfx_cast_job']
             arr = (J * len(self._jobs))()
@@ -402,6 +407,10 @@ class ParamStore:
         d, hd, di, dip, D = md.dim, md.hd, md.di, md.dip, md.depth
         S, C = self._shadow, self._cast
         self._jobs = []
+        # LoRA adapters (lora.py): the casts of an adapted matrix read an fp32 scratch holding W_eff = W + s B A (tfx_lora_merge) instead of the master -
+        # the one rounding to bf16, the row maps, the transposed copies, the GEGLU order and the head padding below stay what they are
+        merged = self.lora.merged_sources(self, stream) if self.lora else {}
+        wp = lambda name: merged.get(name) or self.ptr(name)
         # AdaLN conditioning: one [nt3, 4d] matrix (+ transposed) for every layer / wrapper
         C(stream, self.ptr('transformer.layers.0.1.to_film.weight'), 4 * d, md.nt3, 4 * d, S('ada', md.nt3, 4 * d))
         C(stream, self.ptr('transformer.layers.0.1.to_film.weight'), 4 * d, md.nt3, 4 * d, S('ada_t', 4 * d, md.nt3), transpose=True, n_rows_logical=md.nt3)
@@ -417,15 +426,15 @@ class ParamStore:
                 C(stream, self.ptr(f'{p}.0.weight'), 2 * d, d, 2 * d, S(f'skip{i}', d, 2 * d))
                 C(stream, self.ptr(f'{p}.0.weight'), 2 * d, d, 2 * d, S(f'skip_t{i}', 2 * d, d), transpose=True, n_rows_logical=d)
             if dh == 64:
-                C(stream, self.ptr(f'{p}.1.fn.to_qk.0.weight'), d, md.nq, d, S(f'qkvg{i}', md.nq, d))
-                C(stream, self.ptr(f'{p}.1.fn.to_qk.0.weight'), d, md.nq, d, S(f'qkvg_t{i}', d, md.ldq), transpose=True, n_rows_logical=md.nq)
-                C(stream, self.ptr(f'{p}.1.fn.to_out.1.weight'), hd, d, hd, S(f'out{i}', d, hd))
-                C(stream, self.ptr(f'{p}.1.fn.to_out.1.weight'), hd, d, hd, S(f'out_t{i}', hd, d), transpose=True, n_rows_logical=d)
+                C(stream, wp(f'{p}.1.fn.to_qk.0.weight'), d, md.nq, d, S(f'qkvg{i}', md.nq, d))
+                C(stream, wp(f'{p}.1.fn.to_qk.0.weight'), d, md.nq, d, S(f'qkvg_t{i}', d, md.ldq), transpose=True, n_rows_logical=md.nq)
+                C(stream, wp(f'{p}.1.fn.to_out.1.weight'), hd, d, hd, S(f'out{i}', d, hd))
+                C(stream, wp(f'{p}.1.fn.to_out.1.weight'), hd, d, hd, S(f'out_t{i}', hd, d), transpose=True, n_rows_logical=d)
             else:             # dim_head < 64: every head is zero-padded to the kernels' 64 columns
                 hdk = md.hdk
-                C(stream, self.ptr(f'{p}.1.fn.to_qk.0.weight'), d, md.nq, d, S(f'qkvg{i}', md.nqk, d), rowmap=qmap)
-                C(stream, self.ptr(f'{p}.1.fn.to_qk.0.weight'), d, md.nq, d, S(f'qkvg_t{i}', d, md.ldq), rowmap=qmap, transpose=True, n_rows_logical=md.nqk)
-                wo = self.ptr(f'{p}.1.fn.to_out.1.weight')            # [d, heads * dh] seen as [(d * heads), dh] -> [(d * heads), 64]
+                C(stream, wp(f'{p}.1.fn.to_qk.0.weight'), d, md.nq, d, S(f'qkvg{i}', md.nqk, d), rowmap=qmap)
+                C(stream, wp(f'{p}.1.fn.to_qk.0.weight'), d, md.nq, d, S(f'qkvg_t{i}', d, md.ldq), rowmap=qmap, transpose=True, n_rows_logical=md.nqk)
+                wo = wp(f'{p}.1.fn.to_out.1.weight')            # [d, heads * dh] seen as [(d * heads), dh] -> [(d * heads), 64]
                 C(stream, wo, dh, d * md.heads, dh, S(f'out{i}', d, hdk).view(d * md.heads, 64))
                 ot = S(f'out_t{i}', hdk, d)
                 for h in range(md.heads):                            # head h: columns [h dh, (h+1) dh) of to_out -> rows [64 h, 64 h + dh)
@@ -435,10 +444,10 @@ class ParamStore:
                     if key not in self.shadows:
                         self.shadows[key] = torch.zeros(64, device=self.device)
                     capi.check(capi.lib().tfx_gather_f32(self.ptr(f'{p}.1.fn.{nm}_norm.gamma'), gam_map.data_ptr(), self.shadows[key].data_ptr(), 64, stream), 'gather_f32')
-            C(stream, self.ptr(f'{p}.2.fn.net.0.weight'), d, 2 * di, d, S(f'ff1{i}', 2 * dip, d), rowmap=gmap)
-            C(stream, self.ptr(f'{p}.2.fn.net.0.weight'), d, 2 * di, d, S(f'ff1_t{i}', d, 2 * dip), rowmap=gmap, transpose=True, n_rows_logical=2 * dip)
-            C(stream, self.ptr(f'{p}.2.fn.net.3.weight'), di, d, di, S(f'ff2{i}', d, dip))
-            C(stream, self.ptr(f'{p}.2.fn.net.3.weight'), di, d, di, S(f'ff2_t{i}', dip, d), transpose=True, n_rows_logical=d)
+            C(stream, wp(f'{p}.2.fn.net.0.weight'), d, 2 * di, d, S(f'ff1{i}', 2 * dip, d), rowmap=gmap)
+            C(stream, wp(f'{p}.2.fn.net.0.weight'), d, 2 * di, d, S(f'ff1_t{i}', d, 2 * dip), rowmap=gmap, transpose=True, n_rows_logical=2 * dip)
+            C(stream, wp(f'{p}.2.fn.net.3.weight'), di, d, di, S(f'ff2{i}', d, dip))
+            C(stream, wp(f'{p}.2.fn.net.3.weight'), di, d, di, S(f'ff2_t{i}', dip, d), transpose=True, n_rows_logical=d)
             b1 = self.shadows.get(f'ff1b{i}')
             if b1 is None:
                 b1 = self.shadows[f'ff1b{i}'] = torch.zeros(2 * dip, device=self.device)
@@ -458,4 +467,6 @@ class ParamStore:
         C(stream, self.ptr('to_text_logits.weight'), d, md.vocab, d, S('logits', md.vp, d))
         C(stream, self.ptr('to_text_logits.weight'), d, md.vocab, d, S('logits_t', d, md.vp), transpose=True, n_rows_logical=md.vocab)
         self._launch_casts(stream)
+        if self.lora:
+            self.lora.build_operands()                # A_phys / B^T_phys of every adapter, for the adapter-gradient launches
         self._shadow_version = ver

@@ -201,6 +201,8 @@ class _HeadPred(torch.autograd.Function):
 class SelfMaskedRepTraining(nn.Module):
     def __init__(self, net, ema_beta=0.999, rep_loss_weight=0.1, student_layer=-3, teacher_layer=-1, loss_fn=default_rep_loss_fn,
                  use_asymmetric_dropout=True, student_dropout_rate=0.1, teacher_dropout_rate=0.):
+        from .lora import require_no_lora
+        require_no_lora(net, 'SelfMaskedRepTraining')
         super().__init__()
         assert not use_asymmetric_dropout or student_dropout_rate > teacher_dropout_rate, 'student must have greater dropout rate than teacher to ensure teacher has a better view'
         if use_asymmetric_dropout:

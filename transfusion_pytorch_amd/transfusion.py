@@ -459,6 +459,8 @@ class Transfusion(nn.Module):
         """`copy.deepcopy(model)` (the reference's tests build their EMA teachers that way): a fresh model of the same architecture with the
         parameters copied - plans, launch lists and device index caches hold raw pointers and are rebuilt by the copy on first use"""
         import copy
+        from .lora import require_no_lora
+        require_no_lora(self, 'copy.deepcopy')
         kw = dict(self._init_kwargs)
         kw['transformer'] = self.transformer_config
         for k in ('pre_post_transformer_enc_dec', 'modality_encoder', 'modality_decoder'):
@@ -476,7 +478,8 @@ class Transfusion(nn.Module):
         encoder-decoder modules (optim.FusedAdam steps them with a stock Adam under the same global clip)"""
         mods = [m for m in self.pos_emb_mlp if m is not None]
         mods += [m for t in sorted(self._ext) for m in (self.latent_to_model_projs[t], self.model_to_latent_projs[t])]
-        return [p for m in mods for p in m.parameters() if p.requires_grad]
+        lora = self.store.lora.parameters() if self.store.lora else []          # LoRA adapters (lora.add_lora_): real parameters outside the flat buffer
+        return [p for m in mods for p in m.parameters() if p.requires_grad] + [p for p in lora if p.requires_grad]
 
     def _apply_fn_modality_type(self, fn, samples, modality_type):
         """apply_fn_modality_type (T:542-582): run `fn` on every modality of one type in a list of samples, same-shaped tensors stacked"""
@@ -661,7 +664,8 @@ class Transfusion(nn.Module):
         self._plans[key] = plan                                      # (re-)insert at the most recent position
         if training:
             # `p.requires_grad_(False)` on native parameters: the backward list of the current frozen set (built on first use, a few kept per plan)
-            plan.select_frozen(self.store.frozen_names())
+            # (and the LoRA adapters that train: their gradient launches stand in that list)
+            plan.select_frozen(self.store.frozen_names(), self.store.lora.key() if self.store.lora else ())
         return plan
 
     def _structure(self, key, build):
@@ -1626,6 +1630,8 @@ class Transfusion(nn.Module):
         self._consumed = step_id
         ps = self.store
         ps.ensure_grad_views(plan._frozen)                    # (the frozen set the forward built this step's backward list for)
+        if ps.lora:
+            ps.lora.ensure_grads()                            # `.grad` of the adapters: views of the buffers the list's launches add into
         if plan.bwd_end == 0 and not plan.taps and not plan.rows_in and not (self.md.model_output_clean and plan.clean_mode == 'model' and len(plan.clean_bwd)):
             return                                            # every native parameter is frozen and nothing else consumes the data gradient: no launch
         go = grad_out.reshape(()).to(torch.float32)           # d(total)/d(loss): scales the loss seeds (everything downstream is linear)
@@ -1830,6 +1836,8 @@ class Transfusion(nn.Module):
 
     def create_ema(self, beta=0.99, *ema_kwargs):                   # T:1681-1699
         from .ema import EMA
+        from .lora import require_no_lora
+        require_no_lora(self, 'create_ema()')
         return EMA(self, beta=beta, forward_method_names=('sample', 'sample_one', 'sample_many', 'generate_text_only', 'generate_modality_only'))
 
     @torch.no_grad()
