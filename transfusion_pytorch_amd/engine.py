@@ -188,14 +188,20 @@ class LaunchList(list):
 
 
 class Plan:
-    def __init__(self, ps: ParamStore, b: int, n: int, I: int, R: dict, training: bool = True, cache=None, dp_groups: int = 0, tile_attn: bool = False, units=None, ctl_rows: int = 2, tn_defer=None):
+    def __init__(self, ps: ParamStore, b: int, n: int, I: int, R: dict, training: bool = True, cache=None, dp_groups: int = 0, tile_attn: bool = False, units=None, ctl_rows: int = 2, tn_defer=None, ckpt: bool = False):
         """cache: None, or a KV cache tensor [depth, b, maxlen, 2*heads*64] (k~ | v per token).  With a cache the plan is a
         DECODE step: each layer appends this step's k~ / v rows at `cache_pos` (flat row b*maxlen + position, -1 = skip) and
         attention reads keys / values from the cache (per-token visible length in `kv_end`).
         units = (samples, max rows per sample): a COMPACTED decode plan - its `b * n` token rows are a flat list in which sample s of `samples`
         owns the rows unit_row0[s] .. + unit_cnt[s] (device arrays the step fills; 0 rows = the sample sits this step out), so a mixed step of the
-        continuous schedule carries the rows its live samples need instead of (modality length + 1) rows for every sample."""
+        continuous schedule carries the rows its live samples need instead of (modality length + 1) rows for every sample.
+        ckpt: ACTIVATION CHECKPOINTING (training plans; Transfusion.set_activation_checkpointing_): the per-layer activation family lives in `n_slots`
+        slots instead of one entry per layer, and the backward list recomputes a layer into its slot in front of the layer's backward launches."""
         md = ps.md
+        self.ckpt = bool(ckpt) and training
+        # the side stream's weight-gradient GEMMs read a layer's saved activations one layer behind the data-gradient chain: two slots by layer parity
+        # there, one on a single stream
+        self.n_slots = (2 if self._side_stream(md) else 1) if self.ckpt else None
         self.units = units
         assert not units or (cache is not None and tile_attn), 'compacted plans are decode plans on the tiled attention kernel (the row ranges are its arguments)'
         self.cache = cache
@@ -249,12 +255,23 @@ class Plan:
         # outlives the layer - the hiddens (AttentionResidual reads all of them), the AttentionResidual outputs (U-Net skips), and for a
         # prefill the rotated keys / values that fill the KV cache afterwards; everything else is ONE buffer shared by all layers (`li` = 0).
         # At dim 1024 / depth 24 a 64 x 320-token prefill plan is 5 GB this way instead of 25 GB: eight cached plans used to exhaust the 288 GB.
+        # A CHECKPOINTED training plan keeps per layer what the backward cannot rebuild from the layer's input - hid, xres, arsave, arerr, the soft-cap
+        # plans - and holds everything else in `n_slots` slots (layer i lives in slot i % n_slots): the forward leaves the top n_slots layers in them, the
+        # backward recomputes each lower layer into its slot (_build_backward).
         nl = D if training else 1
         nkv = D if (training or cache is None) else 1
         self._li = (lambda i: i) if training else (lambda i: 0)
         self._lkv = (lambda i: i) if nkv == D else (lambda i: 0)
+        if self.ckpt:
+            nl = nkv = self.n_slots
+            self._li = self._lkv = lambda i: i % nl
         xa_shared = None if training else e(T, d)
-        self.xa = {i: (e(T, d) if training else xa_shared) for i in range(D) if md.has_skip(i)}
+        if self.ckpt:
+            skips = [i for i in range(D) if md.has_skip(i)]              # (consecutive layers: the upper half of the stack)
+            xa_slot = [e(T, d) for _ in range(min(nl, len(skips)))]
+            self.xa = {i: xa_slot[i % len(xa_slot)] for i in skips}
+        else:
+            self.xa = {i: (e(T, d) if training else xa_shared) for i in range(D) if md.has_skip(i)}
         self.stats = e(4, nl, T, dtype=torch.float32)         # mean_a, rstd_a, mean_f, rstd_f
         self.ua = e(nl, T, d); self.uf = e(nl, T, d)
         self.qkvg = z(nkv, T, ldq); self.qkr = e(nkv, T, 2 * hd); self.og = z(nl, T, hd) if units else e(nl, T, hd)       # (compacted plans: padding rows are never written by the attention - keep them finite)
@@ -325,12 +342,13 @@ class Plan:
             # chip cost more than the token-wise overlap gained), so the side stream stopped at dim 512.  With the one-wave weight-gradient kernels and their
             # grouped launches it pays at every BASELINE width: dim 768 84.2 -> 83.0 ms, dim 1024 184.2 -> 181.8 ms per step (gpurun_out/ow41.txt, two rounds)
             # (TFX_SIDE_STREAM=1 forces it on, =0 off)
-            env = os.environ.get('TFX_SIDE_STREAM')
-            self.side = D <= 30 and (env == '1' or (env is None and md.dim <= 1024))
+            self.side = self._side_stream(md)
             # deferred weight gradients (round 7, _tn_run_length): the products of a RUN of layers wait for one table launch at the run's lowest layer, so what they
             # read - dy of both wrappers, d[a|g], d[q|k|v|gates] - is kept per layer: two runs' worth (a run's buffers are reused two runs later, behind a wait
             # for the launch that read them), or one per layer when that covers the stack
-            self.tn_run = self._tn_run_length()
+            # (a checkpointed plan keeps the per-layer groups whatever TFX_TN_DEFER says: a table launch reads a whole run of layers' saved activations,
+            # and a slot holds one layer's)
+            self.tn_run = 0 if self.ckpt else self._tn_run_length()
             self.tn_tables = []                 # [(index in the backward list, lowest layer, highest layer, table bytes on ps.device, records)]
             nb = min(D, 2 * self.tn_run) if self.tn_run else (2 if self.side else 1)
             self.dy_f = [e(T, d) for _ in range(nb)]; self.dy_a = [e(T, d) for _ in range(nb)] if (self.side or self.tn_run) else self.dy_f
@@ -410,6 +428,12 @@ class Plan:
             if out[0].value != 3 or out[1].value != tiles:
                 return 0
         return D
+
+    @staticmethod
+    def _side_stream(md):
+        """whether the backward's weight-gradient GEMMs run on the side stream (TFX_SIDE_STREAM=1 forces it on, =0 off)"""
+        env = os.environ.get('TFX_SIDE_STREAM')
+        return md.depth <= 30 and (env == '1' or (env is None and md.dim <= 1024))
 
     def _bwd_slot(self, i):
         """which of the per-layer backward buffers (dy_f, dy_a, d[a|g], d[q|k|v|gates]) layer i writes"""
@@ -511,7 +535,6 @@ class Plan:
             self._nt(L, A=self.cond, lda=4 * d, B=S['ada'], ldb=4 * d, M=I, N=nt3, K=4 * d, epi=E['TFX_EPI_F32'], C=self.tables, ldc=nt3,
                      bias=pp('transformer.layers.0.1.to_film.bias'))
             self.fwd_cond = (self.fwd_cond[0], len(L))
-        src = skip_sources(md)
         fused_pre = {}                        # layer -> its attention-side AdaLN-pre args when the previous layer's end launch runs them
         # token-wise launches that follow each other on the same rows run as ONE launch (bit-identical to the separate kernels, tests/test_kernels_gpu.py):
         # wrapper output + next wrapper input, and the end of a layer (feed-forward output side, AttentionResidual, the next layer's input side).
@@ -519,58 +542,9 @@ class Plan:
         fuse = True
         for i in range(D):
             p = f'transformer.layers.{i}'
-            li, lkv = self._li(i), self._lkv(i)
-            x_in = self.xres[i]
-            if md.has_skip(i):
-                self._nt(L, A=x_in, lda=d, A2=self.xres[src[i]], lda2=d, K1=d, B=S[f'skip{i}'], ldb=2 * d, M=T, N=d, K=2 * d,
-                         epi=E['TFX_EPI_RESID'], C=self.xa[i], ldc=d, R=x_in, ldr=d)
-                x_a = self.xa[i]
-            else:
-                x_a = x_in
-            ta, _ = self._tab(i, 0); tf, _ = self._tab(i, 1)
-            a_pre_attn = capi.make_args('tfx_adaln_pre_args', T=T, d=d, x=x_a, u=self.ua[li], tok_inst=self.tok_inst, table=ta, ld_table=nt3,
-                                        gamma_text=pp(f'{p}.1.layernorm_gamma'), mean=_p(self.stats, 0, li), rstd=_p(self.stats, 1, li))
-            if i in fused_pre:                # already done by the previous layer's end launch (tfx_layer_end_fwd)
-                assert fused_pre[i].x == a_pre_attn.x and fused_pre[i].u == a_pre_attn.u
-            else:
-                L.append(('tfx_adaln_pre_fwd', a_pre_attn))
-                self._hbm(L, 2, 8 * T)                                  # x in, u out, mean / rstd out
-            gam = self._gains(i)
-            plan_kw = dict(sc_plan=self.sc_plan[i], softcap=50.0) if self.sc_plan is not None else {}
-            # decode plans (round 4): the same epilogue in the decode-step GEMM kernel, with the KV-cache append (`qk_cache`): one launch per layer
-            # less in a step that is nothing but ~225 dependent launches.  Training plans keep the token-wise launch: fused there the projection grows from 150 to
-            # 195 us for the 53 us launch it removes (27.50 vs 27.50 ms per step, round 4)
-            fuse_qk = self.cache is not None
-            if fuse_qk:
-                # SURVEY K4 (T:946-965): QK-RMSNorm + RoPE ride in the epilogue of the [q | k | v | gates] projection (TFX_EPI_QKV_NORM_ROPE: the raw
-                # projection AND q~ | k~ leave the GEMM; shapes off the decode-step kernel run as two launches inside the call), with the KV-cache append
-                self._nt(L, algo_n=md.nq, A=self.ua[li], lda=d, B=S[f'qkvg{i}'], ldb=d, M=T, N=md.nqk, K=d, epi=E['TFX_EPI_QKV_NORM_ROPE'], C=self.qkvg[lkv], ldc=ldq,
-                         C2=self.qkr[lkv], ldc2=2 * hd, qk_heads=H, qk_gamma_q=gam('q'), qk_gamma_k=gam('k'), qk_rot_pos=self.rot_pos, qk_cos=0, qk_sin=0,
-                         qk_q_scale=md.dim_head ** -0.5, qk_norm_scale=md.dim_head ** 0.5,
-                         **({'qk_plan': plan_kw['sc_plan'], 'qk_softcap': 50.0} if plan_kw else {}),
-                         **(dict(qk_cache=self.cache[i], qk_ld_cache=2 * hd, qk_cache_pos=self.cache_pos) if self.cache is not None else {}))
-                self._rope_nt_args = getattr(self, '_rope_nt_args', []) + [L[-1][1]]
-                self._laser_fwd(L, i)
-                self._k(L, 'tfx_attn_fwd' if (self.cache is None or self.tile_attn) else 'tfx_decode_attn', 'tfx_attn_args', **self._attn_kw(i))
-            else:
-                self._nt(L, algo_n=md.nq, A=self.ua[li], lda=d, B=S[f'qkvg{i}'], ldb=d, M=T, N=md.nqk, K=d, epi=E['TFX_EPI_BF16'], C=self.qkvg[lkv], ldc=ldq)
-                self._qknr_separate(L, i, li, lkv, gam, plan_kw)
-            self._nt(L, algo_k=md.hd, A=self.og[li], lda=hd, B=S[f'out{i}'], ldb=hd, M=T, N=d, K=hd, epi=E['TFX_EPI_BF16'], C=self.ya[li], ldc=d)
-            a_post = capi.make_args('tfx_adaln_post_args', T=T, d=d, x=x_a, y=self.ya[li], out=self.xb[li], tok_inst=self.tok_inst,
-                                    table=ta, ld_table=nt3, layerscale=pp(f'{p}.1.layerscale'))
-            a_pre = capi.make_args('tfx_adaln_pre_args', T=T, d=d, x=self.xb[li], u=self.uf[li], tok_inst=self.tok_inst, table=tf, ld_table=nt3,
-                                   gamma_text=pp(f'{p}.2.layernorm_gamma'), mean=_p(self.stats, 2, li), rstd=_p(self.stats, 3, li))
-            if fuse:                          # both sides in one launch
-                self._keep = getattr(self, '_keep', []) + [a_post, a_pre]
-                self._raw(L, capi.lib().tfx_adaln_post_pre_fwd, ctypes.addressof(a_post), ctypes.addressof(a_pre))
-                self._hbm(L, 4, 8 * T)                                  # x, y in; out, u out
-            else:
-                L.append(('tfx_adaln_post_fwd', a_post))
-                L.append(('tfx_adaln_pre_fwd', a_pre))
-            self._nt(L, algo_n=2 * md.di, A=self.uf[li], lda=d, B=S[f'ff1{i}'], ldb=d, M=T, N=2 * dip, K=d, epi=E['TFX_EPI_GEGLU'], C=self.ag[li], ldc=2 * dip,
-                     C2=self.hm[li], ldc2=dip, bias=S[f'ff1b{i}'])
-            self._nt(L, algo_k=md.di, A=self.hm[li], lda=dip, B=S[f'ff2{i}'], ldb=dip, M=T, N=d, K=dip, epi=E['TFX_EPI_BF16'], C=self.yf[li], ldc=d,
-                     bias=pp(f'{p}.2.fn.net.3.bias'))
+            li = self._li(i)
+            tf, _ = self._tab(i, 1)
+            self._layer_body(L, i, fused_pre.get(i))
             a_postf = capi.make_args('tfx_adaln_post_args', T=T, d=d, x=self.xb[li], y=self.yf[li], out=self.hid[i + 1], tok_inst=self.tok_inst,
                                      table=tf, ld_table=nt3, layerscale=pp(f'{p}.2.layerscale'))
             a_ar = capi.make_args('tfx_attnres_args', T=T, d=d, L=i + 2, hiddens=self.hid, stride_h=T * d,
@@ -649,6 +623,70 @@ class Plan:
                                                recon_w=lt['recw'], recon_inst=self.row_inst[t], recon_time=self.inst_time, recon_mode=0,
                                                **(dict(row_inst=self.row_inst[t], inst_time=self.inst_time, clean_eps=float(md.clean_eps)) if md.model_output_clean else {}))
             self.rec.append(('tfx_mse_fwd_bwd', self._rec_args[t]))
+
+    def _layer_body(self, L, i, pre_done=None):
+        """layer i's launches into the list `L`, from the U-Net skip projection up to and including the second feed-forward GEMM - everything but the
+        launch that ends the layer (output side of the feed-forward wrapper + AttentionResidual: they write hid / xres / arsave, which outlive the layer).
+        The forward list and the recompute segments of a checkpointed plan's backward list (_build_backward) are both made here, so they are the same
+        launches on the same buffers - layer i's slot, `_li(i)` / `_lkv(i)`.  `pre_done`: the args of the attention-side AdaLN-pre when the previous
+        layer's end launch has already run it (tfx_layer_end_fwd; bit-identical to the separate launch, tests/test_kernels_gpu.py) - None emits the launch."""
+        ps, md, T = self.ps, self.md, self.T
+        d, hd, dip, ldq, nt3, H = md.dim, md.hdk, md.dip, md.ldq, md.nt3, md.heads
+        S, pp = ps.shadows, ps.ptr
+        fuse = True                       # (token-wise neighbours as one launch: see _build_forward)
+        p = f'transformer.layers.{i}'
+        li, lkv = self._li(i), self._lkv(i)
+        x_in = self.xres[i]
+        if md.has_skip(i):
+            self._nt(L, A=x_in, lda=d, A2=self.xres[skip_sources(md)[i]], lda2=d, K1=d, B=S[f'skip{i}'], ldb=2 * d, M=T, N=d, K=2 * d,
+                     epi=E['TFX_EPI_RESID'], C=self.xa[i], ldc=d, R=x_in, ldr=d)
+            x_a = self.xa[i]
+        else:
+            x_a = x_in
+        ta, _ = self._tab(i, 0); tf, _ = self._tab(i, 1)
+        a_pre_attn = capi.make_args('tfx_adaln_pre_args', T=T, d=d, x=x_a, u=self.ua[li], tok_inst=self.tok_inst, table=ta, ld_table=nt3,
+                                    gamma_text=pp(f'{p}.1.layernorm_gamma'), mean=_p(self.stats, 0, li), rstd=_p(self.stats, 1, li))
+        if pre_done is not None:          # already done by the previous layer's end launch (tfx_layer_end_fwd)
+            assert pre_done.x == a_pre_attn.x and pre_done.u == a_pre_attn.u
+        else:
+            L.append(('tfx_adaln_pre_fwd', a_pre_attn))
+            self._hbm(L, 2, 8 * T)                                  # x in, u out, mean / rstd out
+        gam = self._gains(i)
+        plan_kw = dict(sc_plan=self.sc_plan[i], softcap=50.0) if self.sc_plan is not None else {}
+        # decode plans (round 4): the same epilogue in the decode-step GEMM kernel, with the KV-cache append (`qk_cache`): one launch per layer
+        # less in a step that is nothing but ~225 dependent launches.  Training plans keep the token-wise launch: fused there the projection grows from 150 to
+        # 195 us for the 53 us launch it removes (27.50 vs 27.50 ms per step, round 4)
+        fuse_qk = self.cache is not None
+        if fuse_qk:
+            # SURVEY K4 (T:946-965): QK-RMSNorm + RoPE ride in the epilogue of the [q | k | v | gates] projection (TFX_EPI_QKV_NORM_ROPE: the raw
+            # projection AND q~ | k~ leave the GEMM; shapes off the decode-step kernel run as two launches inside the call), with the KV-cache append
+            self._nt(L, algo_n=md.nq, A=self.ua[li], lda=d, B=S[f'qkvg{i}'], ldb=d, M=T, N=md.nqk, K=d, epi=E['TFX_EPI_QKV_NORM_ROPE'], C=self.qkvg[lkv], ldc=ldq,
+                     C2=self.qkr[lkv], ldc2=2 * hd, qk_heads=H, qk_gamma_q=gam('q'), qk_gamma_k=gam('k'), qk_rot_pos=self.rot_pos, qk_cos=0, qk_sin=0,
+                     qk_q_scale=md.dim_head ** -0.5, qk_norm_scale=md.dim_head ** 0.5,
+                     **({'qk_plan': plan_kw['sc_plan'], 'qk_softcap': 50.0} if plan_kw else {}),
+                     **(dict(qk_cache=self.cache[i], qk_ld_cache=2 * hd, qk_cache_pos=self.cache_pos) if self.cache is not None else {}))
+            self._rope_nt_args = getattr(self, '_rope_nt_args', []) + [L[-1][1]]
+            self._laser_fwd(L, i)
+            self._k(L, 'tfx_attn_fwd' if (self.cache is None or self.tile_attn) else 'tfx_decode_attn', 'tfx_attn_args', **self._attn_kw(i))
+        else:
+            self._nt(L, algo_n=md.nq, A=self.ua[li], lda=d, B=S[f'qkvg{i}'], ldb=d, M=T, N=md.nqk, K=d, epi=E['TFX_EPI_BF16'], C=self.qkvg[lkv], ldc=ldq)
+            self._qknr_separate(L, i, li, lkv, gam, plan_kw)
+        self._nt(L, algo_k=md.hd, A=self.og[li], lda=hd, B=S[f'out{i}'], ldb=hd, M=T, N=d, K=hd, epi=E['TFX_EPI_BF16'], C=self.ya[li], ldc=d)
+        a_post = capi.make_args('tfx_adaln_post_args', T=T, d=d, x=x_a, y=self.ya[li], out=self.xb[li], tok_inst=self.tok_inst,
+                                table=ta, ld_table=nt3, layerscale=pp(f'{p}.1.layerscale'))
+        a_pre = capi.make_args('tfx_adaln_pre_args', T=T, d=d, x=self.xb[li], u=self.uf[li], tok_inst=self.tok_inst, table=tf, ld_table=nt3,
+                               gamma_text=pp(f'{p}.2.layernorm_gamma'), mean=_p(self.stats, 2, li), rstd=_p(self.stats, 3, li))
+        if fuse:                          # both sides in one launch
+            self._keep = getattr(self, '_keep', []) + [a_post, a_pre]
+            self._raw(L, capi.lib().tfx_adaln_post_pre_fwd, ctypes.addressof(a_post), ctypes.addressof(a_pre))
+            self._hbm(L, 4, 8 * T)                                  # x, y in; out, u out
+        else:
+            L.append(('tfx_adaln_post_fwd', a_post))
+            L.append(('tfx_adaln_pre_fwd', a_pre))
+        self._nt(L, algo_n=2 * md.di, A=self.uf[li], lda=d, B=S[f'ff1{i}'], ldb=d, M=T, N=2 * dip, K=d, epi=E['TFX_EPI_GEGLU'], C=self.ag[li], ldc=2 * dip,
+                 C2=self.hm[li], ldc2=dip, bias=S[f'ff1b{i}'])
+        self._nt(L, algo_k=md.di, A=self.hm[li], lda=dip, B=S[f'ff2{i}'], ldb=dip, M=T, N=d, K=dip, epi=E['TFX_EPI_BF16'], C=self.yf[li], ldc=d,
+                 bias=pp(f'{p}.2.fn.net.3.bias'))
 
     def _chain_weight_prefetch(self, L):
         """Decode / prefill plans (round 6): every GEMM launch names the weights of the NEXT GEMM of the list in `prefetch` (tfx.h) - spare blocks of the launch touch
@@ -857,6 +895,7 @@ class Plan:
         tr = lambda name: name not in fz
         gpn = lambda name: gp(name) if name not in fz else None
         low, self.bwd_end = self._lowest_consumer()
+        self._recompute = {}                  # checkpointed plans: layer -> [begin, end) of its recompute segment in this list (recompute_range)
         ada = self._time_cond_trains() or any(tr(n) for n in ps.params if '.to_film.' in n or '.to_ada_ln_zero.' in n)
         if low == 'none':
             self.bwd_end = 0
@@ -989,13 +1028,22 @@ class Plan:
             if not ada:
                 dta = dtf = None                    # no trainable parameter behind the AdaLN tables: their gradient is not formed (tfx.h: dtable NULL)
             par = self._bwd_slot(i)
+            sl = self._li(i)                        # where the layer's saved activations are: entry i, or in a checkpointed plan its slot
             dy_f, dy_a, dag, dqkvg = self.dy_f[par], self.dy_a[par], self.dag_p[par], self.dqkvg_p[par]
             if not run and i + 2 <= D - 1:
                 sync('tfx_join_wait', i + 2)       # this layer reuses the buffers of layer i+2: its weight gradients must have read them
+            if self.ckpt and i < D - self.n_slots:
+                # checkpointed plan: the slot still holds layer i + n_slots (the forward left the top n_slots layers in place) - the layer's forward
+                # launches again, from its kept input xres[i] (_layer_body: the launches of the forward list, with the attention side's AdaLN-pre as
+                # its own launch), up to the second feed-forward GEMM.  Not the layer's end launch: hid / xres / arsave are kept per layer and never
+                # rewritten.  On the side stream the slot is also what the weight-gradient products of layer i + 2 read: the wait above covers them.
+                lo = len(L)
+                self._layer_body(L, i)
+                self._recompute[i] = (lo, len(L))
             if run and i + len(self.dag_p) <= D - 1:
                 sync('tfx_join_wait', run_low[i + len(self.dag_p)])      # ... of layer i + (number of buffers): the table launch of that layer's run
             G = self.dH[i + 1]
-            a_postf = capi.make_args('tfx_adaln_post_args', T=T, d=d, y=self.yf[i], tok_inst=self.tok_inst, table=tf, ld_table=nt3,
+            a_postf = capi.make_args('tfx_adaln_post_args', T=T, d=d, y=self.yf[sl], tok_inst=self.tok_inst, table=tf, ld_table=nt3,
                                      layerscale=pp(f'{p}.2.layerscale'), g=G, dy=dy_f, dtable=dtf, dlayerscale=gpn(f'{p}.2.layerscale'),
                                      seg_start=self.seg_start, seg_len=self.seg_len, n_seg=0, dbias=gpn(f'{p}.2.fn.net.3.bias'))   # ff2 bias gradient = column sums of dy
             self._seg_args.append(a_postf)
@@ -1011,15 +1059,15 @@ class Plan:
                 # ---- feedforward wrapper
                 L.append(('tfx_adaln_post_bwd', a_postf))
             self._nt(L, algo_n=di, A=dy_f, lda=d, B=S[f'ff2_t{i}'], ldb=d, M=T, N=dip, K=d, epi=E['TFX_EPI_GEGLU_BWD'], C=dag, ldc=2 * dip,
-                     aux=self.ag[i], ldaux=2 * dip)
+                     aux=self.ag[sl], ldaux=2 * dip)
             # the weight gradients of this wrapper go to the side stream (dy_f and d[a|g] are final); net.0 carries its bias gradient
             # (column sums of d[a|g]) folded into the same GEMM
             if not run:
                 sync('tfx_fork', 2 * i)
             # (round 5 tried net.3's bias gradient as this GEMM's `colsum` to free 8 registers of the pull kernel: the SUM form of the GEMM is 13 us slower per
             # launch (158 vs 145 us, profiles/r05_shapes.txt) - and with its scale row in LDS the pull kernel no longer spills WITH the bias partials)
-            ff_grp = [(d, di, dict(A=dy_f, lda=d, a_cols=d, B=self.hm[i], ldb=dip, b_cols=dip, C=gp(f'{p}.2.fn.net.3.weight'), ldc=di)),
-                      (2 * dip, d, dict(algo_n=2 * di, A=dag, lda=2 * dip, a_cols=2 * dip, B=self.uf[i], ldb=d, b_cols=d, rowmap=gmap,
+            ff_grp = [(d, di, dict(A=dy_f, lda=d, a_cols=d, B=self.hm[sl], ldb=dip, b_cols=dip, C=gp(f'{p}.2.fn.net.3.weight'), ldc=di)),
+                      (2 * dip, d, dict(algo_n=2 * di, A=dag, lda=2 * dip, a_cols=2 * dip, B=self.uf[sl], ldb=d, b_cols=d, rowmap=gmap,
                                         C=gp(f'{p}.2.fn.net.0.weight'), ldc=d, colsum=gpn(f'{p}.2.fn.net.0.bias')))]
             if fz:
                 ff_grp = [m for m, nm in zip(ff_grp, ('net.3', 'net.0')) if tr(f'{p}.2.fn.{nm}.weight')]
@@ -1033,14 +1081,14 @@ class Plan:
             elif ff_grp:
                 self._tn_group(L, T, ff_grp, side=side)
             # LoRA adapters of the feed-forward matrices: where their weight-gradient products stand or would stand (dy_f, d[a|g] and the saved inputs are final)
-            self._lora_launches(L, i, 'net.3', self.hm[i], dip, dy_f, d)
-            self._lora_launches(L, i, 'net.0', self.uf[i], d, dag, 2 * dip)
+            self._lora_launches(L, i, 'net.3', self.hm[sl], dip, dy_f, d)
+            self._lora_launches(L, i, 'net.0', self.uf[sl], d, dag, 2 * dip)
             self._nt(L, algo_k=2 * di, A=dag, lda=2 * dip, B=S[f'ff1_t{i}'], ldb=2 * dip, M=T, N=d, K=2 * dip, epi=E['TFX_EPI_BF16'], C=self.du, ldc=d)
-            a_pref = capi.make_args('tfx_adaln_pre_args', T=T, d=d, x=self.xb[i], tok_inst=self.tok_inst, table=tf, ld_table=nt3,
-                                    gamma_text=pp(f'{p}.2.layernorm_gamma'), mean=_p(self.stats, 2, i), rstd=_p(self.stats, 3, i), du=self.du, dx=G,
+            a_pref = capi.make_args('tfx_adaln_pre_args', T=T, d=d, x=self.xb[sl], tok_inst=self.tok_inst, table=tf, ld_table=nt3,
+                                    gamma_text=pp(f'{p}.2.layernorm_gamma'), mean=_p(self.stats, 2, sl), rstd=_p(self.stats, 3, sl), du=self.du, dx=G,
                                     dtable=dtf, dgamma_text=gpn(f'{p}.2.layernorm_gamma'), seg_start=self.seg_start, seg_len=self.seg_len, n_seg=0)
             # ---- attention wrapper
-            a_posta = capi.make_args('tfx_adaln_post_args', T=T, d=d, y=self.ya[i], tok_inst=self.tok_inst, table=ta, ld_table=nt3,
+            a_posta = capi.make_args('tfx_adaln_post_args', T=T, d=d, y=self.ya[sl], tok_inst=self.tok_inst, table=ta, ld_table=nt3,
                                      layerscale=pp(f'{p}.1.layerscale'), g=G, dy=dy_a, dtable=dta, dlayerscale=gpn(f'{p}.1.layerscale'),
                                      seg_start=self.seg_start, seg_len=self.seg_len, n_seg=0)
             self._seg_args += [a_pref, a_posta]
@@ -1057,7 +1105,7 @@ class Plan:
             if os.environ.get('TFX_ATTN_QKNR', '1') != '0':
                 # round 5: the backward of QK-RMSNorm + RoPE rides in the epilogues of the dQ and dK/dV kernels (tfx.h tfx_attn_args.nr_*): d q~ | d k~ are never
                 # written out and read back, and the token-wise launch below drops out of the layer
-                self._k(L, 'tfx_attn_bwd', 'tfx_attn_args', **self._attn_kw(i, bwd=True), nr_qkv=self.qkvg[i], nr_ld_qkv=ldq, nr_dqkv=dqkvg, nr_ld_dqkv=ldq,
+                self._k(L, 'tfx_attn_bwd', 'tfx_attn_args', **self._attn_kw(i, bwd=True), nr_qkv=self.qkvg[sl], nr_ld_qkv=ldq, nr_dqkv=dqkvg, nr_ld_dqkv=ldq,
                         nr_gamma_q=gam('q'), nr_gamma_k=gam('k'), nr_rot_pos=self.rot_pos, nr_cos=0, nr_sin=0, nr_q_scale=md.dim_head ** -0.5,
                         nr_norm_scale=md.dim_head ** 0.5, **dgam('nr_'))
                 # (per-block partial rows + a reduction launch instead of the 64 same-address atomics per block measured SLOWER in round 5 - 4.19 vs 4.05 ms -
@@ -1065,7 +1113,7 @@ class Plan:
                 self._rope_attn_args = getattr(self, '_rope_attn_args', []) + [L[-1][1]]
             else:
                 self._k(L, 'tfx_attn_bwd', 'tfx_attn_args', **self._attn_kw(i, bwd=True))
-                self._k(L, 'tfx_qk_norm_rope_bwd', 'tfx_qk_norm_rope_args', T=T, H=H, qkv=self.qkvg[i], ld_qkv=ldq, gamma_q=gam('q'),
+                self._k(L, 'tfx_qk_norm_rope_bwd', 'tfx_qk_norm_rope_args', T=T, H=H, qkv=self.qkvg[sl], ld_qkv=ldq, gamma_q=gam('q'),
                         gamma_k=gam('k'), rot_pos=self.rot_pos, cos_tab=0, sin_tab=0, q_scale=md.dim_head ** -0.5, norm_scale=md.dim_head ** 0.5,
                         dqk=self.dqk, ld_dqk=2 * hd, dqkv=dqkvg, ld_dqkv=ldq, **dgam(''))
                 self._rope_args = getattr(self, '_rope_args', []) + [L[-1][1]]
@@ -1073,30 +1121,30 @@ class Plan:
                 L.meta[len(L) - 1] = ('hbm', 3 * 2 * T * hd * 2)                # q, k (raw) in; d q~, d k~ in; d q, d k out
             if md.laser:                # d v' -> d v in place, before the dX and weight-gradient GEMMs read the [dq | dk | dv | dgate] rows (T:979-983 backwards)
                 dv = dqkvg.data_ptr() + 2 * 2 * hd
-                self._k(L, 'tfx_laser_v_bwd', 'tfx_laser_v_args', T=T, H=H, v=_p(self.qkvg, i) + 2 * 2 * hd, ld_v=ldq, c=md.laser,
+                self._k(L, 'tfx_laser_v_bwd', 'tfx_laser_v_args', T=T, H=H, v=_p(self.qkvg, sl) + 2 * 2 * hd, ld_v=ldq, c=md.laser,
                         dvl=dv, ld_dvl=ldq, dv=dv, ld_dv=ldq)
                 L.meta = L.meta or {}
                 L.meta[len(L) - 1] = ('hbm', 3 * T * hd * 2)                  # v, d v' in; d v out
             self._nt(L, algo_k=md.nq, A=dqkvg, lda=ldq, B=S[f'qkvg_t{i}'], ldb=ldq, M=T, N=d, K=ldq, epi=E['TFX_EPI_BF16'], C=self.du, ldc=d)
             # (pull form: the gradient a U-Net skip hands to this layer's input joins here, so that G ends up as the TOTAL gradient of xres[i])
             self._k(L, 'tfx_adaln_pre_bwd', 'tfx_adaln_pre_args', T=T, d=d, x=x_a, tok_inst=self.tok_inst, table=ta, ld_table=nt3,
-                    gamma_text=pp(f'{p}.1.layernorm_gamma'), mean=_p(self.stats, 0, i), rstd=_p(self.stats, 1, i), du=self.du, dx=G,
+                    gamma_text=pp(f'{p}.1.layernorm_gamma'), mean=_p(self.stats, 0, sl), rstd=_p(self.stats, 1, sl), du=self.du, dx=G,
                     dtable=dta, dgamma_text=gpn(f'{p}.1.layernorm_gamma'), seg_start=self.seg_start, seg_len=self.seg_len, n_seg=0,
                     dx_add=self.dskip[i] if (pull and i in pushed) else None)
             self._hbm(L, 4 + (1 if (pull and i in pushed) else 0))          # du, x in; residual gradient in / out (+ the U-Net skip's share)
             self._seg_args.append(L[-1][1])
             # LoRA adapters of the attention matrices (dy_a and d[q|k|v|gates] are final; to_v reads its columns of the fused gradient)
-            self._lora_launches(L, i, 'to_out', self.og[i], hd, dy_a, d)
-            self._lora_launches(L, i, 'to_qk', self.ua[i], d, dqkvg, ldq)
-            self._lora_launches(L, i, 'to_v', self.ua[i], d, dqkvg.data_ptr() + 2 * 2 * hd, ldq)
+            self._lora_launches(L, i, 'to_out', self.og[sl], hd, dy_a, d)
+            self._lora_launches(L, i, 'to_qk', self.ua[sl], d, dqkvg, ldq)
+            self._lora_launches(L, i, 'to_v', self.ua[sl], d, dqkvg.data_ptr() + 2 * 2 * hd, ldq)
             # weight gradients of the attention wrapper (dy_a, d[q|k|v|gates] and G = dH[i+1] are final) on the side stream
             per = -(-D // self.dp_groups) if self.dp_groups > 0 else D
             launch = bool(run) and run_low[i] == i             # lowest layer of a run: runs count down from the top of an exchange group and end with it
             if not run or launch:
                 sync('tfx_fork', 2 * i + 1)
-            grp = [(d, hd, dict(A=dy_a, lda=d, a_cols=d, B=self.og[i], ldb=hd, b_cols=hd, C=gp(f'{p}.1.fn.to_out.1.weight'), ldc=md.hd,
+            grp = [(d, hd, dict(A=dy_a, lda=d, a_cols=d, B=self.og[sl], ldb=hd, b_cols=hd, C=gp(f'{p}.1.fn.to_out.1.weight'), ldc=md.hd,
                                 k_group=0 if md.dim_head == 64 else md.dim_head)),
-                   (md.nqk, d, dict(algo_n=md.nq, A=dqkvg, lda=ldq, a_cols=ldq, B=self.ua[i], ldb=d, b_cols=d, C=gp(f'{p}.1.fn.to_qk.0.weight'), ldc=d,
+                   (md.nqk, d, dict(algo_n=md.nq, A=dqkvg, lda=ldq, a_cols=ldq, B=self.ua[sl], ldb=d, b_cols=d, C=gp(f'{p}.1.fn.to_qk.0.weight'), ldc=d,
                                     rowmap=ps._maps['heads'] if md.dim_head != 64 else None))]
             if fz:
                 grp = self._frozen_attn_group(grp, p)
@@ -1256,7 +1304,7 @@ class Plan:
 
     # ------------------------------------------------------------------------------------ frozen parameters
     # what a backward list owns: one set of these per frozen set (select_frozen)
-    _BWD_STATE = ('bwd', 'bwd_cuts', 'bwd_end', 'tn_tables', 'clean_bwd', 'tap_final', 'tap0', '_pull_args', '_src_tab', 'ar_tail')
+    _BWD_STATE = ('bwd', 'bwd_cuts', 'bwd_end', 'tn_tables', 'clean_bwd', 'tap_final', 'tap0', '_pull_args', '_src_tab', 'ar_tail', '_recompute')
     _BWD_SETS = 4               # backward lists kept per plan beside the one with nothing frozen
 
     def select_frozen(self, frozen: frozenset, lora: tuple = ()):
@@ -1401,6 +1449,11 @@ class Plan:
             if 1 <= k <= self.md.depth:
                 self._pull_args[k].add = None
         self.taps = {}
+
+    def recompute_range(self, i):
+        """checkpointed plans: [begin, end) of layer i's recompute segment in the current backward list - `Plan.run(plan.bwd, stream, *range)` replays it
+        alone - or None for a layer that is not recomputed (the top `n_slots` layers: still live from the forward; every layer of a plain plan)"""
+        return self._recompute.get(i)
 
     def run_bwd(self, stream, lo=0, hi=None):
         """replay bwd[lo:hi]; a tap at the final norm's output adds its gradient to dembed at its place in the list, a tap at x_0 runs its

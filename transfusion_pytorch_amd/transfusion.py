@@ -394,6 +394,7 @@ class Transfusion(nn.Module):
             self._register_load_state_dict_pre_hook(_pre)
             self._register_state_dict_hook(_post)
         self._plans = {}
+        self._ckpt = False                   # activation checkpointing (set_activation_checkpointing_): part of the plan key
         self._struct_cache = {}
         self._decode_plans = {}              # decode plans of the cached forward calls and of the sampler (sampling.Sampler._decode_plan)
         self._flat_pred_flows = False        # set by `_teacher_pass` around a teacher's forward
@@ -470,6 +471,7 @@ class Transfusion(nn.Module):
             new = new.to(self.device)
         new.load_state_dict(self.state_dict())
         new.train(self.training)
+        new._ckpt = self._ckpt
         memo[id(self)] = new
         return new
 
@@ -633,6 +635,22 @@ class Transfusion(nn.Module):
             self._decode_keep = None
         return super().train(mode)
 
+    @property
+    def activation_checkpointing(self) -> bool:
+        return self._ckpt
+
+    def set_activation_checkpointing_(self, enabled: bool = True):
+        """trade time for memory in training: with the switch on, a training plan keeps per layer only what the backward cannot rebuild from the layer's
+        input (the hiddens, the AttentionResidual outputs and their saved softmax state) and holds every other saved activation in one or two
+        layer-sized slots; the backward list recomputes each layer into its slot, with the forward's own launches, in front of the layer's backward
+        (engine.Plan `ckpt`).  Off by default.  Takes effect on the next training forward - `forward`, `forward_text(return_loss=True)`,
+        `forward_modality(return_loss=True)`; the switch is part of the plan key, so plans of both kinds can sit in the cache together.  Inference, decode
+        and sampling never look at it.  A checkpointed plan forms its weight gradients in per-layer groups whatever TFX_TN_DEFER says.  Returns self."""
+        if not isinstance(enabled, bool):
+            raise TypeError(f'set_activation_checkpointing_ takes a bool, got {type(enabled).__name__}')
+        self._ckpt = enabled
+        return self
+
     def _require_gpu(self):
         if self.device.type != 'cuda':
             raise capi.TfxError('the Transfusion hot path only runs on an MI355X (model.cuda()); there is no CPU fallback')
@@ -650,12 +668,13 @@ class Transfusion(nn.Module):
 
     def _plan(self, b, n, I, R, training):
         dp_groups = getattr(self, '_dp_groups', 0) if training else 0
-        key = (b, n, I, tuple(sorted(R.items())), training, dp_groups)
+        ckpt = training and self._ckpt                              # inference, decode, sampling and hiddens-only plans never look at the switch
+        key = (b, n, I, tuple(sorted(R.items())), training, dp_groups, ckpt)
         plan = self._plans.pop(key, None)
         if plan is None:
             while len(self._plans) >= 8:                             # least recently used plan goes first (dict order = use order)
                 self._plans.pop(next(iter(self._plans)))
-            plan = Plan(self.store, b, n, I, R, training=training, dp_groups=dp_groups)
+            plan = Plan(self.store, b, n, I, R, training=training, dp_groups=dp_groups, ckpt=ckpt)
             # a plan owns every activation of its step (tens of GB for a training plan at dim 1024 / depth 24): besides the count, the cache is
             # bounded by bytes - TFX_PLAN_BUDGET_GB, default 40 % of the device memory - oldest first, the new plan always stays
             budget = float(os.environ.get('TFX_PLAN_BUDGET_GB', 0)) * 2 ** 30 or 0.4 * torch.cuda.get_device_properties(self.device).total_memory
@@ -1829,6 +1848,7 @@ class Transfusion(nn.Module):
         kw['transformer'] = self.transformer_config
         kw['pre_post_transformer_enc_dec'] = copy.deepcopy(kw.get('pre_post_transformer_enc_dec'))     # learnable: the copy owns its own modules
         m = Transfusion(**kw)
+        m._ckpt = self._ckpt                 # (create_ema / EMA: harmless there - a teacher's passes run without gradient, on inference plans)
         return m.to(self.device) if self.device.type == 'cuda' else m
 
     def create_dataloader(self, *args, **kwargs):                   # T:1676-1679
