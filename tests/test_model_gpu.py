@@ -89,6 +89,13 @@ def test_training_step_matches_reference_golden(name):
     g = torch.load(os.path.join(GOLDEN, f'{name}.pt'), weights_only=False)
     cfg, model, out = run_native(name)
     print(f'[{name}]')
+    check_step_against_golden(name, g, out)
+
+
+def check_step_against_golden(name, g, out):
+    """everything test_training_step_matches_reference_golden asserts about `out` (run_native's result) against the reference golden `g`: losses, logits,
+    final embed, greedy tokens, the gradient rule of the golden.  Shared with tests/test_push_form_gpu.py, which runs the same goldens through the
+    push-form backward; returns the measured figures."""
     compare_losses(out, g)
     rs = g['row_step']
     lg, lr = out['logits'][:, ::rs], g['logits']
@@ -127,6 +134,7 @@ def test_training_step_matches_reference_golden(name):
     print(f'  gradients: norm-weighted mean rel err {num / den:.3e}; worst {worst[0]} {worst[1]:.3e}')
     _log_parity(name, grad_mean_rel=num / den, grad_worst_rel=worst[1])
     assert num / den <= GRAD_MEAN_TOL
+    return dict(logits_rel=e_log, embed_rel=e_emb, grad_mean_rel=num / den, grad_worst_rel=worst[1], grad_worst_name=worst[0])
 
 
 def test_canon512_at_bench_batch_matches_golden_rows():

@@ -41,6 +41,17 @@ def skip_sources(md: ModelDims):
     return src
 
 
+# The one definition of where the AttentionResidual backward runs in pull form (tfx_attnres_pull_bwd; Plan.pull).  Outside it - deeper or wider - a
+# training plan builds the push form (tfx_attnres_bwd), which has no hidden taps: Plan.set_taps, Transfusion's return_hiddens next to the loss and
+# SelfMaskedRepTraining all ask pull_form_ok.
+PULL_MAX_DEPTH = 32
+PULL_MAX_DIM = 1024
+PULL_LIMITS = f'depth <= {PULL_MAX_DEPTH} and dim <= {PULL_MAX_DIM}'           # (for the messages of those who refuse the push form)
+
+
+def pull_form_ok(md: ModelDims) -> bool:
+    """whether a training plan of these dimensions runs the pull-form AttentionResidual backward"""
+    return md.depth <= PULL_MAX_DEPTH and md.dim <= PULL_MAX_DIM
 
 
 _LAUNCH = capi.STRUCTS['tfx_launch']
@@ -326,9 +337,9 @@ class Plan:
         self.loaded_structure = None
         self._seg_args, self._n_seg = [], 0
         self.seg_start = z(max(T, 1), dtype=torch.int32); self.seg_len = z(max(T, 1), dtype=torch.int32)
-        # AttentionResidual backward in pull form (tfx_attnres_pull_bwd): every layer's depth softmax is kept per token by the forward;
-        # TFX_ATTNRES_PULL=0 keeps the push form (tfx_attnres_bwd: one read-modify-write sweep over all earlier hiddens per layer; A/B)
-        self.pull = training and D <= 32 and md.dim <= 1024
+        # AttentionResidual backward in pull form (tfx_attnres_pull_bwd): every layer's depth softmax is kept per token by the forward.
+        # Outside pull_form_ok the list keeps the push form (tfx_attnres_bwd: one read-modify-write sweep over all earlier hiddens per layer)
+        self.pull = training and pull_form_ok(md)
         if self.pull:
             self.arsave = [e(T, i + 2, 4, dtype=torch.float32) for i in range(D)]
             self.arerr = e(D, T, d)                          # what rounding each AttentionResidual output to bf16 dropped
@@ -1414,7 +1425,7 @@ class Plan:
         if not grads:
             return
         if not self.pull:
-            raise NotImplementedError('hidden taps need the pull-form AttentionResidual backward (depth <= 32 and dim <= 1024): the push form has no '
+            raise NotImplementedError(f'hidden taps need the pull-form AttentionResidual backward ({PULL_LIMITS}): the push form has no '
                                       'place where a hidden\'s gradient is formed once')
         for k, g in grads.items():
             assert 0 <= k <= D + 1

@@ -23,7 +23,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import capi
+from . import capi, engine
 from .params import geglu_phys_to_ref_rows, pad_to
 
 BF16 = torch.bfloat16
@@ -209,9 +209,9 @@ class SelfMaskedRepTraining(nn.Module):
             raise NotImplementedError('SelfMaskedRepTraining(use_asymmetric_dropout=True): the MI355X kernels have no dropout (Transformer(dropout=...) raises too), '
                                       'so switching dropout probabilities would train something else without saying so - pass use_asymmetric_dropout=False '
                                       '(teacher = EMA weights, its own noise, a deeper layer)')
-        if rep_loss_weight > 0 and (net.md.depth > 32 or net.md.dim > 1024):
-            raise NotImplementedError('SelfMaskedRepTraining needs hidden taps, which ride on the pull-form AttentionResidual backward (depth <= 32 and '
-                                      f'dim <= 1024); this model has depth {net.md.depth}, dim {net.md.dim}')
+        if rep_loss_weight > 0 and not engine.pull_form_ok(net.md):
+            raise NotImplementedError('SelfMaskedRepTraining needs hidden taps, which ride on the pull-form AttentionResidual backward '
+                                      f'({engine.PULL_LIMITS}); this model has depth {net.md.depth}, dim {net.md.dim}')
         self.student = net
         self.teacher = net.create_ema(beta=ema_beta)
         self.rep_loss_weight = rep_loss_weight

@@ -17,6 +17,7 @@ import torch
 from torch import nn
 
 from . import capi
+from . import engine as _engine            # (pull_form_ok is looked up there at call time)
 from .engine import Plan
 from .ode import check_odeint_kwargs
 from .packing import fast_signature, is_int_tensor, scan_batch, scan_signature, token_maps, token_segments
@@ -918,8 +919,8 @@ class Transfusion(nn.Module):
         # ---- plan
         self.store.refresh_shadows(stream)
         plan = self._step_plan(S, return_loss, hid_only, no_teacher=ema is None and not return_only_pred_flows)
-        if train_hiddens and not hid_only and torch.is_grad_enabled() and not plan.pull:
-            raise NotImplementedError('return_hiddens next to the loss (hidden taps) needs the pull-form AttentionResidual backward: depth <= 32 and dim <= 1024 '
+        if train_hiddens and not hid_only and torch.is_grad_enabled() and not (_engine.pull_form_ok(self.md) and plan.pull):
+            raise NotImplementedError(f'return_hiddens next to the loss (hidden taps) needs the pull-form AttentionResidual backward: {_engine.PULL_LIMITS} '
                                       '(under torch.no_grad() the hiddens come back without a tap)')
 
         # ---- inputs onto the plan: token ids (values never visit the host), CFG drop, labels, instance times, latent rows, noise
