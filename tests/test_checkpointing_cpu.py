@@ -1,6 +1,5 @@
 """Activation checkpointing (Transfusion.set_activation_checkpointing_, engine.Plan `ckpt`): what can be checked without a GPU - the switch itself, the
 plan key, and the launch lists and buffers of real training Plans built on the CPU (nothing is launched)."""
-import collections
 import copy
 import ctypes
 import os
@@ -22,15 +21,10 @@ def _model(depth=5):
 
 
 def _cpu_plan(ckpt, depth=5, groups=0):
-    """a real training Plan built on the CPU, as tests/test_tn_table_cpu.py does: the lists are the product's own"""
-    from transfusion_pytorch_amd.engine import Plan
-    from transfusion_pytorch_amd.params import geglu_phys_to_ref_rows
-    m = _model(depth)
-    ps = m.store
-    ps.grad = torch.zeros(ps.numel)
-    ps.shadows = collections.defaultdict(lambda: torch.zeros(8, 8, dtype=torch.bfloat16))
-    ps._map('geglu', geglu_phys_to_ref_rows(m.md.di, m.md.dip))
-    return m, Plan(ps, b=2, n=64, I=4, R={0: 8, 1: 4}, training=True, dp_groups=groups, ckpt=ckpt)
+    """a real training Plan built on the CPU (tests/_plan_digest.py): the lists are the product's own"""
+    from _plan_digest import cpu_plan
+    m, _, plan = cpu_plan(depth=depth, dp_groups=groups, ckpt=ckpt)
+    return m, plan
 
 
 def _name(item):

@@ -117,18 +117,9 @@ def test_overlapped_gradient_exchange_world2():
 def _cpu_plan(depth=5, groups=3):
     """a REAL training Plan (engine.Plan: the launch lists the GPU replays) built on the CPU: nothing is launched, but the lists, their order and
     the cut points `bwd_cuts` are the product's own"""
-    import collections
-    from transfusion_pytorch_amd import Transfusion
-    from transfusion_pytorch_amd.engine import Plan
-    from transfusion_pytorch_amd.params import geglu_phys_to_ref_rows
-    torch.manual_seed(0)
-    m = Transfusion(num_text_tokens=16, dim_latent=(32, 8), transformer=dict(dim=64, depth=depth, heads=1))
-    ps = m.store
-    ps.grad = torch.zeros(ps.numel)
-    ps.shadows = collections.defaultdict(lambda: torch.zeros(8, 8, dtype=torch.bfloat16))      # bf16 kernel-layout copies: only their addresses enter the lists
-    ps._map('geglu', geglu_phys_to_ref_rows(m.md.di, m.md.dip))
-    plan = Plan(ps, b=2, n=64, I=4, R={0: 8, 1: 4}, training=True, dp_groups=groups)
-    return m, ps, plan
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))                # (also in the spawned workers)
+    from _plan_digest import cpu_plan
+    return cpu_plan(depth=depth, dp_groups=groups)
 
 
 def _grad_pointers(item, lo, hi):
@@ -140,7 +131,7 @@ def _grad_pointers(item, lo, hi):
         vals = [v for v in a if isinstance(v, int)]
     elif isinstance(a, ctypes.Structure):
         vals = [getattr(a, f) for f, t in a._fields_ if t is ctypes.c_void_p and getattr(a, f)]
-        # argument structs passed by address (fused launches) ride in the positional form above; nested structs are kept alive in plan._keep
+        # argument structs passed by address (fused launches) ride in the positional form above; the list keeps them alive (LaunchList.keep)
     return [v for v in vals if lo <= v < hi]
 
 
@@ -148,7 +139,6 @@ def test_real_plan_cuts_leave_exchanged_ranges_untouched():
     """with the overlapped exchange a layer group's gradient ranges go out at `Plan.bwd_cuts`; nothing the backward list launches
     AFTER a cut may write into a range that left at or before it.  Checked on the product's own launch list (built on the CPU), including the
     structs the fused launches reference by address and the AttentionResidual source table (its gradients land in the tail by construction)."""
-    import ctypes
     from transfusion_pytorch_amd import capi
     from transfusion_pytorch_amd.optim import GradReducer
     m, ps, plan = _cpu_plan()
@@ -156,15 +146,12 @@ def test_real_plan_cuts_leave_exchanged_ranges_untouched():
     base = ps.grad.data_ptr(); lo, hi = base, base + 4 * ps.numel
     assert [c[1:] for c in plan.bwd_cuts] == [(4, 4), (2, 3), (0, 1)]              # depth 5 in 3 groups of <= 2 layers, last group first
     # structs referenced by address from positional launches (tfx_attnres_pull_bwd, tfx_adaln_pre_post_bwd, ...)
-    by_addr = {ctypes.addressof(k): k for k in getattr(plan, '_keep', []) if isinstance(k, ctypes.Structure)}
+    from _plan_digest import nested_structs
     def pointers(idx):
         item = plan.bwd[idx]
         out = _grad_pointers(item, lo, hi)
-        fn, a = item
-        if isinstance(a, (tuple, list)):
-            for v in a:
-                if isinstance(v, int) and v in by_addr:
-                    out += _grad_pointers(('', by_addr[v]), lo, hi)
+        for s in nested_structs(item):
+            out += _grad_pointers(('', s), lo, hi)
         return out
     sent = []
     cuts = {idx: (first, last) for idx, first, last in plan.bwd_cuts}

@@ -6,29 +6,19 @@ import os
 import sys
 
 import pytest
-import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from transfusion_pytorch_amd import capi
+from _plan_digest import cpu_plan  # noqa: E402
 
 REC = capi.STRUCTS['tfx_gemm_tn_args']
 
 
 def _cpu_plan(tn_defer, depth=5, groups=3):
     """a real training Plan built on the CPU (nothing is launched): the lists and tables are the product's own"""
-    from transfusion_pytorch_amd import Transfusion
-    from transfusion_pytorch_amd.engine import Plan
-    from transfusion_pytorch_amd.params import geglu_phys_to_ref_rows
-    torch.manual_seed(0)
-    m = Transfusion(num_text_tokens=16, dim_latent=(32, 8), transformer=dict(dim=64, depth=depth, heads=1))
-    ps = m.store
-    ps.grad = torch.zeros(ps.numel)
-    ps.shadows = collections.defaultdict(lambda: torch.zeros(8, 8, dtype=torch.bfloat16))
-    ps._map('geglu', geglu_phys_to_ref_rows(m.md.di, m.md.dip))
-    plan = Plan(ps, b=2, n=64, I=4, R={0: 8, 1: 4}, training=True, dp_groups=groups, tn_defer=tn_defer)
-    return m, ps, plan
+    return cpu_plan(depth=depth, dp_groups=groups, tn_defer=tn_defer)
 
 
 def _records(tab, n):

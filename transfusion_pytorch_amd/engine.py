@@ -10,6 +10,7 @@ from __future__ import annotations
 import ctypes
 import os
 import weakref
+from types import SimpleNamespace
 
 import torch
 
@@ -94,7 +95,22 @@ class LaunchList(list):
     model_output_clean launch) is re-packed on every replay."""
     _image = None
     _graphs = None
-    meta = None              # {list index: (family, algorithmic work)} - bookkeeping for bench.py's per-family roofline (HBM-bound launches: bytes)
+
+    def __init__(self, *items):
+        super().__init__(*items)
+        self.meta = {}       # {list index: (family, algorithmic work)} - bookkeeping for bench.py's per-family roofline (HBM-bound launches: bytes)
+        self.keep = []       # args structs the list's items pass BY ADDRESS (the fused token-wise launches): they live as long as the list
+        # what the plan's setters rewrite in place between replays (Plan.set_segments / set_rope_tables / set_rows), registered by whoever appends the item:
+        # 'seg' -> [args struct with n_seg], 'rope' -> [(args struct, cos field, sin field)], ('rows', type) -> [(object, field or list index)]
+        self.patch = {}
+
+    def by_address(self, *structs):
+        """addresses of args structs for a launch that takes them by pointer (None stays NULL); the list keeps them alive"""
+        self.keep += [a for a in structs if a is not None]
+        return [ctypes.addressof(a) if a is not None else None for a in structs]
+
+    def patched(self, kind, entry):
+        self.patch.setdefault(kind, []).append(entry)
 
     def graph(self, lo: int, hi: int):
         """hipGraph of launches[lo:hi] (created on first use).  Only for lists whose kernel arguments are fixed pointers / sizes between
@@ -198,6 +214,25 @@ class LaunchList(list):
         return self._image[1]
 
 
+class _BwdBuild:
+    """what one build of a backward list carries from stage to stage (Plan._build_backward)"""
+
+    def __init__(self, plan):
+        ps, fz = plan.ps, plan._frozen
+        # frozen parameters (`requires_grad_(False)`, select_frozen): `tr(name)` - the parameter trains; `gpn` - its gradient's address, or NULL, which the
+        # token-wise kernels read as "this sum is not formed" (tfx.h).  A weight-gradient product whose target is frozen is not in the list at all.
+        self.fz = fz
+        self.tr = lambda name: name not in fz
+        self.gpn = lambda name: ps.grad_ptr(name) if name not in fz else None
+        self.low = plan._lowest_consumer()[0]
+        self.ada = plan._time_cond_trains() or any(self.tr(n) for n in ps.params if '.to_film.' in n or '.to_ada_ln_zero.' in n)
+        self.src = skip_sources(plan.md)        # U-Net skips: late layer -> the early layer whose input it pops
+        self.pushed = set(self.src.values())
+        self.run_low = plan._tn_runs(self.low)
+        self.pending = []                       # deferred weight-gradient products waiting for their run's table launch
+        self.g = plan.gfin                      # the chain gradient as the layers hand it down
+
+
 class Plan:
     def __init__(self, ps: ParamStore, b: int, n: int, I: int, R: dict, training: bool = True, cache=None, dp_groups: int = 0, tile_attn: bool = False, units=None, ctl_rows: int = 2, tn_defer=None, ckpt: bool = False):
         """cache: None, or a KV cache tensor [depth, b, maxlen, 2*heads*64] (k~ | v per token).  With a cache the plan is a
@@ -209,6 +244,7 @@ class Plan:
         ckpt: ACTIVATION CHECKPOINTING (training plans; Transfusion.set_activation_checkpointing_): the per-layer activation family lives in `n_slots`
         slots instead of one entry per layer, and the backward list recomputes a layer into its slot in front of the layer's backward launches."""
         md = ps.md
+        self.training = training
         self.ckpt = bool(ckpt) and training
         # the side stream's weight-gradient GEMMs read a layer's saved activations one layer behind the data-gradient chain: two slots by layer parity
         # there, one on a single stream
@@ -223,17 +259,44 @@ class Plan:
         self.tile_attn = tile_attn
         assert cache is None or not training
         self.dp_groups = dp_groups          # > 0: the backward list is cut into that many layer groups for the overlapped gradient all-reduce (optim.GradReducer)
-        self.bwd_cuts = []                  # [(list index, first layer of the group, last layer of the group)], in backward order
+        self.bwd_cuts = []                  # (training plans: _build_backward)
         self.tn_defer = tn_defer            # layers per deferred weight-gradient table launch: None = TFX_TN_DEFER / the default rule, 0 = per-layer groups, N, 'all' (_tn_run_length)
         self.ps, self.md, self.b, self.n, self.I, self.R = ps, md, b, n, I, dict(R)
-        self.T = T = b * n
-        dev = ps.device
-        d, hd, D, dip, ldq, nt3 = md.dim, md.hdk, md.depth, md.dip, md.ldq, md.nt3
+        self.T = b * n
         self.nbytes = 0                     # device bytes this plan owns (the plan cache evicts by total size, Transfusion._plan)
-        def z(*s, dtype=BF16):
-            t = torch.zeros(*s, device=dev, dtype=dtype); self.nbytes += t.numel() * t.element_size(); return t
-        def e(*s, dtype=BF16):
-            t = torch.empty(*s, device=dev, dtype=dtype); self.nbytes += t.numel() * t.element_size(); return t
+        # AttentionResidual backward in pull form (tfx_attnres_pull_bwd): every layer's depth softmax is kept per token by the forward.
+        # Outside pull_form_ok the list keeps the push form (tfx_attnres_bwd: one read-modify-write sweep over all earlier hiddens per layer)
+        self.pull = training and pull_form_ok(md)
+        self.fwd, self.bwd = LaunchList(), LaunchList()
+        self.vel = LaunchList()                         # optional launches: velocity-consistency MSE against an EMA teacher's flows (T:3394-3418)
+        self.rec = LaunchList()                         # optional launches: reconstruction loss on the same predictions (MP:177-200, T:2840-2853)
+        self.tap0, self.taps, self._tap_buf = None, {}, {}   # hidden taps (set_taps): the launches of a tap at x_0, this step's taps, their buffers
+        self.noise_args, self._mse_args, self._vel_args, self._rec_args = {}, {}, {}, {}      # per native type: the args of its noising launch and of its loss targets
+        self._clean_launch, self.clean_mode = {}, ('model' if cache is not None else 'latent')
+        self.loaded_structure = None
+        self.cos_tab = self.sin_tab = None
+        self._n_seg = 0
+        self._bwd_sets = {}                 # frozen set -> what its backward list owns (_BWD_STATE; select_frozen)
+        self._alloc_forward(ctl_rows)
+        self._build_forward()
+        if training:
+            self._alloc_backward()
+            self._frozen, self._src_tab = frozenset(), None
+            self._lora, self._lora_ws = (), {}               # LoRA adapters that train (ParamStore.lora.key(), select_frozen) and the workspace their launches share
+            self._build_backward()
+            self._bwd_sets[self._frozen] = {k: getattr(self, k) for k in self._BWD_STATE}
+
+    def _zeros(self, *s, dtype=BF16):
+        t = torch.zeros(*s, device=self.ps.device, dtype=dtype); self.nbytes += t.numel() * t.element_size(); return t
+
+    def _empty(self, *s, dtype=BF16):
+        t = torch.empty(*s, device=self.ps.device, dtype=dtype); self.nbytes += t.numel() * t.element_size(); return t
+
+    def _alloc_forward(self, ctl_rows):
+        """index arrays and forward activations (every plan)"""
+        md, b, n, T, I, R, units, cache, training = self.md, self.b, self.n, self.T, self.I, self.R, self.units, self.cache, self.training
+        d, hd, D, dip, ldq, nt3 = md.dim, md.hdk, md.depth, md.dip, md.ldq, md.nt3
+        z, e = self._zeros, self._empty
         I1 = max(I, 1)
         # ---- index arrays (filled per step)
         # per-token index arrays: rows of ONE int32 buffer, so that a decode step uploads its five host-built arrays
@@ -258,7 +321,6 @@ class Plan:
         # gather form of row_tok (dropped / padding rows, -1 there, clamped to row 0): the row-GATHERING GEMM operands index with it - what they read
         # for such rows is multiplied by zeros or ignored (`set_rows`)
         self.row_gat = {t: z(r, dtype=torch.int32) for t, r in R.items()} if (training and cache is None) else self.row_tok
-        self._rows_dep = {t: [] for t in R}      # per type: (object, field or list index) holding the number of REAL latent rows of the step
         # ---- forward activations
         self.hid = e(D + 1, T, d)
         self.xres = [self.hid[0]] + [e(T, d) for _ in range(D)]
@@ -269,20 +331,12 @@ class Plan:
         # A CHECKPOINTED training plan keeps per layer what the backward cannot rebuild from the layer's input - hid, xres, arsave, arerr, the soft-cap
         # plans - and holds everything else in `n_slots` slots (layer i lives in slot i % n_slots): the forward leaves the top n_slots layers in them, the
         # backward recomputes each lower layer into its slot (_build_backward).
-        nl = D if training else 1
-        nkv = D if (training or cache is None) else 1
-        self._li = (lambda i: i) if training else (lambda i: 0)
-        self._lkv = (lambda i: i) if nkv == D else (lambda i: 0)
-        if self.ckpt:
-            nl = nkv = self.n_slots
-            self._li = self._lkv = lambda i: i % nl
-        xa_shared = None if training else e(T, d)
-        if self.ckpt:
-            skips = [i for i in range(D) if md.has_skip(i)]              # (consecutive layers: the upper half of the stack)
-            xa_slot = [e(T, d) for _ in range(min(nl, len(skips)))]
-            self.xa = {i: xa_slot[i % len(xa_slot)] for i in skips}
-        else:
-            self.xa = {i: (e(T, d) if training else xa_shared) for i in range(D) if md.has_skip(i)}
+        nl = self.n_slots if self.ckpt else D if training else 1                      # entries of the per-layer family ...
+        nkv = self.n_slots if self.ckpt else D if (training or cache is None) else 1  # ... and of the projections / rotated keys
+        self._li, self._lkv = (lambda i: i % nl), (lambda i: i % nkv)                 # layer -> its entry
+        skips = [i for i in range(D) if md.has_skip(i)]                  # (consecutive layers: the upper half of the stack)
+        xa_slot = [e(T, d) for _ in range(min(nl, len(skips)) if training else 1)]
+        self.xa = {i: xa_slot[i % len(xa_slot)] for i in skips}
         self.stats = e(4, nl, T, dtype=torch.float32)         # mean_a, rstd_a, mean_f, rstd_f
         self.ua = e(nl, T, d); self.uf = e(nl, T, d)
         self.qkvg = z(nkv, T, ldq); self.qkr = e(nkv, T, 2 * hd); self.og = z(nl, T, hd) if units else e(nl, T, hd)       # (compacted plans: padding rows are never written by the attention - keep them finite)
@@ -307,10 +361,6 @@ class Plan:
         for t in self.ext_add:
             self.lat[t]['add'] = z(R[t], d)      # additive token rows: the axial positional embedding (T:1384-1403, T:3173-3176), bf16
         self.acc = z(max(8, 2 + 3 * len(md.dim_latents)), dtype=torch.float32)      # [ce sum, ce count, flow sse per type..., velocity sse per type..., weighted recon sse per type...]
-        self.tap0, self.taps, self._tap_buf = None, {}, {}   # hidden taps (set_taps): the launches of a tap at x_0, this step's taps, their buffers
-        self.vel = LaunchList()                         # optional launches: velocity-consistency MSE against an EMA teacher's flows (T:3394-3418)
-        self.rec = LaunchList()                         # optional launches: reconstruction loss on the same predictions (MP:177-200, T:2840-2853)
-        self.cos_tab = self.sin_tab = None
         # per layer: the soft-cap plan tfx_qk_norm_rope_fwd derives from the layer's QK-RMSNorm gains (tfx.h) and its attention kernels - forward
         # and, later, backward - read: polynomial degree and coefficients from the BOUND on the scores, no look at the data.  TFX_SC_PLAN=0: decide from the scores
         # Without QK-RMSNorm (md.qk_norm False) nothing bounds the scores: no plan, the attention kernels take their data-dependent form
@@ -326,58 +376,56 @@ class Plan:
             if cache is None:
                 self.vl = e(nl, T, hd)
             else:
-                side = ps.__dict__.setdefault('_laser_side', weakref.WeakValueDictionary())
+                side = self.ps.__dict__.setdefault('_laser_side', weakref.WeakValueDictionary())
                 key = (cache.data_ptr(), tuple(cache.shape), tuple(cache.stride()))
                 self.vlc = side.get(key)
                 if self.vlc is None:
                     self.vlc = e(D, cache.shape[1] * cache.shape[2], hd)          # counted in the plan that creates it
                     side[key] = self.vlc
-        self.fwd, self.bwd = LaunchList(), LaunchList()
-        self.noise_args = {}
-        self.loaded_structure = None
-        self._seg_args, self._n_seg = [], 0
         self.seg_start = z(max(T, 1), dtype=torch.int32); self.seg_len = z(max(T, 1), dtype=torch.int32)
-        # AttentionResidual backward in pull form (tfx_attnres_pull_bwd): every layer's depth softmax is kept per token by the forward.
-        # Outside pull_form_ok the list keeps the push form (tfx_attnres_bwd: one read-modify-write sweep over all earlier hiddens per layer)
-        self.pull = training and pull_form_ok(md)
         if self.pull:
             self.arsave = [e(T, i + 2, 4, dtype=torch.float32) for i in range(D)]
             self.arerr = e(D, T, d)                          # what rounding each AttentionResidual output to bf16 dropped
-        self._build_forward()
-        if training:
-            self.dH = e(D + 1, T, d)
-            self.gx = {i: e(T, d) for i in range(D) if md.has_skip(i)}; self.du = e(T, d)
-            # weight-gradient GEMMs run on a side stream one layer behind the data-gradient chain (TFX_SIDE_STREAM=0: one stream):
-            # the buffers they read are kept per wrapper and double-buffered by layer parity
-            # measured (A/B on one box): dim 512 -2 % step time; through round 5's first session dim 768 +2 % and dim 1024 +4 % (two 8-wave GEMM kernels sharing the
-            # chip cost more than the token-wise overlap gained), so the side stream stopped at dim 512.  With the one-wave weight-gradient kernels and their
-            # grouped launches it pays at every BASELINE width: dim 768 84.2 -> 83.0 ms, dim 1024 184.2 -> 181.8 ms per step (gpurun_out/ow41.txt, two rounds)
-            # (TFX_SIDE_STREAM=1 forces it on, =0 off)
-            self.side = self._side_stream(md)
-            # deferred weight gradients (round 7, _tn_run_length): the products of a RUN of layers wait for one table launch at the run's lowest layer, so what they
-            # read - dy of both wrappers, d[a|g], d[q|k|v|gates] - is kept per layer: two runs' worth (a run's buffers are reused two runs later, behind a wait
-            # for the launch that read them), or one per layer when that covers the stack
-            # (a checkpointed plan keeps the per-layer groups whatever TFX_TN_DEFER says: a table launch reads a whole run of layers' saved activations,
-            # and a slot holds one layer's)
-            self.tn_run = 0 if self.ckpt else self._tn_run_length()
-            self.tn_tables = []                 # [(index in the backward list, lowest layer, highest layer, table bytes on ps.device, records)]
-            nb = min(D, 2 * self.tn_run) if self.tn_run else (2 if self.side else 1)
-            self.dy_f = [e(T, d) for _ in range(nb)]; self.dy_a = [e(T, d) for _ in range(nb)] if (self.side or self.tn_run) else self.dy_f
-            self.dskip = {j: e(T, d) for j in set(skip_sources(md).values())}
-            self.dqkvg_p = [z(T, ldq) for _ in range(nb)]; self.dog = e(T, hd); self.do_eff = e(T, hd)
-            # d q~ | d k~: written only when the QK-norm / RoPE backward is its own launch (TFX_ATTN_QKNR=0); the fused epilogues never touch dq / dk
-            self.dqk = e(T, 2 * hd) if os.environ.get('TFX_ATTN_QKNR', '1') == '0' else None
-            self.delta = e(b, md.heads, n, dtype=torch.float32)
-            self.dag_p = [e(T, 2 * dip) for _ in range(nb)]; self.dembed = e(T, d); self.gfin = e(T, d); self.dx0 = e(T, d)
-            self.dtables = z(I1, nt3, dtype=torch.float32); self.dtab_bf = e(I1, nt3)
-            self.dcond = e(I1, 4 * d); self.dpre = e(I1, 4 * d)
-            self.onehot = e(T, md.vp)
-            self.gsink = z(64, dtype=torch.float32)          # where a frozen q_norm / k_norm gain's gradient goes (the attention epilogues take no NULL for one gain alone)
-            self.rows_in = False                             # this step hands rows of d loss / d x_0 back to PyTorch (user encoders, positional embeddings): set by the model
-            self._frozen, self._bwd_sets, self._src_tab = frozenset(), {}, None
-            self._lora, self._lora_ws = (), {}               # LoRA adapters that train (ParamStore.lora.key(), select_frozen) and the workspace their launches share
-            self._build_backward()
-            self._bwd_sets[self._frozen] = {k: getattr(self, k) for k in self._BWD_STATE}
+
+    def _alloc_backward(self):
+        """gradient buffers and the backward's fixed choices (training plans)"""
+        md, b, n, T = self.md, self.b, self.n, self.T
+        d, hd, D, dip, ldq, nt3 = md.dim, md.hdk, md.depth, md.dip, md.ldq, md.nt3
+        z, e = self._zeros, self._empty
+        I1 = max(self.I, 1)
+        self.dH = e(D + 1, T, d)
+        self.gx = {i: e(T, d) for i in range(D) if md.has_skip(i)}; self.du = e(T, d)
+        # weight-gradient GEMMs run on a side stream one layer behind the data-gradient chain (TFX_SIDE_STREAM=0: one stream):
+        # the buffers they read are kept per wrapper and double-buffered by layer parity
+        # measured (A/B on one box): dim 512 -2 % step time; through round 5's first session dim 768 +2 % and dim 1024 +4 % (two 8-wave GEMM kernels sharing the
+        # chip cost more than the token-wise overlap gained), so the side stream stopped at dim 512.  With the one-wave weight-gradient kernels and their
+        # grouped launches it pays at every BASELINE width: dim 768 84.2 -> 83.0 ms, dim 1024 184.2 -> 181.8 ms per step (gpurun_out/ow41.txt, two rounds)
+        # (TFX_SIDE_STREAM=1 forces it on, =0 off)
+        self.side = self._side_stream(md)
+        # the overlapped gradient exchange cuts the stack into groups of `group` layers (dp_groups == 0: the whole stack is the one group)
+        self.group = -(-D // self.dp_groups) if self.dp_groups > 0 else D
+        # round 5: the backward of QK-RMSNorm + RoPE rides in the epilogues of the dQ and dK/dV kernels (tfx.h tfx_attn_args.nr_*): d q~ | d k~ are never
+        # written out and read back, and the token-wise launch drops out of the layer.  TFX_ATTN_QKNR=0: its own launch
+        self.attn_qknr = os.environ.get('TFX_ATTN_QKNR', '1') != '0'
+        # deferred weight gradients (round 7, _tn_run_length): the products of a RUN of layers wait for one table launch at the run's lowest layer, so what they
+        # read - dy of both wrappers, d[a|g], d[q|k|v|gates] - is kept per layer: two runs' worth (a run's buffers are reused two runs later, behind a wait
+        # for the launch that read them), or one per layer when that covers the stack
+        # (a checkpointed plan keeps the per-layer groups whatever TFX_TN_DEFER says: a table launch reads a whole run of layers' saved activations,
+        # and a slot holds one layer's)
+        self.tn_run = 0 if self.ckpt else self._tn_run_length()
+        nb = min(D, 2 * self.tn_run) if self.tn_run else (2 if self.side else 1)
+        self.dy_f = [e(T, d) for _ in range(nb)]; self.dy_a = [e(T, d) for _ in range(nb)] if (self.side or self.tn_run) else self.dy_f
+        self.dskip = {j: e(T, d) for j in set(skip_sources(md).values())}
+        self.dqkvg_p = [z(T, ldq) for _ in range(nb)]; self.dog = e(T, hd); self.do_eff = e(T, hd)
+        # d q~ | d k~: written only when the QK-norm / RoPE backward is its own launch; the fused epilogues never touch dq / dk
+        self.dqk = None if self.attn_qknr else e(T, 2 * hd)
+        self.delta = e(b, md.heads, n, dtype=torch.float32)
+        self.dag_p = [e(T, 2 * dip) for _ in range(nb)]; self.dembed = e(T, d); self.gfin = e(T, d); self.dx0 = e(T, d)
+        self.dtables = z(I1, nt3, dtype=torch.float32); self.dtab_bf = e(I1, nt3)
+        self.dcond = e(I1, 4 * d); self.dpre = e(I1, 4 * d)
+        self.onehot = e(T, md.vp)
+        self.gsink = z(64, dtype=torch.float32)          # where a frozen q_norm / k_norm gain's gradient goes (the attention epilogues take no NULL for one gain alone)
+        self.rows_in = False                             # this step hands rows of d loss / d x_0 back to PyTorch (user encoders, positional embeddings): set by the model
 
     # ------------------------------------------------------------------------------------ helpers
     def _nt(self, lst, algo_n=None, algo_k=None, **kw):
@@ -385,14 +433,23 @@ class Plan:
         a._algo_flops = 2.0 * kw['M'] * (algo_n or kw['N']) * (algo_k or kw['K'])      # algorithmic (unpadded) work of this launch
         lst.append(('tfx_gemm_nt', a))
 
-    def _tn(self, lst, M, N, K, **kw):
-        splits = 0                # the library picks the split count from the tile count of the kernel it launches (tfx.h, gemm.hip tn_auto_splits)
+    @staticmethod
+    def _tn_problem(M, N, K, algo_n=None, **kw):
+        """one weight-gradient product dW [N, K] += A^T B over M rows: (tfx_gemm_tn_args, algorithmic flops).  splits = 0: the library picks the split
+        count from the tile count of the kernel it launches (tfx.h, gemm.hip tn_auto_splits)"""
         kw.setdefault('k_valid', K)
-        algo_n = kw.pop('algo_n', None)
-        side = kw.pop('side', False)
-        a = capi.make_args('tfx_gemm_tn_args', M=M, N=N, K=K, splits=splits, accumulate=1, alpha=1.0, **kw)
-        a._algo_flops = 2.0 * M * (algo_n or N) * kw['k_valid']
-        lst.append(Side(('tfx_gemm_tn', a)) if side else ('tfx_gemm_tn', a))
+        a = capi.make_args('tfx_gemm_tn_args', M=M, N=N, K=K, splits=0, accumulate=1, alpha=1.0, **kw)
+        return a, 2.0 * M * (algo_n or N) * kw['k_valid']
+
+    @staticmethod
+    def _put(lst, item, side=False):
+        """append a launch - on the library's side stream (`Side`) or on the caller's"""
+        lst.append(Side(item) if side else item)
+
+    def _tn(self, lst, M, N, K, side=False, **kw):
+        a, flops = self._tn_problem(M, N, K, **kw)
+        a._algo_flops = flops
+        self._put(lst, ('tfx_gemm_tn', a), side)
 
     def _tn_group(self, lst, M, problems, side=False):
         """Weight-gradient products over the same M rows as ONE launch (tfx.h group_next): `problems` = [(N, K, kwargs of _tn), ...].  The library runs the chain
@@ -402,19 +459,13 @@ class Plan:
             for (N, K, kw) in problems:
                 self._tn(lst, M, N, K, side=side, **kw)
             return
-        structs, flops = [], 0.0
-        for (N, K, kw) in problems:
-            kw = dict(kw); kw.setdefault('k_valid', K)
-            algo_n = kw.pop('algo_n', None)
-            a = capi.make_args('tfx_gemm_tn_args', M=M, N=N, K=K, splits=0, accumulate=1, alpha=1.0, **kw)
-            flops += 2.0 * M * (algo_n or N) * kw['k_valid']
-            structs.append(a)
+        structs, flops = zip(*(self._tn_problem(M, N, K, **kw) for N, K, kw in problems))
         for a, b in zip(structs, structs[1:]):
             a.group_next = ctypes.addressof(b)
         head = structs[0]
         head._chain = structs[1:]                                # (keeps the chained structs alive with the list)
-        head._algo_flops = flops
-        lst.append(Side(('tfx_gemm_tn', head)) if side else ('tfx_gemm_tn', head))
+        head._algo_flops = sum(flops, 0.0)
+        self._put(lst, ('tfx_gemm_tn', head), side)
 
     def _tn_run_length(self):
         """layers whose weight-gradient products run as ONE table launch (tfx.h `table`), 0 = the per-layer groups.  Constructor argument `tn_defer`, else
@@ -428,8 +479,7 @@ class Plan:
         if os.environ.get('TFX_TN_GROUP', '1') == '0' or md.dim > 512:
             return 0                       # (dim 768 / 1024: no A/B of the deferred form yet, and ~1 GiB of buffers per deferred layer - they keep the per-layer groups)
         d, hd, di, dip, ldq = md.dim, md.hdk, md.di, md.dip, md.ldq
-        mk = lambda N, K, lda, ldb: capi.make_args('tfx_gemm_tn_args', M=self.T, N=N, K=K, lda=lda, a_cols=lda, ldb=ldb, b_cols=ldb, ldc=K, k_valid=K, splits=0,
-                                                   accumulate=1, alpha=1.0)
+        mk = lambda N, K, lda, ldb: self._tn_problem(self.T, N, K, lda=lda, a_cols=lda, ldb=ldb, b_cols=ldb, ldc=K)[0]
         for chain in ([mk(d, di, d, dip), mk(2 * dip, d, 2 * dip, d)], [mk(d, hd, d, hd), mk(md.nqk, d, ldq, d)]):
             chain[0].group_next = ctypes.addressof(chain[1])
             out = [ctypes.c_int32(-9) for _ in range(4)]
@@ -461,10 +511,8 @@ class Plan:
         ends = (ctypes.c_int32 * n).from_buffer(host, n * rs)
         flops, tiles = 0.0, 0
         for k, (N, K, kw) in enumerate(problems):
-            kw = dict(kw); kw.setdefault('k_valid', K)
-            algo_n = kw.pop('algo_n', None)
-            a = capi.make_args('tfx_gemm_tn_args', M=M, N=N, K=K, splits=0, accumulate=1, alpha=1.0, **kw)
-            flops += 2.0 * M * (algo_n or N) * kw['k_valid']
+            a, fl = self._tn_problem(M, N, K, **kw)
+            flops += fl
             ctypes.memmove(ctypes.addressof(host) + k * rs, ctypes.addressof(a), rs)
             tiles += -(-N // 256) * -(-K // 256)
             ends[k] = tiles
@@ -474,7 +522,7 @@ class Plan:
         head.table, head.table_host, head.table_count = dev.data_ptr(), ctypes.addressof(host), n
         head._table = (host, dev)                                # (keeps both copies alive with the list)
         head._algo_flops = flops
-        lst.append(Side(('tfx_gemm_tn', head)) if side else ('tfx_gemm_tn', head))
+        self._put(lst, ('tfx_gemm_tn', head), side)
         return dev
 
     def _k(self, lst, fn, struct, **kw):
@@ -483,11 +531,9 @@ class Plan:
     def _raw(self, lst, fn, *args):
         lst.append((fn, args))
 
-    def _hbm(self, lst, passes, extra_bytes=0):
-        """tag the launch just appended as HBM-bound with its ALGORITHMIC traffic: `passes` sweeps of a [T, d] bf16 matrix (+ extra bytes).
+    def _hbm(self, lst, passes=0, extra_bytes=0):
+        """tag the launch just appended as HBM-bound with its ALGORITHMIC traffic: `passes` sweeps of a [T, d] bf16 matrix and / or raw bytes.
         Read by bench.py (`roofline_by_family`); no effect on the replay."""
-        if lst.meta is None:
-            lst.meta = {}
         lst.meta[len(lst) - 1] = ('hbm', passes * self.T * self.md.dim * 2 + extra_bytes)
 
     def _tab(self, i, w):
@@ -497,18 +543,14 @@ class Plan:
 
     # ------------------------------------------------------------------------------------ forward
     def _build_forward(self):
-        ps, md, T, I = self.ps, self.md, self.T, self.I
-        d, hd, D, dip, ldq, nt3, H = md.dim, md.hdk, md.depth, md.dip, md.ldq, md.nt3, md.heads
-        S = ps.shadows
-        L = self.fwd
-        pp = ps.ptr
+        ps, md, T, I, L = self.ps, self.md, self.T, self.I, self.fwd
+        d, D, nt3, S, pp = md.dim, md.depth, md.nt3, ps.shadows, ps.ptr
         if self.cache is not None:
             # decode plans: `row_src` = row_tok with the dropped rows (-1) clamped to 0, so a gather never reads out of bounds (those rows are ignored by the caller)
             self.row_src = {t: torch.zeros(r, device=self.ps.device, dtype=torch.int32) for t, r in self.R.items()}
             if self.rowbuf is not None:
                 r, M, rs = next(iter(self.R.values())), len(self.R), self.row_stride
                 self.row_src = {t: self.rowbuf[(M + k) * rs:(M + k) * rs + r] for k, t in enumerate(self.R)}
-        self._clean_launch, self.clean_mode = {}, ('model' if self.cache is not None else 'latent')
         for t, r in self.R.items():
             dl = md.dim_latents[t]; dlp = pad_to(dl, 64); lt = self.lat[t]
             if t in self.ext:     # rows from the user's encoder: scatter them into the stream
@@ -517,7 +559,8 @@ class Plan:
                 self._k(L, 'tfx_noise_mix', 'tfx_noise_mix_args', R=r, dl=dl, x=lt['x'], eps=lt['eps'], row_inst=self.row_inst[t],
                         inst_time=self.inst_time, xt=lt['xt'], ld_xt=dlp, flow=lt['flow'])
                 self.noise_args[t] = L[-1][1]
-                if dl == d:       # nn.Identity latent_to_model (T:1478): the noised rows ARE the tokens - scatter them into the stream
+                L.patched(('rows', t), (L[-1][1], 'R'))
+                if dl == d:      # nn.Identity latent_to_model (T:1478): the noised rows ARE the tokens - scatter them into the stream
                     self._raw(L, capi.lib().tfx_scatter_rows_bf16, lt['xt'].data_ptr(), dlp, d, self.hid[0].data_ptr(), d, self.row_tok[t].data_ptr(), r)
                     lt['proj'] = lt['xt']
                 elif md.model_output_clean:
@@ -531,8 +574,9 @@ class Plan:
                 else:
                     self._nt(L, algo_k=dl, A=lt['xt'], lda=dlp, B=S[f'in{t}'], ldb=dlp, M=r, N=d, K=dlp, epi=E['TFX_EPI_BF16'], C=self.hid[0], ldc=d,
                              bias=pp(f'latent_to_model_projs.{t}.bias'), rowmap=self.row_tok[t])
-            if md.model_output_clean and t not in self.ext:
-                self._clean_q(L, t, r)                    # q = model_to_latent(proj)
+            if md.model_output_clean and t not in self.ext:       # q = W proj of `_clean_flow`: one GEMM over the type's projected token rows
+                lt['q'] = torch.empty(r, dl, device=self.ps.device, dtype=torch.float32)
+                self._nt(L, A=lt['proj'], lda=lt['proj'].shape[1], B=S[f'outp{t}'], ldb=d, M=r, N=dl, K=d, epi=E['TFX_EPI_F32'], C=lt['q'], ldc=dl)
             if t in self.ext_add:     # tokens += positional embedding rows (T:3173-3176): identity GEMM, mapped RESID epilogue
                 self._nt(L, A=lt['add'], lda=d, B=S['eye'], ldb=d, M=r, N=d, K=d, epi=E['TFX_EPI_RESID'], C=self.hid[0], ldc=d,
                          R=self.hid[0], ldr=d, resid_mapped=1, rowmap=self.row_tok[t])
@@ -550,90 +594,67 @@ class Plan:
         # token-wise launches that follow each other on the same rows run as ONE launch (bit-identical to the separate kernels, tests/test_kernels_gpu.py):
         # wrapper output + next wrapper input, and the end of a layer (feed-forward output side, AttentionResidual, the next layer's input side).
         # One HBM round trip of the row instead of two / three; decode plans are launch-bound
-        fuse = True
         for i in range(D):
             p = f'transformer.layers.{i}'
             li = self._li(i)
-            tf, _ = self._tab(i, 1)
             self._layer_body(L, i, fused_pre.get(i))
-            a_postf = capi.make_args('tfx_adaln_post_args', T=T, d=d, x=self.xb[li], y=self.yf[li], out=self.hid[i + 1], tok_inst=self.tok_inst,
-                                     table=tf, ld_table=nt3, layerscale=pp(f'{p}.2.layerscale'))
+            a_postf = self._adaln_post(i, 1, self.yf[li], x=self.xb[li], out=self.hid[i + 1])
             a_ar = capi.make_args('tfx_attnres_args', T=T, d=d, L=i + 2, hiddens=self.hid, stride_h=T * d,
                                   gamma=pp(f'{p}.3.norm_keys.gamma'), pq=pp(f'{p}.3.pseudo_queries'), out=self.xres[i + 1],
                                   save=self.arsave[i] if self.pull else None, err=self.arerr[i] if self.pull else None)
-            if fuse:
-                # the end of the layer is ONE launch - feed-forward output side, AttentionResidual, and (when the next layer reads
-                # the result directly, i.e. has no U-Net skip projection in front) the next layer's attention-side AdaLN-pre
-                nxt = None
-                if i + 1 < D and not md.has_skip(i + 1):
-                    pn = f'transformer.layers.{i + 1}'
-                    nxt = capi.make_args('tfx_adaln_pre_args', T=T, d=d, x=self.xres[i + 1], u=self.ua[self._li(i + 1)], tok_inst=self.tok_inst, table=self._tab(i + 1, 0)[0],
-                                         ld_table=nt3, gamma_text=pp(f'{pn}.1.layernorm_gamma'), mean=_p(self.stats, 0, self._li(i + 1)), rstd=_p(self.stats, 1, self._li(i + 1)))
-                    fused_pre[i + 1] = nxt
-                self._keep = getattr(self, '_keep', []) + [a_postf, a_ar, nxt]
-                self._raw(L, capi.lib().tfx_layer_end_fwd, ctypes.addressof(a_postf), ctypes.addressof(a_ar), ctypes.addressof(nxt) if nxt is not None else None)
-                # x, y in; hidden i+1 out; hiddens 0..i in (the new one comes from registers); result out (+ its rounding residual and the depth softmax
-                # for the pull-form backward); next wrapper's input out
-                self._hbm(L, 3 + (i + 1) + 1 + (1 if self.pull else 0) + (1 if nxt is not None else 0), (16 * (i + 2) * T if self.pull else 0) + 8 * T)
-            else:
-                L.append(('tfx_adaln_post_fwd', a_postf))
-                L.append(('tfx_attnres_fwd', a_ar))
+            # the end of the layer is ONE launch - feed-forward output side, AttentionResidual, and (when the next layer reads
+            # the result directly, i.e. has no U-Net skip projection in front) the next layer's attention-side AdaLN-pre
+            nxt = None
+            if i + 1 < D and not md.has_skip(i + 1):
+                nxt = fused_pre[i + 1] = self._adaln_pre(i + 1, 0, self.xres[i + 1], u=self.ua[self._li(i + 1)])
+            self._raw(L, capi.lib().tfx_layer_end_fwd, *L.by_address(a_postf, a_ar, nxt))
+            # x, y in; hidden i+1 out; hiddens 0..i in (the new one comes from registers); result out (+ its rounding residual and the depth softmax
+            # for the pull-form backward); next wrapper's input out
+            self._hbm(L, 3 + (i + 1) + 1 + (1 if self.pull else 0) + (1 if nxt is not None else 0), (16 * (i + 2) * T if self.pull else 0) + 8 * T)
         self._k(L, 'tfx_rmsnorm_fwd', 'tfx_rmsnorm_args', T=T, d=d, x=self.xres[D], y=self.embed, gamma=pp('transformer.norm.gamma'))
         self._hbm(L, 2)
         self.fwd_embed_end = len(L)          # launches up to here produce `embed` (return_embed / decode paths stop here)
         self._nt(L, A=self.embed, lda=d, B=S['logits'], ldb=d, M=T, N=md.vp, K=d, algo_n=md.vocab, epi=E['TFX_EPI_F32'], C=self.logits, ldc=md.vp)   # zero pad rows: N % 4 == 0 keeps the LDS-DMA kernel
         self.fwd_logits_end = len(L)
-        if self.cache is not None:
-            # decode plans: flow prediction only (model_to_latent on the modality rows), no losses
-            for t, r in self.R.items():
-                if t in self.ext:
-                    continue
-                dl = md.dim_latents[t]; lt = self.lat[t]
-                self._nt(L, A=self.embed, lda=d, a_rowmap=self.row_src[t], B=S[f'outp{t}'], ldb=d, M=r, N=dl, K=d, epi=E['TFX_EPI_F32'], C=lt['pred'], ldc=dl)
-            if md.model_output_clean:        # decode: always the model-space form (T:2446-2456), see below
-                for t, r in self.R.items():
-                    if t not in self.ext:
-                        self._clean_flow(L, t, r)
-            self.fwd_pred_end = len(L)
-            self._chain_weight_prefetch(L)
-            return
         native = {t: r for t, r in self.R.items() if t not in self.ext}      # types whose projections / losses run here
-        for t, r in native.items():          # flow predictions first, so that a loss-free forward can stop at fwd_pred_end
-            dl = md.dim_latents[t]; lt = self.lat[t]
-            self._nt(L, A=self.embed, lda=d, a_rowmap=self.row_gat[t], B=S[f'outp{t}'], ldb=d, M=r, N=dl, K=d, epi=E['TFX_EPI_F32'], C=lt['pred'], ldc=dl)
-        if md.model_output_clean:            # pred <- (pred - noised) / max(1 - t, eps): the model predicts the clean latent (MP:100-126)
+        rows = self.row_gat if self.cache is None else self.row_src
+        for t, r in native.items():          # flow predictions first (model_to_latent on the modality rows), so that a loss-free forward can stop at fwd_pred_end
+            dl = md.dim_latents[t]
+            self._nt(L, A=self.embed, lda=d, a_rowmap=rows[t], B=S[f'outp{t}'], ldb=d, M=r, N=dl, K=d, epi=E['TFX_EPI_F32'], C=self.lat[t]['pred'], ldc=dl)
+        if md.model_output_clean:            # pred <- (pred - noised) / max(1 - t, eps): the model predicts the clean latent (MP:100-126); decode: always the model-space form (T:2446-2456)
             for t, r in native.items():
                 self._clean_flow(L, t, r)
         self.fwd_pred_end = len(L)
+        if self.cache is not None:           # decode plans: no losses
+            self._chain_weight_prefetch(L)
+            return
         self._ce_args = capi.make_args('tfx_ce_args', T=T, V=md.vocab, logits=self.logits, ld=md.vp, labels=self.labels, grad_scale=0.0,
                                        dlogits=self.dlogits, ld_d=md.vp, acc=self.acc)
         L.append(('tfx_ce_fwd_bwd', self._ce_args))
-        L.meta = L.meta or {}
-        L.meta[len(L) - 1] = ('hbm', T * md.vp * (4 + 2))                    # fp32 logits in, bf16 d logits out
-        self._mse_args = {}
+        self._hbm(L, extra_bytes=T * md.vp * (4 + 2))                        # fp32 logits in, bf16 d logits out
+        nm = len(md.dim_latents)
         for t, r in native.items():
-            dl = md.dim_latents[t]; dlp = pad_to(dl, 64); lt = self.lat[t]
-            clean = dict(row_inst=self.row_inst[t], inst_time=self.inst_time, clean_eps=float(md.clean_eps)) if md.model_output_clean else {}
-            self._mse_args[t] = capi.make_args('tfx_mse_args', R=r, dl=dl, pred=lt['pred'], ld_pred=dl, flow=lt['flow'], grad_scale=0.0,
-                                               dpred=lt['dpred'], ld_d=dlp, acc=self.acc.data_ptr() + 4 * (2 + t), **clean)
-            L.append(('tfx_mse_fwd_bwd', self._mse_args[t]))
-        self._vel_args = {}
-        for t, r in native.items():          # second target on the same prediction; dpred accumulates.  Run only when a teacher is given
-            dl = md.dim_latents[t]; dlp = pad_to(dl, 64); lt = self.lat[t]
-            lt['vel'] = torch.zeros(r, dl, device=self.ps.device, dtype=torch.float32)
-            self._vel_args[t] = capi.make_args('tfx_mse_args', R=r, dl=dl, pred=lt['pred'], ld_pred=dl, flow=lt['vel'], grad_scale=0.0,
-                                               dpred=lt['dpred'], ld_d=dlp, acc=self.acc.data_ptr() + 4 * (2 + len(md.dim_latents) + t), accumulate=1,
-                                               **(dict(row_inst=self.row_inst[t], inst_time=self.inst_time, clean_eps=float(md.clean_eps)) if md.model_output_clean else {}))
-            self.vel.append(('tfx_mse_fwd_bwd', self._vel_args[t]))
-        self._rec_args = {}
-        for t, r in native.items():          # third target on the same prediction: the reconstruction residual, per-row weights filled per step
-            dl = md.dim_latents[t]; dlp = pad_to(dl, 64); lt = self.lat[t]
+            lt = self.lat[t]
+            lt['vel'] = torch.zeros(r, md.dim_latents[t], device=self.ps.device, dtype=torch.float32)
             lt['recw'] = torch.zeros(r, device=self.ps.device, dtype=torch.float32)
-            self._rec_args[t] = capi.make_args('tfx_mse_args', R=r, dl=dl, pred=lt['pred'], ld_pred=dl, flow=lt['flow'], grad_scale=0.0,
-                                               dpred=lt['dpred'], ld_d=dlp, acc=self.acc.data_ptr() + 4 * (2 + 2 * len(md.dim_latents) + t), accumulate=1,
-                                               recon_w=lt['recw'], recon_inst=self.row_inst[t], recon_time=self.inst_time, recon_mode=0,
-                                               **(dict(row_inst=self.row_inst[t], inst_time=self.inst_time, clean_eps=float(md.clean_eps)) if md.model_output_clean else {}))
-            self.rec.append(('tfx_mse_fwd_bwd', self._rec_args[t]))
+            self._mse_args[t] = self._loss_target(L, t, 2 + t, lt['flow'])
+            # second target on the same prediction; dpred accumulates.  Run only when a teacher is given
+            self._vel_args[t] = self._loss_target(self.vel, t, 2 + nm + t, lt['vel'], accumulate=1)
+            # third target on the same prediction: the reconstruction residual, per-row weights filled per step
+            self._rec_args[t] = self._loss_target(self.rec, t, 2 + 2 * nm + t, lt['flow'], accumulate=1, recon_w=lt['recw'], recon_inst=self.row_inst[t],
+                                                  recon_time=self.inst_time, recon_mode=0)
+
+    def _loss_target(self, lst, t, slot, target, **extra):
+        """one squared-error target on type t's flow prediction, appended to `lst`: the sum into accumulator `slot`, the gradient into (or, with
+        accumulate, onto) `dpred`; `model_output_clean` models hand every target what the clean-to-flow conversion needs.  Returns the args."""
+        md, lt = self.md, self.lat[t]
+        dl = md.dim_latents[t]
+        clean = dict(row_inst=self.row_inst[t], inst_time=self.inst_time, clean_eps=float(md.clean_eps)) if md.model_output_clean else {}
+        a = capi.make_args('tfx_mse_args', R=self.R[t], dl=dl, pred=lt['pred'], ld_pred=dl, flow=target, grad_scale=0.0, dpred=lt['dpred'], ld_d=pad_to(dl, 64),
+                           acc=self.acc.data_ptr() + 4 * slot, **clean, **extra)
+        lst.append(('tfx_mse_fwd_bwd', a))
+        lst.patched(('rows', t), (a, 'R'))
+        return a
 
     def _layer_body(self, L, i, pre_done=None):
         """layer i's launches into the list `L`, from the U-Net skip projection up to and including the second feed-forward GEMM - everything but the
@@ -642,9 +663,8 @@ class Plan:
         launches on the same buffers - layer i's slot, `_li(i)` / `_lkv(i)`.  `pre_done`: the args of the attention-side AdaLN-pre when the previous
         layer's end launch has already run it (tfx_layer_end_fwd; bit-identical to the separate launch, tests/test_kernels_gpu.py) - None emits the launch."""
         ps, md, T = self.ps, self.md, self.T
-        d, hd, dip, ldq, nt3, H = md.dim, md.hdk, md.dip, md.ldq, md.nt3, md.heads
+        d, hd, dip, ldq, H = md.dim, md.hdk, md.dip, md.ldq, md.heads
         S, pp = ps.shadows, ps.ptr
-        fuse = True                       # (token-wise neighbours as one launch: see _build_forward)
         p = f'transformer.layers.{i}'
         li, lkv = self._li(i), self._lkv(i)
         x_in = self.xres[i]
@@ -654,9 +674,7 @@ class Plan:
             x_a = self.xa[i]
         else:
             x_a = x_in
-        ta, _ = self._tab(i, 0); tf, _ = self._tab(i, 1)
-        a_pre_attn = capi.make_args('tfx_adaln_pre_args', T=T, d=d, x=x_a, u=self.ua[li], tok_inst=self.tok_inst, table=ta, ld_table=nt3,
-                                    gamma_text=pp(f'{p}.1.layernorm_gamma'), mean=_p(self.stats, 0, li), rstd=_p(self.stats, 1, li))
+        a_pre_attn = self._adaln_pre(i, 0, x_a, u=self.ua[li])
         if pre_done is not None:          # already done by the previous layer's end launch (tfx_layer_end_fwd)
             assert pre_done.x == a_pre_attn.x and pre_done.u == a_pre_attn.u
         else:
@@ -667,33 +685,28 @@ class Plan:
         # decode plans (round 4): the same epilogue in the decode-step GEMM kernel, with the KV-cache append (`qk_cache`): one launch per layer
         # less in a step that is nothing but ~225 dependent launches.  Training plans keep the token-wise launch: fused there the projection grows from 150 to
         # 195 us for the 53 us launch it removes (27.50 vs 27.50 ms per step, round 4)
-        fuse_qk = self.cache is not None
-        if fuse_qk:
+        if self.cache is not None:
             # SURVEY K4 (T:946-965): QK-RMSNorm + RoPE ride in the epilogue of the [q | k | v | gates] projection (TFX_EPI_QKV_NORM_ROPE: the raw
             # projection AND q~ | k~ leave the GEMM; shapes off the decode-step kernel run as two launches inside the call), with the KV-cache append
             self._nt(L, algo_n=md.nq, A=self.ua[li], lda=d, B=S[f'qkvg{i}'], ldb=d, M=T, N=md.nqk, K=d, epi=E['TFX_EPI_QKV_NORM_ROPE'], C=self.qkvg[lkv], ldc=ldq,
                      C2=self.qkr[lkv], ldc2=2 * hd, qk_heads=H, qk_gamma_q=gam('q'), qk_gamma_k=gam('k'), qk_rot_pos=self.rot_pos, qk_cos=0, qk_sin=0,
                      qk_q_scale=md.dim_head ** -0.5, qk_norm_scale=md.dim_head ** 0.5,
                      **({'qk_plan': plan_kw['sc_plan'], 'qk_softcap': 50.0} if plan_kw else {}),
-                     **(dict(qk_cache=self.cache[i], qk_ld_cache=2 * hd, qk_cache_pos=self.cache_pos) if self.cache is not None else {}))
-            self._rope_nt_args = getattr(self, '_rope_nt_args', []) + [L[-1][1]]
-            self._laser_fwd(L, i)
-            self._k(L, 'tfx_attn_fwd' if (self.cache is None or self.tile_attn) else 'tfx_decode_attn', 'tfx_attn_args', **self._attn_kw(i))
+                     qk_cache=self.cache[i], qk_ld_cache=2 * hd, qk_cache_pos=self.cache_pos)
+            L.patched('rope', (L[-1][1], 'qk_cos', 'qk_sin'))
         else:
+            # training and prefill plans: the plain projection, then QK-RMSNorm + RoPE as a token-wise launch of its own
             self._nt(L, algo_n=md.nq, A=self.ua[li], lda=d, B=S[f'qkvg{i}'], ldb=d, M=T, N=md.nqk, K=d, epi=E['TFX_EPI_BF16'], C=self.qkvg[lkv], ldc=ldq)
-            self._qknr_separate(L, i, li, lkv, gam, plan_kw)
+            self._k(L, 'tfx_qk_norm_rope_fwd', 'tfx_qk_norm_rope_args', T=T, H=H, qkv=self.qkvg[lkv], ld_qkv=ldq, qk=self.qkr[lkv], ld_qk=2 * hd,
+                    gamma_q=gam('q'), gamma_k=gam('k'), rot_pos=self.rot_pos, cos_tab=0, sin_tab=0, q_scale=md.dim_head ** -0.5, norm_scale=md.dim_head ** 0.5, **plan_kw)
+            L.patched('rope', (L[-1][1], 'cos_tab', 'sin_tab'))
+            self._hbm(L, extra_bytes=2 * 2 * T * hd * 2)                # q, k in; q~, k~ out
+        self._laser_fwd(L, i)
+        self._k(L, 'tfx_attn_fwd' if (self.cache is None or self.tile_attn) else 'tfx_decode_attn', 'tfx_attn_args', **self._attn_kw(i))
         self._nt(L, algo_k=md.hd, A=self.og[li], lda=hd, B=S[f'out{i}'], ldb=hd, M=T, N=d, K=hd, epi=E['TFX_EPI_BF16'], C=self.ya[li], ldc=d)
-        a_post = capi.make_args('tfx_adaln_post_args', T=T, d=d, x=x_a, y=self.ya[li], out=self.xb[li], tok_inst=self.tok_inst,
-                                table=ta, ld_table=nt3, layerscale=pp(f'{p}.1.layerscale'))
-        a_pre = capi.make_args('tfx_adaln_pre_args', T=T, d=d, x=self.xb[li], u=self.uf[li], tok_inst=self.tok_inst, table=tf, ld_table=nt3,
-                               gamma_text=pp(f'{p}.2.layernorm_gamma'), mean=_p(self.stats, 2, li), rstd=_p(self.stats, 3, li))
-        if fuse:                          # both sides in one launch
-            self._keep = getattr(self, '_keep', []) + [a_post, a_pre]
-            self._raw(L, capi.lib().tfx_adaln_post_pre_fwd, ctypes.addressof(a_post), ctypes.addressof(a_pre))
-            self._hbm(L, 4, 8 * T)                                  # x, y in; out, u out
-        else:
-            L.append(('tfx_adaln_post_fwd', a_post))
-            L.append(('tfx_adaln_pre_fwd', a_pre))
+        # output side of the attention wrapper and input side of the feed-forward wrapper in one launch
+        self._raw(L, capi.lib().tfx_adaln_post_pre_fwd, *L.by_address(self._adaln_post(i, 0, self.ya[li], x=x_a, out=self.xb[li]), self._adaln_pre(i, 1, self.xb[li], u=self.uf[li])))
+        self._hbm(L, 4, 8 * T)                                      # x, y in; out, u out
         self._nt(L, algo_n=2 * md.di, A=self.uf[li], lda=d, B=S[f'ff1{i}'], ldb=d, M=T, N=2 * dip, K=d, epi=E['TFX_EPI_GEGLU'], C=self.ag[li], ldc=2 * dip,
                  C2=self.hm[li], ldc2=dip, bias=S[f'ff1b{i}'])
         self._nt(L, algo_k=md.di, A=self.hm[li], lda=dip, B=S[f'ff2{i}'], ldb=dip, M=T, N=d, K=dip, epi=E['TFX_EPI_BF16'], C=self.yf[li], ldc=d,
@@ -727,19 +740,17 @@ class Plan:
             return lambda nm: S[f'g{nm}{i}']
         return lambda nm: self.ps.ptr(f'{p}.1.fn.{nm}_norm.gamma')
 
-    def _qknr_separate(self, L, i, li, lkv, gam, plan_kw):
-        """QK-RMSNorm + RoPE as its own token-wise launch behind the plain projection, then the attention launch (decode plans; TFX_QKNR=0)"""
-        md, T, H, hd, ldq = self.md, self.T, self.md.heads, self.md.hdk, self.md.ldq
-        # decode plans: the KV-cache append (k~ | v rows at `cache_pos`, T:1005-1016) rides in the same launch - a decode step is launch-bound
-        ck = dict(cache=self.cache[i], ld_cache=2 * hd, cache_pos=self.cache_pos) if self.cache is not None else {}
-        self._k(L, 'tfx_qk_norm_rope_fwd', 'tfx_qk_norm_rope_args', T=T, H=H, qkv=self.qkvg[lkv], ld_qkv=ldq, qk=self.qkr[lkv], ld_qk=2 * hd,
-                gamma_q=gam('q'), gamma_k=gam('k'), rot_pos=self.rot_pos,
-                cos_tab=0, sin_tab=0, q_scale=md.dim_head ** -0.5, norm_scale=md.dim_head ** 0.5, **ck, **plan_kw)
-        self._rope_args = getattr(self, '_rope_args', []) + [L[-1][1]]
-        L.meta = L.meta or {}
-        L.meta[len(L) - 1] = ('hbm', 2 * 2 * T * hd * 2)                # q, k in; q~, k~ out
-        self._laser_fwd(L, i)
-        self._k(L, 'tfx_attn_fwd' if (self.cache is None or self.tile_attn) else 'tfx_decode_attn', 'tfx_attn_args', **self._attn_kw(i))
+    def _adaln_pre(self, i, w, x, **kw):
+        """tfx_adaln_pre_args of (layer i, wrapper w: 0 attention, 1 feed-forward) on the rows `x`: the wrapper's table slice, its text gain and where the
+        layer's row statistics live.  `kw`: the forward's `u`, or the backward's `du`, `dx` and gradient addresses"""
+        li = self._li(i)
+        return capi.make_args('tfx_adaln_pre_args', T=self.T, d=self.md.dim, x=x, tok_inst=self.tok_inst, table=self._tab(i, w)[0], ld_table=self.md.nt3,
+                              gamma_text=self.ps.ptr(f'transformer.layers.{i}.{w + 1}.layernorm_gamma'), mean=_p(self.stats, 2 * w, li), rstd=_p(self.stats, 2 * w + 1, li), **kw)
+
+    def _adaln_post(self, i, w, y, **kw):
+        """tfx_adaln_post_args of (layer i, wrapper w) on the branch output `y`.  `kw`: the forward's `x`, `out`, or the backward's `g`, `dy` and gradient addresses"""
+        return capi.make_args('tfx_adaln_post_args', T=self.T, d=self.md.dim, y=y, tok_inst=self.tok_inst, table=self._tab(i, w)[0], ld_table=self.md.nt3,
+                              layerscale=self.ps.ptr(f'transformer.layers.{i}.{w + 1}.layerscale'), **kw)
 
     def _laser_fwd(self, L, i):
         """LASER (T:979-983): v' = exp(c tanh(v / c)) of layer i's values for its attention - the plan's own rows, or in a decode plan every row of the
@@ -748,23 +759,12 @@ class Plan:
         if not md.laser:
             return
         if self.cache is None:
-            self._k(L, 'tfx_laser_v_fwd', 'tfx_laser_v_args', T=self.T, H=md.heads, v=_p(self.qkvg, self._lkv(i)) + 2 * 2 * hd, ld_v=md.ldq,
-                    vl=self.vl[self._li(i)], ld_vl=hd, c=md.laser)
-            rows = self.T
+            rows, v, ld_v, vl = self.T, _p(self.qkvg, self._lkv(i)) + 2 * 2 * hd, md.ldq, self.vl[self._li(i)]
         else:
             ck = self.cache[i]
-            rows = int(ck.shape[0]) * int(ck.shape[1])
-            self._k(L, 'tfx_laser_v_fwd', 'tfx_laser_v_args', T=rows, H=md.heads, v=ck.data_ptr() + 2 * hd, ld_v=2 * hd,      # raw v at column hd (byte 2 hd)
-                    vl=self.vlc[i], ld_vl=hd, c=md.laser)
-        L.meta = L.meta or {}
-        L.meta[len(L) - 1] = ('hbm', 2 * rows * hd * 2)                  # v in, v' out
-
-    def _clean_q(self, L, t, r):
-        """q = W proj of `_clean_flow`: one GEMM over the type's projected token rows"""
-        md, d = self.md, self.md.dim
-        dl = md.dim_latents[t]; lt = self.lat[t]
-        lt['q'] = torch.empty(r, dl, device=self.ps.device, dtype=torch.float32)
-        self._nt(L, A=lt['proj'], lda=lt['proj'].shape[1], B=self.ps.shadows[f'outp{t}'], ldb=d, M=r, N=dl, K=d, epi=E['TFX_EPI_F32'], C=lt['q'], ldc=dl)
+            rows, v, ld_v, vl = int(ck.shape[0]) * int(ck.shape[1]), ck.data_ptr() + 2 * hd, 2 * hd, self.vlc[i]      # raw v at column hd (byte 2 hd)
+        self._k(L, 'tfx_laser_v_fwd', 'tfx_laser_v_args', T=rows, H=md.heads, v=v, ld_v=ld_v, vl=vl, ld_vl=hd, c=md.laser)
+        self._hbm(L, extra_bytes=2 * rows * hd * 2)                      # v in, v' out
 
     def _clean_flow(self, L, t, r):
         """`model_output_clean` (T:1297).  Two conversions exist in the reference:
@@ -818,35 +818,47 @@ class Plan:
         if self.cos_tab is not None and (self.cos_tab.data_ptr() != cos_tab.data_ptr() or self.sin_tab.data_ptr() != sin_tab.data_ptr()):
             self.fwd.invalidate_graphs()                 # captured kernel arguments hold the old table pointers
         self.cos_tab, self.sin_tab = cos_tab, sin_tab
-        for a in getattr(self, '_rope_args', []):
-            a.cos_tab, a.sin_tab = cos_tab.data_ptr(), sin_tab.data_ptr()
-        for a in getattr(self, '_rope_nt_args', []):                      # projections with the fused QK-norm / RoPE epilogue
-            a.qk_cos, a.qk_sin = cos_tab.data_ptr(), sin_tab.data_ptr()
-        for a in getattr(self, '_rope_attn_args', []):                    # attention backward with the fused QK-norm / RoPE backward
-            a.nr_cos, a.nr_sin = cos_tab.data_ptr(), sin_tab.data_ptr()
+        self._patch_structure(self._lists(), seg=False)
 
     def set_segments(self, seg_start, seg_len):
         n_seg = int(seg_start.numel())
         self.seg_start[:n_seg].copy_(seg_start); self.seg_len[:n_seg].copy_(seg_len)
         self._n_seg = n_seg
-        for a in self._seg_args:
-            a.n_seg = n_seg
+        self._patch_structure(self._lists(), rope=False)
+
+    def _lists(self):
+        """every launch list this plan may still replay: the forward's, the current backward's (with a `tap0` made since) and those of the other
+        kept frozen sets.  The setters below patch what these lists registered (LaunchList.patch) - a list dropped by select_frozen takes its
+        args structs with it."""
+        states = [{k: getattr(self, k, None) for k in self._BWD_LISTS}] + [st for st in self._bwd_sets.values() if st['bwd'] is not self.bwd]
+        return [self.fwd, self.vel, self.rec] + [st[k] for st in states for k in self._BWD_LISTS if st[k] is not None]
+
+    def _patch_structure(self, lists, rope=True, seg=True):
+        """write the loaded batch structure's rotary tables (the QK-norm / RoPE launches, the projections and the attention backward that carry them in
+        their epilogues) and segment count into the args of `lists`"""
+        cs = (self.cos_tab.data_ptr(), self.sin_tab.data_ptr()) if rope and self.cos_tab is not None else None
+        for L in lists:
+            if cs is not None:
+                for a, cos, sin in L.patch.get('rope', ()):
+                    setattr(a, cos, cs[0]); setattr(a, sin, cs[1])
+            if seg:
+                for a in L.patch.get('seg', ()):
+                    a.n_seg = self._n_seg
 
     def set_rows(self, R_true: dict):
         """latent rows of this step, per type (<= the plan's capacity `R`: training plans are built for row counts rounded up, so that ragged batches
         share them).  Rows past the real ones scatter nowhere (row_tok = -1) and gather row 0 (row_gat); the kernels whose RESULT would see them -
         the noising, the flow losses, the bias column sum - run over the real rows only, and the operands the weight-gradient GEMMs still
         multiply them with (xt, dpred) are zero there."""
+        lists = self._lists()
         for t, r in R_true.items():
             assert r <= self.R[t]
-            for obj, key in [(self.noise_args.get(t), 'R'), (getattr(self, '_mse_args', {}).get(t), 'R'), (getattr(self, '_vel_args', {}).get(t), 'R'),
-                             (getattr(self, '_rec_args', {}).get(t), 'R'), *self._rows_dep[t]]:
-                if obj is None:
-                    continue
-                if isinstance(obj, list):
-                    obj[key] = r
-                else:
-                    setattr(obj, key, r)
+            for L in lists:
+                for obj, key in L.patch.get(('rows', t), ()):
+                    if isinstance(obj, list):
+                        obj[key] = r
+                    else:
+                        setattr(obj, key, r)
             lt = self.lat[t]
             if r < self.R[t] and 'xt' in lt:
                 lt['xt'][r:].zero_()
@@ -879,7 +891,7 @@ class Plan:
     def set_noise(self, t: int, eps_ptr):
         """noise source of modality type t for this run: a device pointer (training: x_t = t x + (1 - t) eps) or None (no noising)"""
         self.noise_args[t].eps = eps_ptr
-        if t in getattr(self, '_clean_launch', {}) and self.clean_mode == 'latent':
+        if t in self._clean_launch and self.clean_mode == 'latent':
             self._clean_launch[t][2] = eps_ptr
 
     def set_ce_vocab(self, V: int):
@@ -893,69 +905,83 @@ class Plan:
 
     # ------------------------------------------------------------------------------------ backward
     def _build_backward(self):
-        ps, md, T, I = self.ps, self.md, self.T, self.I
-        d, hd, D, di, dip, ldq, nt3, H = md.dim, md.hdk, md.depth, md.di, md.dip, md.ldq, md.nt3, md.heads
-        S = ps.shadows
-        L = self.bwd
-        pp, gp = ps.ptr, ps.grad_ptr
-        lib = capi.lib()
-        gmap = ps._maps['geglu']
-        # frozen parameters (`requires_grad_(False)`, select_frozen): `tr(name)` - the parameter trains; `gpn` - its gradient's address, or NULL, which the
-        # token-wise kernels read as "this sum is not formed" (tfx.h).  A weight-gradient product whose target is frozen is not in the list at all.
-        fz = self._frozen
-        tr = lambda name: name not in fz
-        gpn = lambda name: gp(name) if name not in fz else None
-        low, self.bwd_end = self._lowest_consumer()
+        """the backward list of the current frozen set (`_frozen`, `_lora`) into `self.bwd` - and its side lists `clean_bwd`, `ar_tail` - stage by stage
+        in list order"""
+        c = _BwdBuild(self)
+        self.bwd, self.tap0 = LaunchList(), None
+        self.bwd_cuts = []                    # [(list index, first layer of the group, last layer of the group)], in backward order
+        self.tn_tables = []                   # [(index in the backward list, lowest layer, highest layer, table bytes on ps.device, records)]
+        self.bwd_end = 0 if c.low == 'none' else None      # where a backward with no other consumer of the data gradient ends (None = the whole list): set as the build passes the place
         self._recompute = {}                  # checkpointed plans: layer -> [begin, end) of its recompute segment in this list (recompute_range)
-        ada = self._time_cond_trains() or any(tr(n) for n in ps.params if '.to_film.' in n or '.to_ada_ln_zero.' in n)
-        if low == 'none':
-            self.bwd_end = 0
-        # model-space `model_output_clean`: pred = (W embed - W proj) s, so the (already s-scaled) seed also flows, negated, through q = W proj:
-        #   d proj = -(dpred W)  ->  latent_to_model weight / bias gradients;   dW += (-dpred)^T proj.   Run before the main list when the mode is 'model'.
-        self.clean_bwd = LaunchList()
-        if md.model_output_clean:
-            C = self.clean_bwd
-            for t, r in self.R.items():
-                if t in self.ext:
-                    continue
-                dl = md.dim_latents[t]; dlp = pad_to(dl, 64); lt = self.lat[t]
-                w_out, w_in, b_in = tr(f'model_to_latent_projs.{t}.weight'), dl != d and tr(f'latent_to_model_projs.{t}.weight'), dl != d and tr(f'latent_to_model_projs.{t}.bias')
-                if not (w_out or w_in or b_in):
-                    continue
-                if 'ndpred' not in lt:                                   # (one buffer for the lists of every frozen set)
-                    lt['ndpred'] = torch.zeros(r, dlp, device=self.ps.device, dtype=BF16)
-                self._raw(C, lib.tfx_scale_bf16_copy, lt['dpred'].data_ptr(), lt['ndpred'].data_ptr(), r * dlp, -1.0)
-                if w_out:
-                    self._tn(C, r, dl, d, A=lt['ndpred'], lda=dlp, a_cols=dlp, B=lt['proj'], ldb=lt['proj'].shape[1], b_cols=d,
-                             C=gp(f'model_to_latent_projs.{t}.weight'), ldc=d)
-                if w_in or b_in:
-                    if 'dpx' not in lt:
-                        lt['dpx'] = torch.empty(r, d, device=self.ps.device, dtype=BF16)
-                    self._nt(C, algo_k=dl, A=lt['ndpred'], lda=dlp, B=S[f'outp_t{t}'], ldb=dlp, M=r, N=d, K=dlp, epi=E['TFX_EPI_BF16'], C=lt['dpx'], ldc=d)
-                    if w_in:
-                        self._tn(C, r, d, dl, A=lt['dpx'], lda=d, a_cols=d, B=lt['xt'], ldb=dlp, b_cols=dlp, C=gp(f'latent_to_model_projs.{t}.weight'), ldc=dl)
-                    if b_in:
-                        self._raw(C, lib.tfx_colsum_bf16, lt['dpx'].data_ptr(), d, r, d, None, None, gp(f'latent_to_model_projs.{t}.bias'))
-        def head_tn(t=None):
-            if t is None:
-                if tr('to_text_logits.weight'):
-                    self._tn(L, T, md.vocab, d, A=self.dlogits, lda=md.vp, a_cols=md.vp, B=self.embed, ldb=d, b_cols=d, C=gp('to_text_logits.weight'), ldc=d)
-            elif tr(f'model_to_latent_projs.{t}.weight'):
-                dl = md.dim_latents[t]; dlp = pad_to(dl, 64)
-                self._tn(L, self.R[t], dl, d, A=self.lat[t]['dpred'], lda=dlp, a_cols=dlp, B=self.embed, ldb=d, b_cols=d, b_rowmap=self.row_gat[t],
+        self._pull_args = {}                  # hidden index -> its pull launch's args (hidden taps 1 .. depth set their `add` operand, set_taps)
+        self._bwd_clean_side(c)
+        self._bwd_heads_and_norm(c)
+        self._bwd_source_table(c)
+        for i in range(self.md.depth - 1, -1, -1):
+            self._bwd_layer(c, i)
+        self._sync(self.bwd, 'tfx_join', 63)       # every weight gradient is complete before the list returns
+        self._bwd_x0_tail(c)
+
+    def _sync(self, lst, op, slot):
+        """a fork / join of the side stream (nothing on a single stream)"""
+        if self.side:
+            lst.append((op, slot))
+
+    def _bwd_clean_side(self, c):
+        """model-space `model_output_clean`: pred = (W embed - W proj) s, so the (already s-scaled) seed also flows, negated, through q = W proj:
+          d proj = -(dpred W)  ->  latent_to_model weight / bias gradients;   dW += (-dpred)^T proj.   Run before the main list when the mode is 'model'."""
+        md, d, S, gp, tr, lib = self.md, self.md.dim, self.ps.shadows, self.ps.grad_ptr, c.tr, capi.lib()
+        C = self.clean_bwd = LaunchList()
+        if not md.model_output_clean:
+            return
+        for t, r in self.R.items():
+            if t in self.ext:
+                continue
+            dl = md.dim_latents[t]; dlp = pad_to(dl, 64); lt = self.lat[t]
+            w_out, w_in, b_in = tr(f'model_to_latent_projs.{t}.weight'), dl != d and tr(f'latent_to_model_projs.{t}.weight'), dl != d and tr(f'latent_to_model_projs.{t}.bias')
+            if not (w_out or w_in or b_in):
+                continue
+            if 'ndpred' not in lt:                                   # (one buffer for the lists of every frozen set)
+                lt['ndpred'] = torch.zeros(r, dlp, device=self.ps.device, dtype=BF16)
+            self._raw(C, lib.tfx_scale_bf16_copy, lt['dpred'].data_ptr(), lt['ndpred'].data_ptr(), r * dlp, -1.0)
+            if w_out:
+                self._tn(C, r, dl, d, A=lt['ndpred'], lda=dlp, a_cols=dlp, B=lt['proj'], ldb=lt['proj'].shape[1], b_cols=d,
                          C=gp(f'model_to_latent_projs.{t}.weight'), ldc=d)
-        if fz:
+            if w_in or b_in:
+                if 'dpx' not in lt:
+                    lt['dpx'] = torch.empty(r, d, device=self.ps.device, dtype=BF16)
+                self._nt(C, algo_k=dl, A=lt['ndpred'], lda=dlp, B=S[f'outp_t{t}'], ldb=dlp, M=r, N=d, K=dlp, epi=E['TFX_EPI_BF16'], C=lt['dpx'], ldc=d)
+                if w_in:
+                    self._tn(C, r, d, dl, A=lt['dpx'], lda=d, a_cols=d, B=lt['xt'], ldb=dlp, b_cols=dlp, C=gp(f'latent_to_model_projs.{t}.weight'), ldc=dl)
+                if b_in:
+                    self._raw(C, lib.tfx_colsum_bf16, lt['dpx'].data_ptr(), d, r, d, None, None, gp(f'latent_to_model_projs.{t}.bias'))
+
+    def _head_tn(self, c, t=None):
+        """weight gradient of the text head (t None) or of type t's model_to_latent, if it trains"""
+        md, d, L, gp = self.md, self.md.dim, self.bwd, self.ps.grad_ptr
+        if t is None:
+            if c.tr('to_text_logits.weight'):
+                self._tn(L, self.T, md.vocab, d, A=self.dlogits, lda=md.vp, a_cols=md.vp, B=self.embed, ldb=d, b_cols=d, C=gp('to_text_logits.weight'), ldc=d)
+        elif c.tr(f'model_to_latent_projs.{t}.weight'):
+            dl = md.dim_latents[t]; dlp = pad_to(dl, 64)
+            self._tn(L, self.R[t], dl, d, A=self.lat[t]['dpred'], lda=dlp, a_cols=dlp, B=self.embed, ldb=d, b_cols=d, b_rowmap=self.row_gat[t],
+                     C=gp(f'model_to_latent_projs.{t}.weight'), ldc=d)
+
+    def _bwd_heads_and_norm(self, c):
+        """d logits and d pred back to d embed, the heads' weight gradients, the final norm"""
+        md, T, d, D, S, L = self.md, self.T, self.md.dim, self.md.depth, self.ps.shadows, self.bwd
+        if c.fz:
             # with a frozen set the heads' weight gradients come FIRST, so that a backward with nothing trainable below the heads is this prefix of the
             # list (`bwd_end`); with nothing frozen the list keeps the order it always had
-            head_tn()
+            self._head_tn(c)
             for t in self.R:
                 if t not in self.ext:
-                    head_tn(t)
-            if low == 'heads':
+                    self._head_tn(c, t)
+            if c.low == 'heads':
                 self.bwd_end = len(L)
         self._nt(L, algo_k=md.vocab, A=self.dlogits, lda=md.vp, B=S['logits_t'], ldb=md.vp, M=T, N=d, K=md.vp, epi=E['TFX_EPI_BF16'], C=self.dembed, ldc=d)
-        if not fz:
-            head_tn()
+        if not c.fz:
+            self._head_tn(c)
         for t, r in self.R.items():
             dl = md.dim_latents[t]; dlp = pad_to(dl, 64); lt = self.lat[t]
             if t in self.ext:     # d loss / d (embedding rows handed to the user's decoder), from autograd: dembed[row_tok] += gemb
@@ -964,281 +990,300 @@ class Plan:
                 continue
             self._nt(L, algo_k=dl, A=lt['dpred'], lda=dlp, B=S[f'outp_t{t}'], ldb=dlp, M=r, N=d, K=dlp, epi=E['TFX_EPI_RESID'], C=self.dembed, ldc=d,
                      R=self.dembed, ldr=d, resid_mapped=1, rowmap=self.row_tok[t])
-            if not fz:
-                head_tn(t)
+            if not c.fz:
+                self._head_tn(c, t)
         self.tap_final = len(L)               # hidden tap depth + 1 (the final norm's output): its gradient joins `dembed` in front of this launch (run_bwd)
-        self._k(L, 'tfx_rmsnorm_bwd', 'tfx_rmsnorm_args', T=T, d=d, x=self.xres[D], gamma=pp('transformer.norm.gamma'), dy=self.dembed,
-                dx=self.gfin, dgamma=gpn('transformer.norm.gamma'))
+        self._k(L, 'tfx_rmsnorm_bwd', 'tfx_rmsnorm_args', T=T, d=d, x=self.xres[D], gamma=self.ps.ptr('transformer.norm.gamma'), dy=self.dembed,
+                dx=self.gfin, dgamma=c.gpn('transformer.norm.gamma'))
         self._hbm(L, 3)
-        if low == 'norm':
+        if c.low == 'norm':
             self.bwd_end = len(L)
-        src = skip_sources(md)
-        pushed = set(src.values())
-        g = self.gfin
-        side = self.side
-        def sync(op, slot):
-            if side:
-                L.append((op, slot))
-        pull = self.pull
-        if pull:
-            # pull-form AttentionResidual backward: one source record per layer (device array, lowest layer first) - the FINAL gradient of the
-            # layer's AttentionResidual output (the backward's last write to that buffer), its saved softmax state, its w = (1 + gamma) pq
-            if not hasattr(self, 'dsum'):                                                        # (shared by the lists of every frozen set: one runs at a time)
-                self.dsum = torch.empty(D, T, device=ps.device, dtype=torch.float32)
-                self.wtab = torch.empty(2, D, d, device=ps.device, dtype=torch.float32)          # w rows | d w accumulators
-                self.nbytes += self.dsum.numel() * 4 + self.wtab.numel() * 4
-            SRC = capi.STRUCTS['tfx_attnres_src']
-            recs = (SRC * D)()
-            for j in range(D):
-                pj = f'transformer.layers.{j}.3'
-                gj = self.gfin if j == D - 1 else (self.gx[j + 1] if md.has_skip(j + 1) else self.dH[j + 2])
-                for k, v in dict(g=gj, save=self.arsave[j], dsum=self.dsum[j], w=self.wtab[0, j], dw=self.wtab[1, j], gamma=pp(f'{pj}.norm_keys.gamma'),
-                                 pq=pp(f'{pj}.pseudo_queries'), dgamma=gpn(f'{pj}.norm_keys.gamma'), dpq=gpn(f'{pj}.pseudo_queries'), L=j + 2).items():
-                    setattr(recs[j], k, v.data_ptr() if hasattr(v, 'data_ptr') else v)
-            raw = torch.frombuffer(bytearray(ctypes.string_at(ctypes.addressof(recs), ctypes.sizeof(recs))), dtype=torch.uint8)
-            self._src_tab = raw.to(ps.device)
-            self._src_size = ctypes.sizeof(SRC)
-            self._raw(L, lib.tfx_attnres_prep, self._src_tab.data_ptr(), D, d)
-        self._pull_args = {}                  # hidden index -> its pull launch's args (hidden taps 1 .. depth set their `add` operand, set_taps)
-        def pull_launch(l, out_own, add, dh, post, j0=None, lst=None):
-            """gradient of hidden l from the layers j >= max(l - 1, 0) that mixed it (+ the output side `post` of the wrapper that produced the hidden).
-            d w of those layers accumulates inside the launch for few narrow sources; otherwise the launch exports the per-token coefficients and
-            one weight-gradient GEMM K1^T . h adds them (rows j0.. of the d w table are contiguous)"""
-            tail = j0 is not None              # (`ar_tail` below: only the d w of the sources j0 .. D - 1 is wanted, into the list `lst`)
-            lst = L if lst is None else lst
-            j0 = max(l - 1, 0) if j0 is None else j0
-            ns = D - j0
-            export = ns > 8 or d > 512
-            if export and not hasattr(self, 'k1buf'):
-                self.k1buf = torch.zeros(T, 32, device=ps.device, dtype=BF16); self.nbytes += self.k1buf.numel() * 2
-            a = capi.make_args('tfx_attnres_pull_args', T=T, d=d, l=l, n_src=ns, h=self.hid[l], src=self._src_tab.data_ptr() + j0 * self._src_size,
-                               out_own=out_own, out_err=self.arerr[l - 1] if out_own is not None else None, add=add, dh=dh,
-                               seg_start=self.seg_start, seg_len=self.seg_len, n_seg=0, k1=self.k1buf if export else None, ld_k1=32)
-            self._seg_args.append(a)
-            if not tail:
-                self._pull_args[l] = a
-            self._keep = getattr(self, '_keep', []) + [a, post]
-            self._raw(lst, lib.tfx_attnres_pull_bwd, ctypes.addressof(a), ctypes.addressof(post) if post is not None else None)
-            self._hbm(lst, ns + 6 if post is not None else ns + 4, 12 * ns * T)     # n_src gradient rows + h, out, err in, dh out (+ g, y in, dy out of the wrapper side); saved softmax state
-            if export:
-                self._tn(lst, T, ns, d, A=self.k1buf, lda=32, a_cols=32, B=self.hid[l], ldb=d, b_cols=d, C=self.wtab[1, j0], ldc=d)
-        run, pending = self.tn_run, []
-        run_low = {}                          # layer -> lowest layer of its run (where the run's table launch sits and its join event is recorded)
+
+    def _bwd_source_table(self, c):
+        """pull-form AttentionResidual backward: one source record per layer (device array, lowest layer first) - the FINAL gradient of the
+        layer's AttentionResidual output (the backward's last write to that buffer), its saved softmax state, its w = (1 + gamma) pq"""
+        if not self.pull:
+            return
+        md, T, d, D, ps, pp = self.md, self.T, self.md.dim, self.md.depth, self.ps, self.ps.ptr
+        if not hasattr(self, 'dsum'):                                                        # (shared by the lists of every frozen set: one runs at a time)
+            self.dsum = torch.empty(D, T, device=ps.device, dtype=torch.float32)
+            self.wtab = torch.empty(2, D, d, device=ps.device, dtype=torch.float32)          # w rows | d w accumulators
+            self.nbytes += self.dsum.numel() * 4 + self.wtab.numel() * 4
+        SRC = capi.STRUCTS['tfx_attnres_src']
+        recs = (SRC * D)()
+        for j in range(D):
+            pj = f'transformer.layers.{j}.3'
+            gj = self.gfin if j == D - 1 else (self.gx[j + 1] if md.has_skip(j + 1) else self.dH[j + 2])
+            for k, v in dict(g=gj, save=self.arsave[j], dsum=self.dsum[j], w=self.wtab[0, j], dw=self.wtab[1, j], gamma=pp(f'{pj}.norm_keys.gamma'),
+                             pq=pp(f'{pj}.pseudo_queries'), dgamma=c.gpn(f'{pj}.norm_keys.gamma'), dpq=c.gpn(f'{pj}.pseudo_queries'), L=j + 2).items():
+                setattr(recs[j], k, v.data_ptr() if hasattr(v, 'data_ptr') else v)
+        raw = torch.frombuffer(bytearray(ctypes.string_at(ctypes.addressof(recs), ctypes.sizeof(recs))), dtype=torch.uint8)
+        self._src_tab = raw.to(ps.device)
+        self._src_size = ctypes.sizeof(SRC)
+        self._raw(self.bwd, capi.lib().tfx_attnres_prep, self._src_tab.data_ptr(), D, d)
+
+    def _pull_launch(self, lst, l, out_own, add, dh, post, j0=None):
+        """gradient of hidden l from the layers j >= max(l - 1, 0) that mixed it (+ the output side `post` of the wrapper that produced the hidden), into `lst`.
+        d w of those layers accumulates inside the launch for few narrow sources; otherwise the launch exports the per-token coefficients and
+        one weight-gradient GEMM K1^T . h adds them (rows j0.. of the d w table are contiguous).
+        `j0` given (`ar_tail`): only the d w of the sources j0 .. D - 1 is wanted."""
+        T, d, D = self.T, self.md.dim, self.md.depth
+        tail = j0 is not None
+        j0 = max(l - 1, 0) if j0 is None else j0
+        ns = D - j0
+        export = ns > 8 or d > 512
+        if export and not hasattr(self, 'k1buf'):
+            self.k1buf = torch.zeros(T, 32, device=self.ps.device, dtype=BF16); self.nbytes += self.k1buf.numel() * 2
+        a = capi.make_args('tfx_attnres_pull_args', T=T, d=d, l=l, n_src=ns, h=self.hid[l], src=self._src_tab.data_ptr() + j0 * self._src_size,
+                           out_own=out_own, out_err=self.arerr[l - 1] if out_own is not None else None, add=add, dh=dh,
+                           seg_start=self.seg_start, seg_len=self.seg_len, n_seg=0, k1=self.k1buf if export else None, ld_k1=32)
+        lst.patched('seg', a)
+        if not tail:
+            self._pull_args[l] = a
+        self._raw(lst, capi.lib().tfx_attnres_pull_bwd, *lst.by_address(a, post))
+        self._hbm(lst, ns + 6 if post is not None else ns + 4, 12 * ns * T)     # n_src gradient rows + h, out, err in, dh out (+ g, y in, dy out of the wrapper side); saved softmax state
+        if export:
+            self._tn(lst, T, ns, d, A=self.k1buf, lda=32, a_cols=32, B=self.hid[l], ldb=d, b_cols=d, C=self.wtab[1, j0], ldc=d)
+
+    def _tn_runs(self, low):
+        """deferred weight gradients (`tn_run` layers per table launch): layer -> lowest layer of its run, where the run's table launch sits and its join
+        event is recorded.  Runs count down from the top of an exchange group and end with it."""
+        D, run, per, run_low = self.md.depth, self.tn_run, self.group, {}
         if run:
-            per_g = -(-D // self.dp_groups) if self.dp_groups > 0 else D
             for j in range(D - 1, -1, -1):
-                top = min((j // per_g + 1) * per_g, D) - 1
-                run_low[j] = max(top - ((top - j) // run + 1) * run + 1, j // per_g * per_g)
+                top = min((j // per + 1) * per, D) - 1
+                run_low[j] = max(top - ((top - j) // run + 1) * run + 1, j // per * per)
                 if isinstance(low, int) and j >= low:
                     run_low[j] = max(run_low[j], low)               # the products of the layers above a frozen stack launch where the truncated backward ends
-        for i in range(D - 1, -1, -1):
-            p = f'transformer.layers.{i}'
-            x_in = self.xres[i]
-            x_a = self.xa[i] if md.has_skip(i) else x_in
-            (ta, dta), (tf, dtf) = self._tab(i, 0), self._tab(i, 1)
-            if not ada:
-                dta = dtf = None                    # no trainable parameter behind the AdaLN tables: their gradient is not formed (tfx.h: dtable NULL)
-            par = self._bwd_slot(i)
-            sl = self._li(i)                        # where the layer's saved activations are: entry i, or in a checkpointed plan its slot
-            dy_f, dy_a, dag, dqkvg = self.dy_f[par], self.dy_a[par], self.dag_p[par], self.dqkvg_p[par]
-            if not run and i + 2 <= D - 1:
-                sync('tfx_join_wait', i + 2)       # this layer reuses the buffers of layer i+2: its weight gradients must have read them
-            if self.ckpt and i < D - self.n_slots:
-                # checkpointed plan: the slot still holds layer i + n_slots (the forward left the top n_slots layers in place) - the layer's forward
-                # launches again, from its kept input xres[i] (_layer_body: the launches of the forward list, with the attention side's AdaLN-pre as
-                # its own launch), up to the second feed-forward GEMM.  Not the layer's end launch: hid / xres / arsave are kept per layer and never
-                # rewritten.  On the side stream the slot is also what the weight-gradient products of layer i + 2 read: the wait above covers them.
-                lo = len(L)
-                self._layer_body(L, i)
-                self._recompute[i] = (lo, len(L))
-            if run and i + len(self.dag_p) <= D - 1:
-                sync('tfx_join_wait', run_low[i + len(self.dag_p)])      # ... of layer i + (number of buffers): the table launch of that layer's run
-            G = self.dH[i + 1]
-            a_postf = capi.make_args('tfx_adaln_post_args', T=T, d=d, y=self.yf[sl], tok_inst=self.tok_inst, table=tf, ld_table=nt3,
-                                     layerscale=pp(f'{p}.2.layerscale'), g=G, dy=dy_f, dtable=dtf, dlayerscale=gpn(f'{p}.2.layerscale'),
-                                     seg_start=self.seg_start, seg_len=self.seg_len, n_seg=0, dbias=gpn(f'{p}.2.fn.net.3.bias'))   # ff2 bias gradient = column sums of dy
-            self._seg_args.append(a_postf)
-            if pull:
-                # dH[i+1] = gradient of hidden i + 1 from the AttentionResiduals of layers i .. D-1 (all final), formed ONCE; the feed-forward
-                # wrapper's output side rides in the same launch
-                pull_launch(i + 1, self.xres[i + 1], None, G, a_postf)
-            else:
-                g2 = self.dskip[i + 1] if (i + 1) in pushed else None
-                self._k(L, 'tfx_attnres_bwd', 'tfx_attnres_args', T=T, d=d, L=i + 2, hiddens=self.hid, stride_h=T * d,
-                        gamma=pp(f'{p}.3.norm_keys.gamma'), pq=pp(f'{p}.3.pseudo_queries'), g=g, g2=capi.ptr(g2), dhiddens=self.dH, stride_dh=T * d,
-                        first=1 if i == D - 1 else 0, dgamma=gpn(f'{p}.3.norm_keys.gamma'), dpq=gpn(f'{p}.3.pseudo_queries'))
-                # ---- feedforward wrapper
-                L.append(('tfx_adaln_post_bwd', a_postf))
-            self._nt(L, algo_n=di, A=dy_f, lda=d, B=S[f'ff2_t{i}'], ldb=d, M=T, N=dip, K=d, epi=E['TFX_EPI_GEGLU_BWD'], C=dag, ldc=2 * dip,
-                     aux=self.ag[sl], ldaux=2 * dip)
-            # the weight gradients of this wrapper go to the side stream (dy_f and d[a|g] are final); net.0 carries its bias gradient
-            # (column sums of d[a|g]) folded into the same GEMM
-            if not run:
-                sync('tfx_fork', 2 * i)
-            # (round 5 tried net.3's bias gradient as this GEMM's `colsum` to free 8 registers of the pull kernel: the SUM form of the GEMM is 13 us slower per
-            # launch (158 vs 145 us, profiles/r05_shapes.txt) - and with its scale row in LDS the pull kernel no longer spills WITH the bias partials)
-            ff_grp = [(d, di, dict(A=dy_f, lda=d, a_cols=d, B=self.hm[sl], ldb=dip, b_cols=dip, C=gp(f'{p}.2.fn.net.3.weight'), ldc=di)),
-                      (2 * dip, d, dict(algo_n=2 * di, A=dag, lda=2 * dip, a_cols=2 * dip, B=self.uf[sl], ldb=d, b_cols=d, rowmap=gmap,
-                                        C=gp(f'{p}.2.fn.net.0.weight'), ldc=d, colsum=gpn(f'{p}.2.fn.net.0.bias')))]
-            if fz:
-                ff_grp = [m for m, nm in zip(ff_grp, ('net.3', 'net.0')) if tr(f'{p}.2.fn.{nm}.weight')]
-                if tr(f'{p}.2.fn.net.0.bias') and not tr(f'{p}.2.fn.net.0.weight'):
-                    # a trainable bias behind a frozen weight: its column sums of d[a|g] without the product they used to ride in
-                    self._raw(L, lib.tfx_colsum_bf16, dag.data_ptr(), 2 * dip, T, 2 * dip, gmap.data_ptr(), None, gp(f'{p}.2.fn.net.0.bias'))
-            # (one launch per LAYER - these two waiting for the attention wrapper's products - measured 4.21 -> 3.97 ms on the family and nothing on the overlapped
-            #  step, profiles/r05b_ab_tn_layer_group.txt: removed in round 6)
-            if run:
-                pending += ff_grp
-            elif ff_grp:
-                self._tn_group(L, T, ff_grp, side=side)
-            # LoRA adapters of the feed-forward matrices: where their weight-gradient products stand or would stand (dy_f, d[a|g] and the saved inputs are final)
-            self._lora_launches(L, i, 'net.3', self.hm[sl], dip, dy_f, d)
-            self._lora_launches(L, i, 'net.0', self.uf[sl], d, dag, 2 * dip)
-            self._nt(L, algo_k=2 * di, A=dag, lda=2 * dip, B=S[f'ff1_t{i}'], ldb=2 * dip, M=T, N=d, K=2 * dip, epi=E['TFX_EPI_BF16'], C=self.du, ldc=d)
-            a_pref = capi.make_args('tfx_adaln_pre_args', T=T, d=d, x=self.xb[sl], tok_inst=self.tok_inst, table=tf, ld_table=nt3,
-                                    gamma_text=pp(f'{p}.2.layernorm_gamma'), mean=_p(self.stats, 2, sl), rstd=_p(self.stats, 3, sl), du=self.du, dx=G,
-                                    dtable=dtf, dgamma_text=gpn(f'{p}.2.layernorm_gamma'), seg_start=self.seg_start, seg_len=self.seg_len, n_seg=0)
-            # ---- attention wrapper
-            a_posta = capi.make_args('tfx_adaln_post_args', T=T, d=d, y=self.ya[sl], tok_inst=self.tok_inst, table=ta, ld_table=nt3,
-                                     layerscale=pp(f'{p}.1.layerscale'), g=G, dy=dy_a, dtable=dta, dlayerscale=gpn(f'{p}.1.layerscale'),
-                                     seg_start=self.seg_start, seg_len=self.seg_len, n_seg=0)
-            self._seg_args += [a_pref, a_posta]
-            # input side of the feed-forward wrapper + output side of the attention wrapper: the residual-gradient row is written once, not read back
-            self._keep = getattr(self, '_keep', []) + [a_pref, a_posta]
-            self._raw(L, lib.tfx_adaln_pre_post_bwd, ctypes.addressof(a_pref), ctypes.addressof(a_posta))
-            self._hbm(L, 6)                                             # du, x in, residual gradient in / out, y in, dy out
-            self._nt(L, algo_n=md.hd, A=dy_a, lda=d, B=S[f'out_t{i}'], ldb=d, M=T, N=hd, K=d, epi=E['TFX_EPI_BF16'], C=self.dog, ldc=hd)
-            gam = self._gains(i)
-            # (without QK-RMSNorm the gain gradients are never written: the unread q_norm / k_norm gammas keep a zero gradient)
-            # (a frozen gain's sum goes to the plan's 64-float sink: the attention epilogues take NULL for both gains - no RMS normalisation - not for one)
-            dgam = lambda pre: {f'{pre}dgamma_{nm}': (gp(f'{p}.1.fn.{nm}_norm.gamma') if tr(f'{p}.1.fn.{nm}_norm.gamma') else self.gsink.data_ptr()) if md.qk_norm else 0
-                                for nm in 'qk'}
-            if os.environ.get('TFX_ATTN_QKNR', '1') != '0':
-                # round 5: the backward of QK-RMSNorm + RoPE rides in the epilogues of the dQ and dK/dV kernels (tfx.h tfx_attn_args.nr_*): d q~ | d k~ are never
-                # written out and read back, and the token-wise launch below drops out of the layer
-                self._k(L, 'tfx_attn_bwd', 'tfx_attn_args', **self._attn_kw(i, bwd=True), nr_qkv=self.qkvg[sl], nr_ld_qkv=ldq, nr_dqkv=dqkvg, nr_ld_dqkv=ldq,
-                        nr_gamma_q=gam('q'), nr_gamma_k=gam('k'), nr_rot_pos=self.rot_pos, nr_cos=0, nr_sin=0, nr_q_scale=md.dim_head ** -0.5,
-                        nr_norm_scale=md.dim_head ** 0.5, **dgam('nr_'))
-                # (per-block partial rows + a reduction launch instead of the 64 same-address atomics per block measured SLOWER in round 5 - 4.19 vs 4.05 ms -
-                # and were removed in round 6)
-                self._rope_attn_args = getattr(self, '_rope_attn_args', []) + [L[-1][1]]
-            else:
-                self._k(L, 'tfx_attn_bwd', 'tfx_attn_args', **self._attn_kw(i, bwd=True))
-                self._k(L, 'tfx_qk_norm_rope_bwd', 'tfx_qk_norm_rope_args', T=T, H=H, qkv=self.qkvg[sl], ld_qkv=ldq, gamma_q=gam('q'),
-                        gamma_k=gam('k'), rot_pos=self.rot_pos, cos_tab=0, sin_tab=0, q_scale=md.dim_head ** -0.5, norm_scale=md.dim_head ** 0.5,
-                        dqk=self.dqk, ld_dqk=2 * hd, dqkv=dqkvg, ld_dqkv=ldq, **dgam(''))
-                self._rope_args = getattr(self, '_rope_args', []) + [L[-1][1]]
-                L.meta = L.meta or {}
-                L.meta[len(L) - 1] = ('hbm', 3 * 2 * T * hd * 2)                # q, k (raw) in; d q~, d k~ in; d q, d k out
-            if md.laser:                # d v' -> d v in place, before the dX and weight-gradient GEMMs read the [dq | dk | dv | dgate] rows (T:979-983 backwards)
-                dv = dqkvg.data_ptr() + 2 * 2 * hd
-                self._k(L, 'tfx_laser_v_bwd', 'tfx_laser_v_args', T=T, H=H, v=_p(self.qkvg, sl) + 2 * 2 * hd, ld_v=ldq, c=md.laser,
-                        dvl=dv, ld_dvl=ldq, dv=dv, ld_dv=ldq)
-                L.meta = L.meta or {}
-                L.meta[len(L) - 1] = ('hbm', 3 * T * hd * 2)                  # v, d v' in; d v out
-            self._nt(L, algo_k=md.nq, A=dqkvg, lda=ldq, B=S[f'qkvg_t{i}'], ldb=ldq, M=T, N=d, K=ldq, epi=E['TFX_EPI_BF16'], C=self.du, ldc=d)
-            # (pull form: the gradient a U-Net skip hands to this layer's input joins here, so that G ends up as the TOTAL gradient of xres[i])
-            self._k(L, 'tfx_adaln_pre_bwd', 'tfx_adaln_pre_args', T=T, d=d, x=x_a, tok_inst=self.tok_inst, table=ta, ld_table=nt3,
-                    gamma_text=pp(f'{p}.1.layernorm_gamma'), mean=_p(self.stats, 0, sl), rstd=_p(self.stats, 1, sl), du=self.du, dx=G,
-                    dtable=dta, dgamma_text=gpn(f'{p}.1.layernorm_gamma'), seg_start=self.seg_start, seg_len=self.seg_len, n_seg=0,
-                    dx_add=self.dskip[i] if (pull and i in pushed) else None)
-            self._hbm(L, 4 + (1 if (pull and i in pushed) else 0))          # du, x in; residual gradient in / out (+ the U-Net skip's share)
-            self._seg_args.append(L[-1][1])
-            # LoRA adapters of the attention matrices (dy_a and d[q|k|v|gates] are final; to_v reads its columns of the fused gradient)
-            self._lora_launches(L, i, 'to_out', self.og[sl], hd, dy_a, d)
-            self._lora_launches(L, i, 'to_qk', self.ua[sl], d, dqkvg, ldq)
-            self._lora_launches(L, i, 'to_v', self.ua[sl], d, dqkvg.data_ptr() + 2 * 2 * hd, ldq)
-            # weight gradients of the attention wrapper (dy_a, d[q|k|v|gates] and G = dH[i+1] are final) on the side stream
-            per = -(-D // self.dp_groups) if self.dp_groups > 0 else D
-            launch = bool(run) and run_low[i] == i             # lowest layer of a run: runs count down from the top of an exchange group and end with it
-            if not run or launch:
-                sync('tfx_fork', 2 * i + 1)
-            grp = [(d, hd, dict(A=dy_a, lda=d, a_cols=d, B=self.og[sl], ldb=hd, b_cols=hd, C=gp(f'{p}.1.fn.to_out.1.weight'), ldc=md.hd,
-                                k_group=0 if md.dim_head == 64 else md.dim_head)),
-                   (md.nqk, d, dict(algo_n=md.nq, A=dqkvg, lda=ldq, a_cols=ldq, B=self.ua[sl], ldb=d, b_cols=d, C=gp(f'{p}.1.fn.to_qk.0.weight'), ldc=d,
-                                    rowmap=ps._maps['heads'] if md.dim_head != 64 else None))]
-            if fz:
-                grp = self._frozen_attn_group(grp, p)
-            if md.has_skip(i) and tr(f'{p}.0.weight'):
-                sk = self.xres[src[i]]
-                # d W_skip [d, 2 d] = G^T [x | skip]: two members of the layer's group (as ONE split-B product it measured 117.6 us against 2 x 64 us,
-                # profiles/r05b_ab_skip_tn_split.txt: the split-B form was removed in round 6)
-                grp.append((d, d, dict(A=G, lda=d, a_cols=d, B=x_in, ldb=d, b_cols=d, C=gp(f'{p}.0.weight'), ldc=2 * d)))
-                grp.append((d, d, dict(A=G, lda=d, a_cols=d, B=sk, ldb=d, b_cols=d, C=gp(f'{p}.0.weight', d), ldc=2 * d)))
-            if run:
-                # deferred: nothing reads a weight gradient before the optimizer or its group's exchange, so the run's products wait for ONE table launch at the
-                # run's lowest layer, behind the fork the per-layer launch would have used and in front of the exchange cut (a run never crosses one: `launch`
-                # is true at every i % per == 0).  dH[i + 1], the saved activations and the per-layer dy / d[a|g] / d[q|k|v|gates] buffers are not rewritten
-                # before it (the hidden taps ride in the pull launches, which write dH[l] once)
-                pending += grp
-                if launch and len(pending) == 1:                     # (a frozen set left one product of the run: the plain launch)
-                    self._tn_group(L, T, pending, side=side)
-                    pending = []
-                elif launch and pending:
-                    hi_l = max(j for j in run_low if run_low[j] == i)
-                    self.tn_tables.append((len(L), i, hi_l, self._tn_table(L, T, pending, side=side), len(pending)))
-                    pending = []
-            elif grp:
+        return run_low
+
+    def _bwd_layer(self, c, i):
+        """layer i of the backward list: (checkpointed plans: its recompute segment,) the feed-forward wrapper, the attention wrapper, the weight
+        gradients that are final with it, the exchange cut and the U-Net skip projection's data gradients"""
+        md, T, d, D, L, S, run = self.md, self.T, self.md.dim, self.md.depth, self.bwd, self.ps.shadows, self.tn_run
+        w = SimpleNamespace()                   # what the layer's stages share: its buffers, table slices and gradient G
+        w.i, w.p, w.x_in = i, f'transformer.layers.{i}', self.xres[i]
+        w.x_a = self.xa[i] if md.has_skip(i) else w.x_in
+        # (no trainable parameter behind the AdaLN tables: their gradient is not formed - tfx.h: dtable NULL)
+        w.dta, w.dtf = (self._tab(i, 0)[1], self._tab(i, 1)[1]) if c.ada else (None, None)
+        w.seg = dict(seg_start=self.seg_start, seg_len=self.seg_len, n_seg=0)      # (the segment forms of the token-wise backward kernels: set_segments)
+        par = self._bwd_slot(i)
+        w.sl = self._li(i)                      # where the layer's saved activations are: entry i, or in a checkpointed plan its slot
+        w.dy_f, w.dy_a, w.dag, w.dqkvg = self.dy_f[par], self.dy_a[par], self.dag_p[par], self.dqkvg_p[par]
+        w.launch = bool(run) and c.run_low[i] == i     # lowest layer of a run of deferred weight gradients: the run's table launch sits here
+        if not run and i + 2 <= D - 1:
+            self._sync(L, 'tfx_join_wait', i + 2)      # this layer reuses the buffers of layer i+2: its weight gradients must have read them
+        if self.ckpt and i < D - self.n_slots:
+            # checkpointed plan: the slot still holds layer i + n_slots (the forward left the top n_slots layers in place) - the layer's forward
+            # launches again, from its kept input xres[i] (_layer_body: the launches of the forward list, with the attention side's AdaLN-pre as
+            # its own launch), up to the second feed-forward GEMM.  Not the layer's end launch: hid / xres / arsave are kept per layer and never
+            # rewritten.  On the side stream the slot is also what the weight-gradient products of layer i + 2 read: the wait above covers them.
+            lo = len(L)
+            self._layer_body(L, i)
+            self._recompute[i] = (lo, len(L))
+        if run and i + len(self.dag_p) <= D - 1:
+            self._sync(L, 'tfx_join_wait', c.run_low[i + len(self.dag_p)])      # ... of layer i + (number of buffers): the table launch of that layer's run
+        w.G = self.dH[i + 1]
+        self._bwd_feedforward(c, w)
+        self._bwd_attention(c, w)
+        self._bwd_attention_weights(c, w)
+        self._bwd_adaln_group(c, i)
+        if not run or w.launch:
+            self._sync(L, 'tfx_join_record', i)
+        if self.dp_groups > 0 and i % self.group == 0:           # lowest layer of a group: every gradient of layers >= i is final
+            self._sync(L, 'tfx_join_wait', i)
+            self.bwd_cuts.append((len(L), i, min(i + self.group, D) - 1))
+        if c.low == i and c.fz:
+            # nothing below this layer trains: a backward without another consumer of the data gradient (rows PyTorch receives, hidden taps) ends
+            # here, behind a join of its own (the list's last one is further down)
+            self._sync(L, 'tfx_join', 62)
+            self.bwd_end = len(L)
+        if md.has_skip(i):
+            st = S[f'skip_t{i}']
+            self._nt(L, A=w.G, lda=d, B=st, ldb=d, M=T, N=d, K=d, epi=E['TFX_EPI_RESID'], C=self.gx[i], ldc=d, R=w.G, ldr=d)
+            self._nt(L, A=w.G, lda=d, B=st[d:], ldb=d, M=T, N=d, K=d, epi=E['TFX_EPI_BF16'], C=self.dskip[c.src[i]], ldc=d)
+            c.g = self.gx[i]
+        else:
+            c.g = w.G
+
+    def _bwd_feedforward(self, c, w):
+        """the hidden's gradient (pull form: formed here, once) and the feed-forward wrapper, down to d u of its input side"""
+        md, T, d, D, L, S, pp, gp, run = self.md, self.T, self.md.dim, self.md.depth, self.bwd, self.ps.shadows, self.ps.ptr, self.ps.grad_ptr, self.tn_run
+        di, dip, lib = md.di, md.dip, capi.lib()
+        i, p, sl, G, dy_f, dag = w.i, w.p, w.sl, w.G, w.dy_f, w.dag
+        gmap = self.ps._maps['geglu']
+        a_postf = self._adaln_post(i, 1, self.yf[sl], g=G, dy=dy_f, dtable=w.dtf, dlayerscale=c.gpn(f'{p}.2.layerscale'),
+                                   dbias=c.gpn(f'{p}.2.fn.net.3.bias'), **w.seg)                      # ff2 bias gradient = column sums of dy
+        L.patched('seg', a_postf)
+        if self.pull:
+            # dH[i+1] = gradient of hidden i + 1 from the AttentionResiduals of layers i .. D-1 (all final), formed ONCE; the feed-forward
+            # wrapper's output side rides in the same launch
+            self._pull_launch(L, i + 1, self.xres[i + 1], None, G, a_postf)
+        else:
+            g2 = self.dskip[i + 1] if (i + 1) in c.pushed else None
+            self._k(L, 'tfx_attnres_bwd', 'tfx_attnres_args', T=T, d=d, L=i + 2, hiddens=self.hid, stride_h=T * d,
+                    gamma=pp(f'{p}.3.norm_keys.gamma'), pq=pp(f'{p}.3.pseudo_queries'), g=c.g, g2=capi.ptr(g2), dhiddens=self.dH, stride_dh=T * d,
+                    first=1 if i == D - 1 else 0, dgamma=c.gpn(f'{p}.3.norm_keys.gamma'), dpq=c.gpn(f'{p}.3.pseudo_queries'))
+            L.append(('tfx_adaln_post_bwd', a_postf))
+        self._nt(L, algo_n=di, A=dy_f, lda=d, B=S[f'ff2_t{i}'], ldb=d, M=T, N=dip, K=d, epi=E['TFX_EPI_GEGLU_BWD'], C=dag, ldc=2 * dip,
+                 aux=self.ag[sl], ldaux=2 * dip)
+        # the weight gradients of this wrapper go to the side stream (dy_f and d[a|g] are final); net.0 carries its bias gradient
+        # (column sums of d[a|g]) folded into the same GEMM
+        if not run:
+            self._sync(L, 'tfx_fork', 2 * i)
+        # (round 5 tried net.3's bias gradient as this GEMM's `colsum` to free 8 registers of the pull kernel: the SUM form of the GEMM is 13 us slower per
+        # launch (158 vs 145 us, profiles/r05_shapes.txt) - and with its scale row in LDS the pull kernel no longer spills WITH the bias partials)
+        ff_grp = [(d, di, dict(A=dy_f, lda=d, a_cols=d, B=self.hm[sl], ldb=dip, b_cols=dip, C=gp(f'{p}.2.fn.net.3.weight'), ldc=di)),
+                  (2 * dip, d, dict(algo_n=2 * di, A=dag, lda=2 * dip, a_cols=2 * dip, B=self.uf[sl], ldb=d, b_cols=d, rowmap=gmap,
+                                    C=gp(f'{p}.2.fn.net.0.weight'), ldc=d, colsum=c.gpn(f'{p}.2.fn.net.0.bias')))]
+        if c.fz:
+            ff_grp = [m for m, nm in zip(ff_grp, ('net.3', 'net.0')) if c.tr(f'{p}.2.fn.{nm}.weight')]
+            if c.tr(f'{p}.2.fn.net.0.bias') and not c.tr(f'{p}.2.fn.net.0.weight'):
+                # a trainable bias behind a frozen weight: its column sums of d[a|g] without the product they used to ride in
+                self._raw(L, lib.tfx_colsum_bf16, dag.data_ptr(), 2 * dip, T, 2 * dip, gmap.data_ptr(), None, gp(f'{p}.2.fn.net.0.bias'))
+        # (one launch per LAYER - these two waiting for the attention wrapper's products - measured 4.21 -> 3.97 ms on the family and nothing on the overlapped
+        #  step, profiles/r05b_ab_tn_layer_group.txt: removed in round 6)
+        if run:
+            c.pending += ff_grp
+        elif ff_grp:
+            self._tn_group(L, T, ff_grp, side=self.side)
+        # LoRA adapters of the feed-forward matrices: where their weight-gradient products stand or would stand (dy_f, d[a|g] and the saved inputs are final)
+        self._lora_launches(L, i, 'net.3', self.hm[sl], dip, dy_f, d)
+        self._lora_launches(L, i, 'net.0', self.uf[sl], d, dag, 2 * dip)
+        self._nt(L, algo_k=2 * di, A=dag, lda=2 * dip, B=S[f'ff1_t{i}'], ldb=2 * dip, M=T, N=d, K=2 * dip, epi=E['TFX_EPI_BF16'], C=self.du, ldc=d)
+
+    def _bwd_attention(self, c, w):
+        """input side of the feed-forward wrapper, then the attention wrapper down to the layer's input gradient G"""
+        md, T, d, L, S, gp = self.md, self.T, self.md.dim, self.bwd, self.ps.shadows, self.ps.grad_ptr
+        hd, ldq, H = md.hdk, md.ldq, md.heads
+        i, p, sl, G, dy_a, dqkvg = w.i, w.p, w.sl, w.G, w.dy_a, w.dqkvg
+        a_pref = self._adaln_pre(i, 1, self.xb[sl], du=self.du, dx=G, dtable=w.dtf, dgamma_text=c.gpn(f'{p}.2.layernorm_gamma'), **w.seg)
+        a_posta = self._adaln_post(i, 0, self.ya[sl], g=G, dy=dy_a, dtable=w.dta, dlayerscale=c.gpn(f'{p}.1.layerscale'), **w.seg)
+        L.patched('seg', a_pref); L.patched('seg', a_posta)
+        # input side of the feed-forward wrapper + output side of the attention wrapper: the residual-gradient row is written once, not read back
+        self._raw(L, capi.lib().tfx_adaln_pre_post_bwd, *L.by_address(a_pref, a_posta))
+        self._hbm(L, 6)                                             # du, x in, residual gradient in / out, y in, dy out
+        self._nt(L, algo_n=md.hd, A=dy_a, lda=d, B=S[f'out_t{i}'], ldb=d, M=T, N=hd, K=d, epi=E['TFX_EPI_BF16'], C=self.dog, ldc=hd)
+        gam = self._gains(i)
+        # (without QK-RMSNorm the gain gradients are never written: the unread q_norm / k_norm gammas keep a zero gradient)
+        # (a frozen gain's sum goes to the plan's 64-float sink: the attention epilogues take NULL for both gains - no RMS normalisation - not for one)
+        dgam = lambda pre: {f'{pre}dgamma_{nm}': (gp(f'{p}.1.fn.{nm}_norm.gamma') if c.tr(f'{p}.1.fn.{nm}_norm.gamma') else self.gsink.data_ptr()) if md.qk_norm else 0
+                            for nm in 'qk'}
+        nr = dict(gamma_q=gam('q'), gamma_k=gam('k'), rot_pos=self.rot_pos, q_scale=md.dim_head ** -0.5, norm_scale=md.dim_head ** 0.5)
+        if self.attn_qknr:
+            # the QK-RMSNorm / RoPE backward in the epilogues of the dQ and dK/dV kernels (_alloc_backward)
+            self._k(L, 'tfx_attn_bwd', 'tfx_attn_args', **self._attn_kw(i, bwd=True), nr_qkv=self.qkvg[sl], nr_ld_qkv=ldq, nr_dqkv=dqkvg, nr_ld_dqkv=ldq,
+                    nr_cos=0, nr_sin=0, **{'nr_' + k: v for k, v in nr.items()}, **dgam('nr_'))
+            # (per-block partial rows + a reduction launch instead of the 64 same-address atomics per block measured SLOWER in round 5 - 4.19 vs 4.05 ms -
+            # and were removed in round 6)
+            L.patched('rope', (L[-1][1], 'nr_cos', 'nr_sin'))
+        else:
+            self._k(L, 'tfx_attn_bwd', 'tfx_attn_args', **self._attn_kw(i, bwd=True))
+            self._k(L, 'tfx_qk_norm_rope_bwd', 'tfx_qk_norm_rope_args', T=T, H=H, qkv=self.qkvg[sl], ld_qkv=ldq, cos_tab=0, sin_tab=0,
+                    dqk=self.dqk, ld_dqk=2 * hd, dqkv=dqkvg, ld_dqkv=ldq, **nr, **dgam(''))
+            L.patched('rope', (L[-1][1], 'cos_tab', 'sin_tab'))
+            self._hbm(L, extra_bytes=3 * 2 * T * hd * 2)                # q, k (raw) in; d q~, d k~ in; d q, d k out
+        if md.laser:                # d v' -> d v in place, before the dX and weight-gradient GEMMs read the [dq | dk | dv | dgate] rows (T:979-983 backwards)
+            dv = dqkvg.data_ptr() + 2 * 2 * hd
+            self._k(L, 'tfx_laser_v_bwd', 'tfx_laser_v_args', T=T, H=H, v=_p(self.qkvg, sl) + 2 * 2 * hd, ld_v=ldq, c=md.laser,
+                    dvl=dv, ld_dvl=ldq, dv=dv, ld_dv=ldq)
+            self._hbm(L, extra_bytes=3 * T * hd * 2)                    # v, d v' in; d v out
+        self._nt(L, algo_k=md.nq, A=dqkvg, lda=ldq, B=S[f'qkvg_t{i}'], ldb=ldq, M=T, N=d, K=ldq, epi=E['TFX_EPI_BF16'], C=self.du, ldc=d)
+        # (pull form: the gradient a U-Net skip hands to this layer's input joins here, so that G ends up as the TOTAL gradient of xres[i])
+        joins = self.pull and i in c.pushed
+        L.append(('tfx_adaln_pre_bwd', self._adaln_pre(i, 0, w.x_a, du=self.du, dx=G, dtable=w.dta, dgamma_text=c.gpn(f'{p}.1.layernorm_gamma'),
+                                                       dx_add=self.dskip[i] if joins else None, **w.seg)))
+        self._hbm(L, 4 + (1 if joins else 0))                       # du, x in; residual gradient in / out (+ the U-Net skip's share)
+        L.patched('seg', L[-1][1])
+        # LoRA adapters of the attention matrices (dy_a and d[q|k|v|gates] are final; to_v reads its columns of the fused gradient)
+        self._lora_launches(L, i, 'to_out', self.og[sl], hd, dy_a, d)
+        self._lora_launches(L, i, 'to_qk', self.ua[sl], d, dqkvg, ldq)
+        self._lora_launches(L, i, 'to_v', self.ua[sl], d, dqkvg.data_ptr() + 2 * 2 * hd, ldq)
+
+    def _bwd_attention_weights(self, c, w):
+        """weight gradients of the attention wrapper and the U-Net skip projection (dy_a, d[q|k|v|gates] and G = dH[i+1] are final) on the side stream -
+        as the layer's group, or (deferred) with everything pending as the table launch of the run that ends here"""
+        md, T, d, L, gp, run, side = self.md, self.T, self.md.dim, self.bwd, self.ps.grad_ptr, self.tn_run, self.side
+        hd, ldq = md.hdk, md.ldq
+        i, p, sl = w.i, w.p, w.sl
+        if not run or w.launch:
+            self._sync(L, 'tfx_fork', 2 * i + 1)
+        grp = [(d, hd, dict(A=w.dy_a, lda=d, a_cols=d, B=self.og[sl], ldb=hd, b_cols=hd, C=gp(f'{p}.1.fn.to_out.1.weight'), ldc=md.hd,
+                            k_group=0 if md.dim_head == 64 else md.dim_head)),
+               (md.nqk, d, dict(algo_n=md.nq, A=w.dqkvg, lda=ldq, a_cols=ldq, B=self.ua[sl], ldb=d, b_cols=d, C=gp(f'{p}.1.fn.to_qk.0.weight'), ldc=d,
+                                rowmap=self.ps._maps['heads'] if md.dim_head != 64 else None))]
+        if c.fz:
+            grp = self._frozen_attn_group(grp, p)
+        if md.has_skip(i) and c.tr(f'{p}.0.weight'):
+            sk = self.xres[c.src[i]]
+            # d W_skip [d, 2 d] = G^T [x | skip]: two members of the layer's group (as ONE split-B product it measured 117.6 us against 2 x 64 us,
+            # profiles/r05b_ab_skip_tn_split.txt: the split-B form was removed in round 6)
+            grp.append((d, d, dict(A=w.G, lda=d, a_cols=d, B=w.x_in, ldb=d, b_cols=d, C=gp(f'{p}.0.weight'), ldc=2 * d)))
+            grp.append((d, d, dict(A=w.G, lda=d, a_cols=d, B=sk, ldb=d, b_cols=d, C=gp(f'{p}.0.weight', d), ldc=2 * d)))
+        if not run:
+            if grp:
                 self._tn_group(L, T, grp, side=side)
-            # (a frozen stack below layer `low`: the group that holds `low` forms its products there, where the truncated backward ends, and the group
-            #  bases under it have nothing left to form)
-            if I > 0 and (i % per == 0 or i == low) and not (isinstance(low, int) and i < low):
-                # AdaLN conditioning weights (6d table columns per layer, 63 % of all parameters) of the layer GROUP that ends here: their table
-                # gradients are final once the group's backward is.  With the overlapped gradient exchange (dp_groups > 0) the weight / bias
-                # gradients are formed group by group, so that the gradient buffer completes back to front and a group's all-reduce can start
-                # during the backward; one GEMM per group (>= 768 tiles: no split, every block reduces all I instances).  Without an exchange
-                # (dp_groups == 0: one GPU, or one all-reduce after the backward) the "group" is the whole stack: ONE GEMM after layer 0
-                hi = min((i // per + 1) * per, D)
-                off, cols = i * 2 * 3 * d, (hi - i) * 2 * 3 * d
-                w_item = lambda it: L.append(Side(it) if side else it)
-                # (frozen sets: the table columns of the group's trainable to_film / to_ada_ln_zero weights and biases, as runs of adjacent columns - with
-                #  nothing frozen one run each, the launches the list always held; the bf16 cast also feeds the time conditioning's backward)
-                w_runs, b_runs = self._adaln_runs(i, hi)
-                if w_runs or self._time_cond_trains():
-                    w_item((lib.tfx_cast_block_bf16, (self.dtables.data_ptr() + 4 * off, nt3, self.dtab_bf.data_ptr() + 2 * off, nt3, I, cols)))
-                g0 = ps.grad.data_ptr() + 4 * ps.offsets['transformer.layers.0.1.to_film.weight'][0]
-                b0 = ps.grad.data_ptr() + 4 * ps.offsets['transformer.layers.0.1.to_film.bias'][0]
-                for c0, nc in w_runs:
-                    self._tn(L, I, nc, 4 * d, side=side, A=self.dtab_bf.data_ptr() + 2 * c0, lda=nt3, a_cols=nc, B=self.cond, ldb=4 * d, b_cols=4 * d,
-                             C=g0 + 4 * c0 * 4 * d, ldc=4 * d)
-                for c0, nc in b_runs:
-                    w_item((lib.tfx_colsum_f32, (self.dtables.data_ptr() + 4 * c0, nt3, I, nc, b0 + 4 * c0)))
-            if not run or launch:
-                sync('tfx_join_record', i)
-            if self.dp_groups > 0:
-                if i % per == 0:                                     # lowest layer of a group: every gradient of layers >= i is final
-                    sync('tfx_join_wait', i)
-                    self.bwd_cuts.append((len(L), i, min(i + per, D) - 1))
-            if low == i and fz:
-                # nothing below this layer trains: a backward without another consumer of the data gradient (rows PyTorch receives, hidden taps) ends
-                # here, behind a join of its own (the list's last one is further down)
-                sync('tfx_join', 62)
-                self.bwd_end = len(L)
-            if md.has_skip(i):
-                st = S[f'skip_t{i}']
-                self._nt(L, A=G, lda=d, B=st, ldb=d, M=T, N=d, K=d, epi=E['TFX_EPI_RESID'], C=self.gx[i], ldc=d, R=G, ldr=d)
-                self._nt(L, A=G, lda=d, B=st[d:], ldb=d, M=T, N=d, K=d, epi=E['TFX_EPI_BF16'], C=self.dskip[src[i]], ldc=d)
-                g = self.gx[i]
-            else:
-                g = G
-        sync('tfx_join', 63)                       # every weight gradient is complete before the list returns
-        # ---- gradient wrt the transformer input x0 = hid[0] = xres[0]
-        if pull:
-            pull_launch(0, None, g, self.dx0, None)               # hidden 0 = the transformer input: every layer mixed it; + the chain gradient g
+            return
+        # deferred: nothing reads a weight gradient before the optimizer or its group's exchange, so the run's products wait for ONE table launch at the
+        # run's lowest layer, behind the fork the per-layer launch would have used and in front of the exchange cut (a run never crosses one: `launch`
+        # is true at every i % group == 0).  dH[i + 1], the saved activations and the per-layer dy / d[a|g] / d[q|k|v|gates] buffers are not rewritten
+        # before it (the hidden taps ride in the pull launches, which write dH[l] once)
+        c.pending += grp
+        if w.launch and len(c.pending) == 1:                     # (a frozen set left one product of the run: the plain launch)
+            self._tn_group(L, T, c.pending, side=side)
+        elif w.launch and c.pending:
+            hi_l = max(j for j in c.run_low if c.run_low[j] == i)
+            self.tn_tables.append((len(L), i, hi_l, self._tn_table(L, T, c.pending, side=side), len(c.pending)))
+        if w.launch:
+            c.pending = []
+
+    def _bwd_adaln_group(self, c, i):
+        """AdaLN conditioning weights (6d table columns per layer, 63 % of all parameters) of the layer GROUP that ends at layer i: their table
+        gradients are final once the group's backward is.  With the overlapped gradient exchange (dp_groups > 0) the weight / bias
+        gradients are formed group by group, so that the gradient buffer completes back to front and a group's all-reduce can start
+        during the backward; one GEMM per group (>= 768 tiles: no split, every block reduces all I instances).  Without an exchange
+        (dp_groups == 0: one GPU, or one all-reduce after the backward) the "group" is the whole stack: ONE GEMM after layer 0."""
+        md, d, D, I, L, ps, per, low, side, lib = self.md, self.md.dim, self.md.depth, self.I, self.bwd, self.ps, self.group, c.low, self.side, capi.lib()
+        nt3 = md.nt3
+        # (a frozen stack below layer `low`: the group that holds `low` forms its products there, where the truncated backward ends, and the group
+        #  bases under it have nothing left to form)
+        if not (I > 0 and (i % per == 0 or i == low) and not (isinstance(low, int) and i < low)):
+            return
+        hi = min((i // per + 1) * per, D)
+        off, cols = i * 2 * 3 * d, (hi - i) * 2 * 3 * d
+        # (frozen sets: the table columns of the group's trainable to_film / to_ada_ln_zero weights and biases, as runs of adjacent columns - with
+        #  nothing frozen one run each, the launches the list always held; the bf16 cast also feeds the time conditioning's backward)
+        w_runs, b_runs = self._adaln_runs(i, hi)
+        if w_runs or self._time_cond_trains():
+            self._put(L, (lib.tfx_cast_block_bf16, (self.dtables.data_ptr() + 4 * off, nt3, self.dtab_bf.data_ptr() + 2 * off, nt3, I, cols)), side)
+        g0 = ps.grad.data_ptr() + 4 * ps.offsets['transformer.layers.0.1.to_film.weight'][0]
+        b0 = ps.grad.data_ptr() + 4 * ps.offsets['transformer.layers.0.1.to_film.bias'][0]
+        for c0, nc in w_runs:
+            self._tn(L, I, nc, 4 * d, side=side, A=self.dtab_bf.data_ptr() + 2 * c0, lda=nt3, a_cols=nc, B=self.cond, ldb=4 * d, b_cols=4 * d,
+                     C=g0 + 4 * c0 * 4 * d, ldc=4 * d)
+        for c0, nc in b_runs:
+            self._put(L, (lib.tfx_colsum_f32, (self.dtables.data_ptr() + 4 * c0, nt3, I, nc, b0 + 4 * c0)), side)
+
+    def _bwd_x0_tail(self, c):
+        """behind the layers: the gradient wrt the transformer input x0 = hid[0] = xres[0], the parameters that made x0, the time conditioning"""
+        md, T, d, D, I, L, S, gp, tr, lib = self.md, self.T, self.md.dim, self.md.depth, self.I, self.bwd, self.ps.shadows, self.ps.grad_ptr, c.tr, capi.lib()
+        nt3 = md.nt3
+        if self.pull:
+            self._pull_launch(L, 0, None, c.g, self.dx0, None)    # hidden 0 = the transformer input: every layer mixed it; + the chain gradient g
             self._raw(L, lib.tfx_attnres_finish, self._src_tab.data_ptr(), D, d)
         else:
-            self._raw(L, lib.tfx_add_bf16, g.data_ptr(), self.dH[0].data_ptr(), self.dx0.data_ptr(), T * d)
-            if 0 in pushed:
+            self._raw(L, lib.tfx_add_bf16, c.g.data_ptr(), self.dH[0].data_ptr(), self.dx0.data_ptr(), T * d)
+            if 0 in c.pushed:
                 self._raw(L, lib.tfx_add_bf16, self.dx0.data_ptr(), self.dskip[0].data_ptr(), self.dx0.data_ptr(), T * d)
         self.ar_tail = None
-        if fz and pull and isinstance(low, int) and any('.3.' in n for n in ps.params if n.startswith('transformer.layers.') and tr(n)):
+        if c.fz and self.pull and isinstance(c.low, int) and any('.3.' in n for n in self.ps.params if n.startswith('transformer.layers.') and tr(n)):
             # the backward ends at layer `low` (bwd_end), but d pseudo_queries / d norm_keys.gamma of a layer j sum over EVERY hidden 0 .. j + 1: the terms of
             # hiddens 0 .. low, which the pull launches below `low` would have added on their way, come from launches of their own behind the truncated list -
             # the trainable sources low .. D - 1 only, no wrapper side, the hidden's gradient into the (then unused) x_0 gradient buffer - and the closing
             # tfx_attnres_finish.  A backward that runs the whole list (rows for PyTorch, hidden taps) does not run these.
             A = self.ar_tail = LaunchList()
-            for l in range(low, -1, -1):
-                pull_launch(l, None, None, self.dx0, None, j0=low, lst=A)
+            for l in range(c.low, -1, -1):
+                self._pull_launch(A, l, None, None, self.dx0, None, j0=c.low)
             self._raw(A, lib.tfx_attnres_finish, self._src_tab.data_ptr(), D, d)
         if tr('text_embed.weight'):
             self._raw(L, lib.tfx_onehot_bf16, self.text_ids.data_ptr(), self.tok_inst.data_ptr(), self.onehot.data_ptr(), T, md.vp)
@@ -1252,6 +1297,7 @@ class Plan:
                          C=gp('transformer.to_time_cond.1.weight'), ldc=d + 1)
             if tr('transformer.to_time_cond.1.bias'):
                 self._raw(L, lib.tfx_colsum_bf16, self.dpre.data_ptr(), 4 * d, I, 4 * d, None, None, gp('transformer.to_time_cond.1.bias'))
+
 
     def _x0_param_grads(self, L, dx0):
         """from `dx0` = a gradient wrt the transformer input x_0 ([T, d] bf16): the gradients of the parameters that produced x_0 - the text embedding
@@ -1271,8 +1317,8 @@ class Plan:
             if not tr(f'latent_to_model_projs.{t}.bias'):
                 continue
             cs = [dx0.data_ptr(), d, int(self.noise_args[t].R), d, None, self.row_tok[t].data_ptr(), gp(f'latent_to_model_projs.{t}.bias')]      # (mutable: the row count follows the step)
-            self._rows_dep[t].append((cs, 2))
             L.append((lib.tfx_colsum_bf16, cs))
+            L.patched(('rows', t), (cs, 2))
 
     # ------------------------------------------------------------------------------------ LoRA adapters
     def _lora_launches(self, L, i, target, X, ldx, dY, ldy):
@@ -1315,7 +1361,8 @@ class Plan:
 
     # ------------------------------------------------------------------------------------ frozen parameters
     # what a backward list owns: one set of these per frozen set (select_frozen)
-    _BWD_STATE = ('bwd', 'bwd_cuts', 'bwd_end', 'tn_tables', 'clean_bwd', 'tap_final', 'tap0', '_pull_args', '_src_tab', 'ar_tail', '_recompute')
+    _BWD_LISTS = ('bwd', 'clean_bwd', 'ar_tail', 'tap0')
+    _BWD_STATE = _BWD_LISTS + ('bwd_cuts', 'bwd_end', 'tn_tables', 'tap_final', '_pull_args', '_src_tab', '_recompute')
     _BWD_SETS = 4               # backward lists kept per plan beside the one with nothing frozen
 
     def select_frozen(self, frozen: frozenset, lora: tuple = ()):
@@ -1332,15 +1379,11 @@ class Plan:
             while len(sets) > self._BWD_SETS:
                 sets.pop(next(k for k in sets if k))
             self._frozen, self._lora = frozen, lora
-            self.bwd, self.bwd_cuts, self.tn_tables, self.tap0 = LaunchList(), [], [], None
             self._build_backward()
             st = {k: getattr(self, k) for k in self._BWD_STATE}
             # what the loaded batch structure set in the args of the lists that existed then (a caller that meets the same structure again does not reload it)
-            if self.cos_tab is not None:
-                self.set_rope_tables(self.cos_tab, self.sin_tab)
-            for a in self._seg_args:
-                a.n_seg = self._n_seg
-        sets[key] = st                                                  # (re-)insert at the most recent position
+            self._patch_structure([st[k] for k in self._BWD_LISTS if st[k] is not None])
+        sets[key] = st                                                 # (re-)insert at the most recent position
         self._frozen, self._lora = frozen, lora
         for k, v in st.items():
             setattr(self, k, v)
