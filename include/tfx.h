@@ -434,6 +434,28 @@ typedef struct {
 } tfx_ce_args;
 int tfx_ce_fwd_bwd(const tfx_ce_args* a, void* stream);
 
+/* the same cross entropy SPLIT into a forward and a backward launch over a CHUNK of rows (engine.Plan `chunk`, Transfusion.set_text_head_chunking_): the
+ * fp32 logits of T rows at a time live in one small buffer that the forward fills and the backward fills again with the same product, so a step never
+ * holds [all rows, V] logits or their gradient.  The forward keeps one float per row - lse = log sum exp - and the backward forms the gradient from it:
+ *   tfx_ce_fwd   one pass over the row (online max / sum, 16-byte loads): lse[t] = m + log sum_c exp(l_c - m), acc[0] += sum_t (lse[t] - l[label_t]), acc[1] += #valid;
+ *                ignored rows (label -1) get lse 0 and are not read; a launch whose rows are all ignored leaves `acc` untouched.  Reads logits, labels; writes lse, acc.
+ *   tfx_ce_bwd   one pass: dlogits[t, c] = bf16((exp(l_c - lse[t]) - [c == label_t]) * grad_scale * (scale_dev ? *scale_dev : 1)), columns V .. ld_d - 1 and
+ *                ignored rows zero (bf16x8 stores).  Reads logits, labels, lse; writes dlogits.
+ * Rows of at most 1024 logits (ld) run one wave per row, four rows per block; wider rows one block per row with an LDS combine of the waves' (max, sum) pairs.
+ * Both: grid-stride over rows under a capped grid; two atomics into `acc` per block, as tfx_ce_fwd_bwd.  1 <= V <= ld, ld_d; ld and ld_d multiples of 8 and
+ * logits / dlogits 16-byte aligned, or -1. */
+typedef struct {
+  int32_t T, V; const float* logits; int32_t ld;      /* a chunk: T rows */
+  const int32_t* labels;                              /* -1 = ignore */
+  float* lse;                                         /* [T]; ignored rows get 0 */
+  float* acc;                                         /* acc[0] += sum CE, acc[1] += #valid  (as tfx_ce_fwd_bwd) */
+  /* backward */
+  float grad_scale; const float* scale_dev;           /* g *= grad_scale * (scale_dev ? *scale_dev : 1) */
+  tfx_bf16* dlogits; int32_t ld_d;                    /* pad columns V..ld_d-1 and ignored rows zeroed */
+} tfx_ce_chunk_args;
+int tfx_ce_fwd(const tfx_ce_chunk_args* a, void* stream);
+int tfx_ce_bwd(const tfx_ce_chunk_args* a, void* stream);
+
 /* fused MSE forward + backward: pred/flow fp32 [R, dl]   T:3359-3362 */
 typedef struct {
   int32_t R, dl; const float* pred; int32_t ld_pred; const float* flow;
@@ -776,11 +798,12 @@ enum { TFX_OP_GEMM_NT = 0, TFX_OP_GEMM_TN = 1, TFX_OP_ATTN_FWD = 2, TFX_OP_ATTN_
        TFX_OP_ATTNRES_BWD = 11, TFX_OP_RMSNORM_FWD = 12, TFX_OP_RMSNORM_BWD = 13, TFX_OP_EMBED_FWD = 14, TFX_OP_EMBED_BWD = 15,
        TFX_OP_NOISE_MIX = 16, TFX_OP_FOURIER = 17, TFX_OP_CE_FWD_BWD = 18, TFX_OP_MSE_FWD_BWD = 19, TFX_OP_CAST_ROWS = 20, TFX_OP_CAST_ROWS_T = 21,
        TFX_OP_ADAM_STEP = 22, TFX_OP_DECODE_ATTN = 23, TFX_OP_LASER_V_FWD = 24, TFX_OP_LASER_V_BWD = 25, TFX_OP_COSINE_FWD_BWD = 26,
-       TFX_OP_ADAM_ATAN2_STEP = 27, TFX_OP_LORA_MERGE = 28, TFX_OP_LORA_DOWN = 29, TFX_OP_LORA_GRAD = 30,
+       TFX_OP_ADAM_ATAN2_STEP = 27, TFX_OP_LORA_MERGE = 28, TFX_OP_LORA_DOWN = 29, TFX_OP_LORA_GRAD = 30, TFX_OP_CE_FWD = 31,
        /* positional entry points (args = tfx_raw_args) */
        TFX_OP_OUTPUT_TO_FLOW = 32, TFX_OP_GATHER_F32 = 33, TFX_OP_ONEHOT_BF16 = 34, TFX_OP_SCATTER_ROWS_BF16 = 35, TFX_OP_F32_TO_BF16 = 36,
        TFX_OP_SILU_BWD = 37, TFX_OP_COLSUM_BF16 = 38, TFX_OP_COLSUM_F32 = 39, TFX_OP_ADD_BF16 = 40, TFX_OP_SCALE_BF16_DEV = 41, TFX_OP_CAST_BLOCK_BF16 = 42, TFX_OP_SCALE_BF16_COPY = 43, TFX_OP_ADALN_POST_PRE_FWD = 44, TFX_OP_LAYER_END_FWD = 45,
        TFX_OP_ATTNRES_PREP = 46, TFX_OP_ATTNRES_PULL_BWD = 47, TFX_OP_ATTNRES_FINISH = 52, TFX_OP_ADALN_PRE_POST_BWD = 53,
+       TFX_OP_CE_BWD = 54,                      /* (args = tfx_ce_chunk_args, as TFX_OP_CE_FWD: the struct codes below 32 are used up) */
        /* stream control (args = any non-NULL pointer; `stream` = event slot 0..63):
           FORK: the library's side stream waits for everything enqueued so far on the caller's stream;
           JOIN_RECORD: mark "everything enqueued so far on the side stream";  JOIN_WAIT: the caller's stream waits for that mark;

@@ -32,6 +32,8 @@ inline int run_one(const tfx_launch& l, void* s) {
     case TFX_OP_NOISE_MIX:        return tfx_noise_mix(static_cast<const tfx_noise_mix_args*>(a), s);
     case TFX_OP_FOURIER:          return tfx_fourier(static_cast<const tfx_fourier_args*>(a), s);
     case TFX_OP_CE_FWD_BWD:       return tfx_ce_fwd_bwd(static_cast<const tfx_ce_args*>(a), s);
+    case TFX_OP_CE_FWD:           return tfx_ce_fwd(static_cast<const tfx_ce_chunk_args*>(a), s);
+    case TFX_OP_CE_BWD:           return tfx_ce_bwd(static_cast<const tfx_ce_chunk_args*>(a), s);
     case TFX_OP_MSE_FWD_BWD:      return tfx_mse_fwd_bwd(static_cast<const tfx_mse_args*>(a), s);
     case TFX_OP_CAST_ROWS:        return tfx_cast_rows(static_cast<const tfx_cast_args*>(a), s);
     case TFX_OP_CAST_ROWS_T:      return tfx_cast_rows_t(static_cast<const tfx_cast_args*>(a), s);
@@ -221,6 +223,7 @@ inline size_t struct_bytes(int op) {
     case TFX_OP_NOISE_MIX: return sizeof(tfx_noise_mix_args);
     case TFX_OP_FOURIER: return sizeof(tfx_fourier_args);
     case TFX_OP_CE_FWD_BWD: return sizeof(tfx_ce_args);
+    case TFX_OP_CE_FWD: case TFX_OP_CE_BWD: return sizeof(tfx_ce_chunk_args);
     case TFX_OP_MSE_FWD_BWD: return sizeof(tfx_mse_args);
     case TFX_OP_CAST_ROWS: case TFX_OP_CAST_ROWS_T: return sizeof(tfx_cast_args);
     case TFX_OP_ADAM_STEP: return sizeof(tfx_adam_args);

@@ -1702,6 +1702,95 @@ __global__ __launch_bounds__(256) void ce_k(tfx_ce_args p) {
   }
 }
 
+// ---- the cross entropy split into a forward and a backward launch over a chunk of rows (tfx.h tfx_ce_chunk_args) ----------------------------------
+// Both kernels read a logit ONCE, 16 bytes per lane.  WIDE = false: one wave per row, four rows per block (rows of at most 1024 logits: four trips of a
+// wave); WIDE = true: one block per row, the four waves' (max, sum) pairs meet in LDS.  Rows are grid-strided under the caps of the launch functions.
+constexpr int CE_WIDE_LD = 1024;          // rows wider than this (ld) take a block each
+constexpr int CE_CAP_NARROW = 1024;       // blocks: 4096 rows per trip of the narrow grid (the cap of ce_k: every block ends in two atomics on one address pair)
+constexpr int CE_CAP_WIDE = 2048;         // blocks = rows per trip of the wide grid
+
+// one lane's running (max, sum exp(. - max)) over the chunk's four logits; columns >= V count as -inf.  The max moves at most once per chunk: five
+// exponentials per four logits (exp(0) = 1 exactly where it does not move).  A chunk always holds one column < V, so `nm` is finite.
+TFX_DEV void ce_online4(const f32x4 v, int c, int V, float& m, float& s) {
+  float x[4];
+#pragma unroll
+  for (int e = 0; e < 4; e++) x[e] = c + e < V ? v[e] : -INFINITY;
+  const float nm = fmaxf(m, fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3])));
+  s = s * __expf(m - nm) + ((__expf(x[0] - nm) + __expf(x[1] - nm)) + (__expf(x[2] - nm) + __expf(x[3] - nm)));
+  m = nm;
+}
+
+template <bool WIDE>
+__global__ __launch_bounds__(256) void ce_chunk_fwd_k(tfx_ce_chunk_args p) {
+  __shared__ float sacc[2][WAVES];
+  __shared__ float spair[2][2][WAVES];                        // [row parity][max | sum][wave]: two sets, so one barrier per row is enough
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int q0 = WIDE ? threadIdx.x : lane, qs = WIDE ? 256 : 64;      // 4-column chunks: first, stride
+  const int nq = (p.V + 3) >> 2;
+  float loss = 0.f, cnt = 0.f;
+  int par = 0;
+  for (int t = WIDE ? blockIdx.x : blockIdx.x * WAVES + w; t < p.T; t += WIDE ? gridDim.x : gridDim.x * WAVES) {
+    const int lab = p.labels[t];                               // (uniform over the row's waves: an ignored row skips the barrier as a block)
+    if (lab < 0) { if (q0 == 0) p.lse[t] = 0.f; continue; }
+    const float* lg = p.logits + (size_t)t * p.ld;
+    float m = -INFINITY, s = 0.f;
+#pragma unroll 4
+    for (int q = q0; q < nq; q += qs) ce_online4(*(const f32x4*)(lg + 4 * q), 4 * q, p.V, m, s);
+    float M = wave_max(m);
+    float S = wave_sum(m == -INFINITY ? 0.f : s * __expf(m - M));      // (a lane without a chunk adds nothing - and in a wave without one M is -inf too)
+    if (WIDE) {
+      if (lane == 0) { spair[par][0][w] = M; spair[par][1][w] = S; }
+      __syncthreads();
+      float mm = spair[par][0][0];
+#pragma unroll
+      for (int i = 1; i < WAVES; i++) mm = fmaxf(mm, spair[par][0][i]);
+      float ss = 0.f;
+#pragma unroll
+      for (int i = 0; i < WAVES; i++) ss += spair[par][1][i] * __expf(spair[par][0][i] - mm);
+      M = mm; S = ss; par ^= 1;
+    }
+    if (q0 == 0) {
+      const float lse = M + __logf(S);
+      p.lse[t] = lse;
+      loss += lse - lg[lab]; cnt += 1.f;                       // (the label's logit: one more 4-byte read per row)
+    }
+  }
+  if (lane == 0) { sacc[0][w] = loss; sacc[1][w] = cnt; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float a = 0.f, b = 0.f;
+    for (int i = 0; i < WAVES; i++) { a += sacc[0][i]; b += sacc[1][i]; }
+    if (b > 0.f) { atomicAdd(p.acc, a); atomicAdd(p.acc + 1, b); }
+  }
+}
+
+template <bool WIDE>
+__global__ __launch_bounds__(256) void ce_chunk_bwd_k(tfx_ce_chunk_args p) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int c0 = (WIDE ? threadIdx.x : lane) * 8, cs = WIDE ? 2048 : 512;      // 8 columns per lane and trip: two 16-byte loads, one bf16x8 store
+  const float sc = p.grad_scale * (p.scale_dev ? *p.scale_dev : 1.f);
+  for (int t = WIDE ? blockIdx.x : blockIdx.x * WAVES + w; t < p.T; t += WIDE ? gridDim.x : gridDim.x * WAVES) {
+    const int lab = p.labels[t];
+    const float lse = p.lse[t];
+    const float* lg = p.logits + (size_t)t * p.ld;
+    bf16* dl = p.dlogits + (size_t)t * p.ld_d;
+    for (int c = c0; c < p.ld_d; c += cs) {
+      bf16x8 o;
+#pragma unroll
+      for (int e = 0; e < 8; e++) o[e] = f2bf(0.f);
+      if (lab >= 0 && c < p.V) {                               // c < V <= ld, both multiples of 8 but V: the eight floats lie inside the row
+        const f32x4 a = *(const f32x4*)(lg + c), b = *(const f32x4*)(lg + c + 4);
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+          const float x = e < 4 ? a[e & 3] : b[e & 3];
+          if (c + e < p.V) o[e] = f2bf((__expf(x - lse) - (c + e == lab ? 1.f : 0.f)) * sc);
+        }
+      }
+      *(bf16x8*)(dl + c) = o;
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void mse_k(tfx_mse_args p) {
   __shared__ float sacc[WAVES];
   const long long n = (long long)p.R * p.ld_d;
@@ -2485,6 +2574,29 @@ int tfx_fourier(const tfx_fourier_args* a, void* s) { if (a->I == 0) return 0; h
 int tfx_ce_fwd_bwd(const tfx_ce_args* a, void* s) {
   int g = grid_tokens(a->T); if (g > 1024) g = 1024;
   hipLaunchKernelGGL(ce_k, dim3(g), dim3(256), 0, ST(s), *a); RET();
+}
+static inline int ce_chunk_check(const tfx_ce_chunk_args* a, bool bwd) {
+  if (!a || a->T < 0) return -1;
+  if (a->T == 0) return 1;
+  if (a->V < 1 || a->V > a->ld || (a->ld & 7) || !a->logits || (((uintptr_t)a->logits) & 15) || !a->labels || !a->lse) return -1;
+  if (bwd ? (!a->dlogits || (((uintptr_t)a->dlogits) & 15) || (a->ld_d & 7) || a->V > a->ld_d) : !a->acc) return -1;
+  return 0;
+}
+static inline int ce_chunk_grid(const tfx_ce_chunk_args* a, bool wide) {
+  const int g = wide ? a->T : grid_tokens(a->T), cap = wide ? CE_CAP_WIDE : CE_CAP_NARROW;
+  return g < cap ? g : cap;
+}
+int tfx_ce_fwd(const tfx_ce_chunk_args* a, void* s) {
+  const int rc = ce_chunk_check(a, false); if (rc) return rc < 0 ? rc : 0;
+  if (a->ld > CE_WIDE_LD) hipLaunchKernelGGL(ce_chunk_fwd_k<true>, dim3(ce_chunk_grid(a, true)), dim3(256), 0, ST(s), *a);
+  else hipLaunchKernelGGL(ce_chunk_fwd_k<false>, dim3(ce_chunk_grid(a, false)), dim3(256), 0, ST(s), *a);
+  RET();
+}
+int tfx_ce_bwd(const tfx_ce_chunk_args* a, void* s) {
+  const int rc = ce_chunk_check(a, true); if (rc) return rc < 0 ? rc : 0;
+  if (a->ld_d > CE_WIDE_LD) hipLaunchKernelGGL(ce_chunk_bwd_k<true>, dim3(ce_chunk_grid(a, true)), dim3(256), 0, ST(s), *a);
+  else hipLaunchKernelGGL(ce_chunk_bwd_k<false>, dim3(ce_chunk_grid(a, false)), dim3(256), 0, ST(s), *a);
+  RET();
 }
 int tfx_mse_fwd_bwd(const tfx_mse_args* a, void* s) {
   long long n = (long long)a->R * a->ld_d; if (n == 0) return 0;

@@ -234,7 +234,8 @@ class _BwdBuild:
 
 
 class Plan:
-    def __init__(self, ps: ParamStore, b: int, n: int, I: int, R: dict, training: bool = True, cache=None, dp_groups: int = 0, tile_attn: bool = False, units=None, ctl_rows: int = 2, tn_defer=None, ckpt: bool = False):
+    def __init__(self, ps: ParamStore, b: int, n: int, I: int, R: dict, training: bool = True, cache=None, dp_groups: int = 0, tile_attn: bool = False, units=None, ctl_rows: int = 2, tn_defer=None, ckpt: bool = False,
+                 chunk_rows=None):
         """cache: None, or a KV cache tensor [depth, b, maxlen, 2*heads*64] (k~ | v per token).  With a cache the plan is a
         DECODE step: each layer appends this step's k~ / v rows at `cache_pos` (flat row b*maxlen + position, -1 = skip) and
         attention reads keys / values from the cache (per-token visible length in `kv_end`).
@@ -242,10 +243,15 @@ class Plan:
         owns the rows unit_row0[s] .. + unit_cnt[s] (device arrays the step fills; 0 rows = the sample sits this step out), so a mixed step of the
         continuous schedule carries the rows its live samples need instead of (modality length + 1) rows for every sample.
         ckpt: ACTIVATION CHECKPOINTING (training plans; Transfusion.set_activation_checkpointing_): the per-layer activation family lives in `n_slots`
-        slots instead of one entry per layer, and the backward list recomputes a layer into its slot in front of the layer's backward launches."""
+        slots instead of one entry per layer, and the backward list recomputes a layer into its slot in front of the layer's backward launches.
+        chunk_rows: CHUNKED TEXT HEAD (training plans; Transfusion.set_text_head_chunking_): the logits and their gradient exist for `chunk_rows` token rows
+        at a time - `logits_c`, `dlogits_c` - instead of for all T (`logits`, `dlogits`: not allocated).  The forward runs the logits product and tfx_ce_fwd
+        chunk by chunk and keeps one float per row (`ce_lse`); the backward runs the same product again, tfx_ce_bwd and the head's two gradient products per
+        chunk (_bwd_text_chunks).  The upstream gradient of the loss reaches tfx_ce_bwd through the device scalar `go_dev`."""
         md = ps.md
         self.training = training
         self.ckpt = bool(ckpt) and training
+        self.chunk = min(int(chunk_rows), max(b * n, 1)) if (chunk_rows and training) else None      # rows per chunk of the text head (None: the whole head at once)
         # the side stream's weight-gradient GEMMs read a layer's saved activations one layer behind the data-gradient chain: two slots by layer parity
         # there, one on a single stream
         self.n_slots = (2 if self._side_stream(md) else 1) if self.ckpt else None
@@ -344,7 +350,12 @@ class Plan:
         self.ya = e(nl, T, d); self.xb = e(nl, T, d); self.yf = e(nl, T, d)
         self.ag = e(nl, T, 2 * dip); self.hm = e(nl, T, dip)
         self.embed = e(T, d)
-        self.logits = e(T, md.vp, dtype=torch.float32); self.dlogits = e(T, md.vp)
+        if self.chunk:
+            self.logits_c = e(self.chunk, md.vp, dtype=torch.float32); self.dlogits_c = e(self.chunk, md.vp)
+            self.ce_lse = e(T, dtype=torch.float32)           # log sum exp of every row's logits: what the backward needs of the forward's softmax
+            self.go_dev = torch.ones(1, device=self.ps.device, dtype=torch.float32); self.nbytes += 4      # d total / d loss of the step's backward (tfx_ce_chunk_args.scale_dev)
+        else:
+            self.logits = e(T, md.vp, dtype=torch.float32); self.dlogits = e(T, md.vp)
         self.fe = z(I1, md.kf); self.cond = e(I1, 4 * d); self.pre = e(I1, 4 * d)
         self.tables = z(I1, nt3, dtype=torch.float32)
         self.lat = {}
@@ -614,7 +625,13 @@ class Plan:
         self._k(L, 'tfx_rmsnorm_fwd', 'tfx_rmsnorm_args', T=T, d=d, x=self.xres[D], y=self.embed, gamma=pp('transformer.norm.gamma'))
         self._hbm(L, 2)
         self.fwd_embed_end = len(L)          # launches up to here produce `embed` (return_embed / decode paths stop here)
-        self._nt(L, A=self.embed, lda=d, B=S['logits'], ldb=d, M=T, N=md.vp, K=d, algo_n=md.vocab, epi=E['TFX_EPI_F32'], C=self.logits, ldc=md.vp)   # zero pad rows: N % 4 == 0 keeps the LDS-DMA kernel
+        if self.chunk:
+            for r0, m in self._chunks():                  # per chunk: its logits, then their cross entropy - nothing of the chunk outlives it but `ce_lse`
+                self._chunk_logits(L, r0, m)
+                L.append(('tfx_ce_fwd', self._ce_chunk_args(L, r0, m)))
+                self._hbm(L, extra_bytes=m * (md.vp * 4 + 4))              # fp32 logits in, lse out
+        else:
+            self._nt(L, A=self.embed, lda=d, B=S['logits'], ldb=d, M=T, N=md.vp, K=d, algo_n=md.vocab, epi=E['TFX_EPI_F32'], C=self.logits, ldc=md.vp)   # zero pad rows: N % 4 == 0 keeps the LDS-DMA kernel
         self.fwd_logits_end = len(L)
         native = {t: r for t, r in self.R.items() if t not in self.ext}      # types whose projections / losses run here
         rows = self.row_gat if self.cache is None else self.row_src
@@ -628,10 +645,11 @@ class Plan:
         if self.cache is not None:           # decode plans: no losses
             self._chain_weight_prefetch(L)
             return
-        self._ce_args = capi.make_args('tfx_ce_args', T=T, V=md.vocab, logits=self.logits, ld=md.vp, labels=self.labels, grad_scale=0.0,
-                                       dlogits=self.dlogits, ld_d=md.vp, acc=self.acc)
-        L.append(('tfx_ce_fwd_bwd', self._ce_args))
-        self._hbm(L, extra_bytes=T * md.vp * (4 + 2))                        # fp32 logits in, bf16 d logits out
+        if not self.chunk:
+            self._ce_args = capi.make_args('tfx_ce_args', T=T, V=md.vocab, logits=self.logits, ld=md.vp, labels=self.labels, grad_scale=0.0,
+                                           dlogits=self.dlogits, ld_d=md.vp, acc=self.acc)
+            L.append(('tfx_ce_fwd_bwd', self._ce_args))
+            self._hbm(L, extra_bytes=T * md.vp * (4 + 2))                        # fp32 logits in, bf16 d logits out
         nm = len(md.dim_latents)
         for t, r in native.items():
             lt = self.lat[t]
@@ -643,6 +661,29 @@ class Plan:
             # third target on the same prediction: the reconstruction residual, per-row weights filled per step
             self._rec_args[t] = self._loss_target(self.rec, t, 2 + 2 * nm + t, lt['flow'], accumulate=1, recon_w=lt['recw'], recon_inst=self.row_inst[t],
                                                   recon_time=self.inst_time, recon_mode=0)
+
+    # ---- the chunked text head (`chunk`)
+    def _chunks(self):
+        """(first row, rows) of every chunk of the text head: ceil(T / chunk) of them, the last one ragged"""
+        return [(r0, min(self.chunk, self.T - r0)) for r0 in range(0, self.T, self.chunk)]
+
+    def _chunk_logits(self, lst, r0, m):
+        """the logits of rows r0 .. r0 + m into `logits_c`: ONE spelling for the forward and for the backward's recompute, so the backward sees the bits
+        `ce_lse` was formed from"""
+        md, d = self.md, self.md.dim
+        self._nt(lst, A=self.embed[r0:], lda=d, B=self.ps.shadows['logits'], ldb=d, M=m, N=md.vp, K=d, algo_n=md.vocab, epi=E['TFX_EPI_F32'], C=self.logits_c, ldc=md.vp)
+
+    def _ce_chunk_args(self, lst, r0, m):
+        """tfx_ce_chunk_args of rows r0 .. r0 + m, owned by `lst` and registered with it for the per-step setters (set_ce_vocab, set_loss_scales)"""
+        md = self.md
+        a = capi.make_args('tfx_ce_chunk_args', T=m, V=md.vocab, logits=self.logits_c, ld=md.vp, labels=self.labels[r0:], lse=self.ce_lse[r0:], acc=self.acc,
+                           grad_scale=0.0, scale_dev=self.go_dev, dlogits=self.dlogits_c, ld_d=md.vp)
+        lst.patched('ce', a)
+        return a
+
+    def _ce_structs(self):
+        """the cross-entropy args the per-step setters write: the fused launch's, or every chunk's in every list that may still replay"""
+        return [a for L in self._lists() for a in L.patch.get('ce', ())] if self.chunk else [self._ce_args]
 
     def _loss_target(self, lst, t, slot, target, **extra):
         """one squared-error target on type t's flow prediction, appended to `lst`: the sum into accumulator `slot`, the gradient into (or, with
@@ -896,10 +937,12 @@ class Plan:
 
     def set_ce_vocab(self, V: int):
         """number of logit columns the cross entropy runs over (the full vocabulary, or the text-only prefix for forward_text)"""
-        self._ce_args.V = V
+        for a in self._ce_structs():
+            a.V = V
 
     def set_loss_scales(self, ce_scale: float, mse_scales: dict):
-        self._ce_args.grad_scale = ce_scale
+        for a in self._ce_structs():
+            a.grad_scale = ce_scale
         for t, s in mse_scales.items():
             self._mse_args[t].grad_scale = s
 
@@ -960,16 +1003,31 @@ class Plan:
         """weight gradient of the text head (t None) or of type t's model_to_latent, if it trains"""
         md, d, L, gp = self.md, self.md.dim, self.bwd, self.ps.grad_ptr
         if t is None:
-            if c.tr('to_text_logits.weight'):
+            if c.tr('to_text_logits.weight') and not self.chunk:          # (chunked text head: the chunks' products, _bwd_text_chunks)
                 self._tn(L, self.T, md.vocab, d, A=self.dlogits, lda=md.vp, a_cols=md.vp, B=self.embed, ldb=d, b_cols=d, C=gp('to_text_logits.weight'), ldc=d)
         elif c.tr(f'model_to_latent_projs.{t}.weight'):
             dl = md.dim_latents[t]; dlp = pad_to(dl, 64)
             self._tn(L, self.R[t], dl, d, A=self.lat[t]['dpred'], lda=dlp, a_cols=dlp, B=self.embed, ldb=d, b_cols=d, b_rowmap=self.row_gat[t],
                      C=gp(f'model_to_latent_projs.{t}.weight'), ldc=d)
 
+    def _bwd_text_chunks(self, c):
+        """chunked text head: per chunk the forward's logits product again (its very arguments: the bits `ce_lse` belongs to), tfx_ce_bwd into `dlogits_c`,
+        the chunk's share of the head's weight gradient (if it trains) and the chunk's rows of `dembed`.  All on the caller's stream: the next chunk reuses
+        both buffers, and the head's gradient range is final before the layers start."""
+        md, d, S, L = self.md, self.md.dim, self.ps.shadows, self.bwd
+        for r0, m in self._chunks():
+            self._chunk_logits(L, r0, m)
+            L.append(('tfx_ce_bwd', self._ce_chunk_args(L, r0, m)))
+            self._hbm(L, extra_bytes=m * (md.vp * (4 + 2) + 4))                # fp32 logits and lse in, bf16 d logits out
+            if c.tr('to_text_logits.weight'):
+                self._tn(L, m, md.vocab, d, A=self.dlogits_c, lda=md.vp, a_cols=md.vp, B=self.embed[r0:], ldb=d, b_cols=d, C=self.ps.grad_ptr('to_text_logits.weight'), ldc=d)
+            self._nt(L, algo_k=md.vocab, A=self.dlogits_c, lda=md.vp, B=S['logits_t'], ldb=md.vp, M=m, N=d, K=md.vp, epi=E['TFX_EPI_BF16'], C=self.dembed[r0:], ldc=d)
+
     def _bwd_heads_and_norm(self, c):
         """d logits and d pred back to d embed, the heads' weight gradients, the final norm"""
         md, T, d, D, S, L = self.md, self.T, self.md.dim, self.md.depth, self.ps.shadows, self.bwd
+        if self.chunk:
+            self._bwd_text_chunks(c)       # (in place of the text head's two launches below; with a frozen set they too stand in front of `bwd_end`)
         if c.fz:
             # with a frozen set the heads' weight gradients come FIRST, so that a backward with nothing trainable below the heads is this prefix of the
             # list (`bwd_end`); with nothing frozen the list keeps the order it always had
@@ -979,7 +1037,8 @@ class Plan:
                     self._head_tn(c, t)
             if c.low == 'heads':
                 self.bwd_end = len(L)
-        self._nt(L, algo_k=md.vocab, A=self.dlogits, lda=md.vp, B=S['logits_t'], ldb=md.vp, M=T, N=d, K=md.vp, epi=E['TFX_EPI_BF16'], C=self.dembed, ldc=d)
+        if not self.chunk:
+            self._nt(L, algo_k=md.vocab, A=self.dlogits, lda=md.vp, B=S['logits_t'], ldb=md.vp, M=T, N=d, K=md.vp, epi=E['TFX_EPI_BF16'], C=self.dembed, ldc=d)
         if not c.fz:
             self._head_tn(c)
         for t, r in self.R.items():

@@ -396,6 +396,7 @@ class Transfusion(nn.Module):
             self._register_state_dict_hook(_post)
         self._plans = {}
         self._ckpt = False                   # activation checkpointing (set_activation_checkpointing_): part of the plan key
+        self._chunk = None                   # rows per chunk of the text head (set_text_head_chunking_; None = off): part of the plan key
         self._struct_cache = {}
         self._decode_plans = {}              # decode plans of the cached forward calls and of the sampler (sampling.Sampler._decode_plan)
         self._flat_pred_flows = False        # set by `_teacher_pass` around a teacher's forward
@@ -472,7 +473,7 @@ class Transfusion(nn.Module):
             new = new.to(self.device)
         new.load_state_dict(self.state_dict())
         new.train(self.training)
-        new._ckpt = self._ckpt
+        new._ckpt, new._chunk = self._ckpt, self._chunk
         memo[id(self)] = new
         return new
 
@@ -652,6 +653,27 @@ class Transfusion(nn.Module):
         self._ckpt = enabled
         return self
 
+    @property
+    def text_head_chunk_rows(self):
+        return self._chunk
+
+    def set_text_head_chunking_(self, rows):
+        """bound the text head's memory in training: with `rows` set (a positive multiple of 64; None = off, the default) a training plan never holds the
+        logits of all its token rows - fp32 [rows of the step, padded vocabulary] and their bf16 gradient, 6 bytes per token and vocabulary entry: 12.6 GB at
+        65 536 tokens x 32 k entries - but those of `rows` token rows at a time.  The forward runs the logits product and the cross entropy chunk by chunk and
+        keeps one float per row; the backward forms each chunk's logits once more, their gradient, and the head's two gradient products from it
+        (engine.Plan `chunk_rows`).  The price is that second logits product and one more pass over the chunk's logits.  Applies to the calls that return the
+        text loss - `forward(..., return_loss=True)` and `forward_text(return_loss=True)`; calls that hand out logits, decode plans and the sampler never look
+        at it.  The value is part of the plan key, so plans of several settings can sit in the cache together.  Losses and gradients agree with the
+        unchunked step to the rounding of the logits product (a product over `rows` rows may pick another kernel than one over all of them).  Returns self."""
+        if rows is not None:
+            if isinstance(rows, bool) or not isinstance(rows, int):
+                raise TypeError(f'set_text_head_chunking_ takes an int or None, got {type(rows).__name__}')
+            if rows <= 0 or rows % 64:
+                raise ValueError(f'set_text_head_chunking_: rows must be a positive multiple of 64, got {rows}')
+        self._chunk = rows
+        return self
+
     def _require_gpu(self):
         if self.device.type != 'cuda':
             raise capi.TfxError('the Transfusion hot path only runs on an MI355X (model.cuda()); there is no CPU fallback')
@@ -667,15 +689,17 @@ class Transfusion(nn.Module):
             self._rope = (cos.to(self.device).contiguous(), sin.to(self.device).contiguous())
         return self._rope
 
-    def _plan(self, b, n, I, R, training):
+    def _plan(self, b, n, I, R, training, text_loss=False):
+        """`text_loss`: the call returns the text loss (forward, forward_text with return_loss) - the training plans set_text_head_chunking_ applies to"""
         dp_groups = getattr(self, '_dp_groups', 0) if training else 0
         ckpt = training and self._ckpt                              # inference, decode, sampling and hiddens-only plans never look at the switch
-        key = (b, n, I, tuple(sorted(R.items())), training, dp_groups, ckpt)
+        chunk = self._chunk if (training and text_loss) else None   # ... nor at this one; forward_modality's training plans neither (no text loss)
+        key = (b, n, I, tuple(sorted(R.items())), training, dp_groups, ckpt, chunk)
         plan = self._plans.pop(key, None)
         if plan is None:
             while len(self._plans) >= 8:                             # least recently used plan goes first (dict order = use order)
                 self._plans.pop(next(iter(self._plans)))
-            plan = Plan(self.store, b, n, I, R, training=training, dp_groups=dp_groups, ckpt=ckpt)
+            plan = Plan(self.store, b, n, I, R, training=training, dp_groups=dp_groups, ckpt=ckpt, **({'chunk_rows': chunk} if chunk else {}))
             # a plan owns every activation of its step (tens of GB for a training plan at dim 1024 / depth 24): besides the count, the cache is
             # bounded by bytes - TFX_PLAN_BUDGET_GB, default 40 % of the device memory - oldest first, the new plan always stays
             budget = float(os.environ.get('TFX_PLAN_BUDGET_GB', 0)) * 2 ** 30 or 0.4 * torch.cuda.get_device_properties(self.device).total_memory
@@ -966,7 +990,7 @@ class Transfusion(nn.Module):
                   and not md.model_output_clean and os.environ.get('TFX_PLAN_BUCKETS', '1') != '0')
         Ip = _bucket(I, 64) if (bucket and I > 0) else I
         Rp = {t: _bucket(r, 256) for t, r in R.items()} if bucket else R
-        plan = self._plan(S['b'], S['n'], Ip, Rp, training=return_loss and not hid_only)
+        plan = self._plan(S['b'], S['n'], Ip, Rp, training=return_loss and not hid_only, text_loss=True)
         if return_loss and not hid_only:
             plan.clear_taps()                               # a tap lives for the step that set it
         if md.model_output_clean:
@@ -1378,7 +1402,7 @@ class Transfusion(nn.Module):
                         seg_start=D(seg_start), seg_len=D(seg_len))
         S = self._structure(('text', b, n), build)
         self.store.refresh_shadows(stream)
-        plan = self._plan(b, n, 0, {}, training=return_loss)
+        plan = self._plan(b, n, 0, {}, training=return_loss, text_loss=True)
         if plan.loaded_structure is not S:
             plan.load_structure(S, self._rope_tables(n), S['tok_inst'], S['kv_end'], S['q_start'], S['rot_pos'], segments=(S['seg_start'], S['seg_len']))
         plan.text_ids.copy_(inp.masked_fill(inp == -1, 0).reshape(-1))                      # T:2608
@@ -1660,7 +1684,9 @@ class Transfusion(nn.Module):
         lib, stream = capi.lib(), self._stream()
         sp = ctypes.c_void_p(stream)
         # fp32 scalar read on the device; exactly 1.0 (plain loss.backward()) skips the pass over the seeds
-        for seed in [plan.dlogits] + [lt['dpred'] for lt in plan.lat.values() if 'dpred' in lt]:
+        if plan.chunk:
+            plan.go_dev.copy_(go.reshape(1))                  # chunked text head: no d logits exist yet - tfx_ce_bwd reads the scalar as it forms each chunk's
+        for seed in ([] if plan.chunk else [plan.dlogits]) + [lt['dpred'] for lt in plan.lat.values() if 'dpred' in lt]:
             capi.check(lib.tfx_scale_bf16_dev(seed.data_ptr(), seed.numel(), go.data_ptr(), sp), 'tfx_scale_bf16_dev')
         plan.dtables.zero_()
         if self.md.model_output_clean and plan.clean_mode == 'model' and len(plan.clean_bwd):
@@ -1850,6 +1876,7 @@ class Transfusion(nn.Module):
         kw['pre_post_transformer_enc_dec'] = copy.deepcopy(kw.get('pre_post_transformer_enc_dec'))     # learnable: the copy owns its own modules
         m = Transfusion(**kw)
         m._ckpt = self._ckpt                 # (create_ema / EMA: harmless there - a teacher's passes run without gradient, on inference plans)
+        m._chunk = self._chunk
         return m.to(self.device) if self.device.type == 'cuda' else m
 
     def create_dataloader(self, *args, **kwargs):                   # T:1676-1679
