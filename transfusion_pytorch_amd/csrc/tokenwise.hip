@@ -80,6 +80,32 @@ template <int NC> TFX_DEV void widen(Row<NC>& o, const RowRaw<NC>& r) {
 #pragma unroll
     for (int e = 0; e < 8; e++) o.v[i][e] = bf2f(r.v[i][e]);
 }
+
+// ------------------------------------------------------------------------------------------------
+// Row helpers: the plain row loops (every element a lane owns, in i, e order) and the wrapper's output scale.  They are loop helpers, not the definition
+// of the LayerNorm / AdaLN row arithmetic: each kernel below spells its own statistics, modulation and backward sums, because what the compiler
+// contracts into an fma or vectorises depends on the code around an expression, and a fused kernel must reproduce the kernels it fuses bit for bit
+// (profiles/tokenwise_row_helpers.txt).
+// ------------------------------------------------------------------------------------------------
+template <int NC, class F> TFX_DEV void row_each(F f) {                            // f(i, e) for every element a lane owns
+#pragma unroll
+  for (int i = 0; i < NC; i++)
+#pragma unroll
+    for (int e = 0; e < 8; e++) f(i, e);
+}
+template <int NC> TFX_DEV void row_zero(Row<NC>& r) { row_each<NC>([&](int i, int e) { r.v[i][e] = 0.f; }); }
+template <int NC> TFX_DEV void row_add(Row<NC>& a, const Row<NC>& b) { row_each<NC>([&](int i, int e) { a.v[i][e] += b.v[i][e]; }); }
+
+// the wrapper's output scale from the loaded value: text 1 + layerscale | modality sigmoid(z)
+TFX_DEV float wrapper_scale(float s, int inst) { return inst < 0 ? 1.f + s : sigmoidf_(s); }
+// the wrapper's output x <- x + y scale(s); ROUND: rounded to bf16, as a kernel that re-reads the stored row sees it
+template <bool ROUND, int NC> TFX_DEV void wrapper_out(Row<NC>& x, const Row<NC>& y, const Row<NC>& s, int inst) {
+  row_each<NC>([&](int i, int e) {
+    const float v = x.v[i][e] + y.v[i][e] * wrapper_scale(s.v[i][e], inst);
+    x.v[i][e] = ROUND ? bf2f(f2bf(v)) : v;
+  });
+}
+
 // block-level reduction of per-lane column partials over the block's waves, then global atomics
 // out == NULL (a frozen parameter's gradient, tfx.h "NULL parameter-gradient outputs"): the sum is not formed and nothing is added - `out` is a
 // kernel argument, so the branch is uniform over the block and no wave misses a barrier
@@ -227,13 +253,7 @@ template <int NC> __global__ __launch_bounds__(256) void adaln_post_fwd_k(tfx_ad
   const int inst = p.tok_inst[t];
   if (inst < 0) load_vec(s, p.layerscale, d, lane);
   else load_vec(s, p.table + (size_t)inst * p.ld_table + 2 * d, d, lane);
-#pragma unroll
-  for (int i = 0; i < NC; i++)
-#pragma unroll
-    for (int e = 0; e < 8; e++) {
-      float sc = inst < 0 ? 1.f + s.v[i][e] : sigmoidf_(s.v[i][e]);
-      x.v[i][e] += y.v[i][e] * sc;
-    }
+  wrapper_out<false>(x, y, s, inst);
   store_row(x, p.out + (size_t)t * d, d, lane);
 }
 
@@ -252,16 +272,10 @@ template <int NC> __global__ __launch_bounds__(256) void adaln_post_pre_fwd_k(tf
     load_vec(s, p.table + (size_t)inst * p.ld_table + 2 * d, d, lane);
     load_vec(g, q.table + (size_t)inst * q.ld_table, d, lane); load_vec(b, q.table + (size_t)inst * q.ld_table + d, d, lane);
   }
-  float sm = 0.f;
-#pragma unroll
-  for (int i = 0; i < NC; i++)
-#pragma unroll
-    for (int e = 0; e < 8; e++) {
-      const float sc = inst < 0 ? 1.f + s.v[i][e] : sigmoidf_(s.v[i][e]);
-      x.v[i][e] = bf2f(f2bf(x.v[i][e] + y.v[i][e] * sc));            // what tfx_adaln_pre_fwd would read back
-      sm += x.v[i][e];
-    }
+  wrapper_out<true>(x, y, s, inst);                            // (rounded: what tfx_adaln_pre_fwd would read back)
   store_row(x, p.out + (size_t)t * d, d, lane);
+  float sm = 0.f;
+  row_each<NC>([&](int i, int e) { sm += x.v[i][e]; });
   const float mean = wave_sum(sm) / d;
   float qq = 0.f;
 #pragma unroll
@@ -273,13 +287,10 @@ template <int NC> __global__ __launch_bounds__(256) void adaln_post_pre_fwd_k(tf
   }
   const float rstd = rsqrtf(wave_sum(qq) / d + 1e-5f);
   if (lane == 0) { q.mean[t] = mean; q.rstd[t] = rstd; }
-#pragma unroll
-  for (int i = 0; i < NC; i++)
-#pragma unroll
-    for (int e = 0; e < 8; e++) {
-      float xh = (x.v[i][e] - mean) * rstd;
-      x.v[i][e] = xh * (1.f + g.v[i][e]) + (inst < 0 ? 0.f : b.v[i][e]);
-    }
+  row_each<NC>([&](int i, int e) {
+    float xh = (x.v[i][e] - mean) * rstd;
+    x.v[i][e] = xh * (1.f + g.v[i][e]) + (inst < 0 ? 0.f : b.v[i][e]);
+  });
   store_row(x, q.u + (size_t)t * d, d, lane);
 }
 
@@ -422,20 +433,14 @@ template <int NC> __global__ __launch_bounds__(512) void adaln_post_bwd_seg_k(tf
   const int lane = threadIdx.x & 63;
   const int d = p.d;
   Row<NC> pl, pb;                                           // per-lane partials: d layerscale, d bias (column sums of dy)
-#pragma unroll
-  for (int i = 0; i < NC; i++)
-#pragma unroll
-    for (int e = 0; e < 8; e++) { pl.v[i][e] = 0.f; pb.v[i][e] = 0.f; }
+  row_zero(pl); row_zero(pb);
   for (int s = blockIdx.x * SEG_WAVES + (threadIdx.x >> 6); s < p.n_seg; s += gridDim.x * SEG_WAVES) {
     const int t0 = p.seg_start[s], len = p.seg_len[s];
     const int inst = p.tok_inst[t0];
     Row<NC> sc, az;
     if (inst < 0) load_vec(sc, p.layerscale, d, lane);
     else load_vec(sc, p.table + (size_t)inst * p.ld_table + 2 * d, d, lane);
-#pragma unroll
-    for (int i = 0; i < NC; i++)
-#pragma unroll
-      for (int e = 0; e < 8; e++) { sc.v[i][e] = inst < 0 ? 1.f + sc.v[i][e] : sigmoidf_(sc.v[i][e]); az.v[i][e] = 0.f; }
+    row_each<NC>([&](int i, int e) { sc.v[i][e] = wrapper_scale(sc.v[i][e], inst); az.v[i][e] = 0.f; });
     constexpr int U = NC == 1 ? 4 : (NC == 2 ? 2 : 1);      // U tokens per trip, loads first (see adaln_pre_bwd_seg_k)
     const int tend = t0 + len;
     for (int tb = t0; tb < tend; tb += U) {
@@ -459,12 +464,8 @@ template <int NC> __global__ __launch_bounds__(512) void adaln_post_bwd_seg_k(tf
         store_row(gg, p.dy + (size_t)t * d, d, lane);
       }
     }
-    if (inst < 0) {
-#pragma unroll
-      for (int i = 0; i < NC; i++)
-#pragma unroll
-        for (int e = 0; e < 8; e++) pl.v[i][e] += az.v[i][e];
-    } else if (p.dtable) {
+    if (inst < 0) row_add(pl, az);
+    else if (p.dtable) {
       float* dt = p.dtable + (size_t)inst * p.ld_table + 2 * d;
 #pragma unroll
       for (int i = 0; i < NC; i++) {
@@ -514,31 +515,22 @@ template <int NC> __global__ __launch_bounds__(256) void rmsnorm_bwd_k(tfx_rmsno
   const int d = p.d;
   Row<NC> pg, g;
   load_vec(g, p.gamma, d, lane);
-#pragma unroll
-  for (int i = 0; i < NC; i++)
-#pragma unroll
-    for (int e = 0; e < 8; e++) pg.v[i][e] = 0.f;
+  row_zero(pg);
   for (int t = blockIdx.x * WAVES + (threadIdx.x >> 6); t < p.T; t += gridDim.x * WAVES) {
     Row<NC> x, dy;
     load_row(x, p.x + (size_t)t * d, d, lane);
     load_row(dy, p.dy + (size_t)t * d, d, lane);
     float q = 0.f, S = 0.f;
-#pragma unroll
-    for (int i = 0; i < NC; i++)
-#pragma unroll
-      for (int e = 0; e < 8; e++) { q += x.v[i][e] * x.v[i][e]; S += (1.f + g.v[i][e]) * dy.v[i][e] * x.v[i][e]; }
+    row_each<NC>([&](int i, int e) { q += x.v[i][e] * x.v[i][e]; S += (1.f + g.v[i][e]) * dy.v[i][e] * x.v[i][e]; });
     q = wave_sum(q); S = wave_sum(S);
     const float nrm = sqrtf(q);
     const float r = sqrtf((float)d) / fmaxf(nrm, 1e-12f);
     // under the clamp the denominator is a constant: no projection term (r^3 overflows fp32 there, and inf * 0 made an all-zero row's gradient NaN)
     const float k2 = nrm > 1e-12f ? r * r * r / d * S : 0.f;
-#pragma unroll
-    for (int i = 0; i < NC; i++)
-#pragma unroll
-      for (int e = 0; e < 8; e++) {
-        pg.v[i][e] += dy.v[i][e] * x.v[i][e] * r;
-        x.v[i][e] = r * (1.f + g.v[i][e]) * dy.v[i][e] - x.v[i][e] * k2;
-      }
+    row_each<NC>([&](int i, int e) {
+      pg.v[i][e] += dy.v[i][e] * x.v[i][e] * r;
+      x.v[i][e] = r * (1.f + g.v[i][e]) * dy.v[i][e] - x.v[i][e] * k2;
+    });
     store_row(x, p.dx + (size_t)t * d, d, lane);
   }
   flush_col_partials<NC>(pg, p.dgamma, d, smem);
@@ -552,10 +544,7 @@ template <int NC> __global__ __launch_bounds__(256) void rmsnorm_bwd_k(tfx_rmsno
 template <int NC> TFX_DEV void attnres_mix(const Row<NC>& h, const Row<NC>& w, Row<NC>& o, float& m, float& den, float& s_out, float& inv_out) {
   // every multiply-add is spelled as an explicit fma: the compiler's own contraction choices depend on the surrounding code
   float nsq = 0.f, dt = 0.f;
-#pragma unroll
-  for (int i = 0; i < NC; i++)
-#pragma unroll
-    for (int e = 0; e < 8; e++) { nsq = __builtin_fmaf(h.v[i][e], h.v[i][e], nsq); dt = __builtin_fmaf(h.v[i][e], w.v[i][e], dt); }
+  row_each<NC>([&](int i, int e) { nsq = __builtin_fmaf(h.v[i][e], h.v[i][e], nsq); dt = __builtin_fmaf(h.v[i][e], w.v[i][e], dt); });
   nsq = wave_sum(nsq); dt = wave_sum(dt);
   const float nrm = fmaxf(sqrtf(nsq), 1e-12f);
   const float s = dt / nrm;
@@ -563,10 +552,7 @@ template <int NC> TFX_DEV void attnres_mix(const Row<NC>& h, const Row<NC>& w, R
   const float mn = fmaxf(m, s);
   const float al = __expf(m - mn), ex = __expf(s - mn);
   den = __builtin_fmaf(den, al, ex); m = mn;
-#pragma unroll
-  for (int i = 0; i < NC; i++)
-#pragma unroll
-    for (int e = 0; e < 8; e++) { const float t = ex * h.v[i][e]; o.v[i][e] = __builtin_fmaf(o.v[i][e], al, t); }
+  row_each<NC>([&](int i, int e) { const float t = ex * h.v[i][e]; o.v[i][e] = __builtin_fmaf(o.v[i][e], al, t); });
 }
 
 template <int NC> TFX_DEV void attnres_mix(const Row<NC>& h, const Row<NC>& w, Row<NC>& o, float& m, float& den) {
@@ -587,10 +573,7 @@ template <int NC> __global__ __launch_bounds__(256) void attnres_fwd_k(tfx_attnr
   const int d = p.d;
   Row<NC> w, pq, o;
   load_vec(w, p.gamma, d, lane); load_vec(pq, p.pq, d, lane);
-#pragma unroll
-  for (int i = 0; i < NC; i++)
-#pragma unroll
-    for (int e = 0; e < 8; e++) { w.v[i][e] = (1.f + w.v[i][e]) * pq.v[i][e]; o.v[i][e] = 0.f; }
+  row_each<NC>([&](int i, int e) { w.v[i][e] = (1.f + w.v[i][e]) * pq.v[i][e]; o.v[i][e] = 0.f; });
   float m = -INFINITY, den = 0.f;
   float s_l = 0.f, inv_l = 0.f;
   constexpr int PF = NC == 1 ? 4 : 2;          // rows requested before the first of them is reduced (see attnres_bwd_k)
@@ -610,16 +593,10 @@ template <int NC> __global__ __launch_bounds__(256) void attnres_fwd_k(tfx_attnr
   }
   if (p.save) attnres_save(p.save, t, p.L, lane, s_l, inv_l, m, den);
   const float inv = 1.f / den;
-#pragma unroll
-  for (int i = 0; i < NC; i++)
-#pragma unroll
-    for (int e = 0; e < 8; e++) o.v[i][e] *= inv;
+  row_each<NC>([&](int i, int e) { o.v[i][e] *= inv; });
   store_row(o, p.out + (size_t)t * d, d, lane);
   if (p.err) {
-#pragma unroll
-    for (int i = 0; i < NC; i++)
-#pragma unroll
-      for (int e = 0; e < 8; e++) o.v[i][e] -= bf2f(f2bf(o.v[i][e]));
+    row_each<NC>([&](int i, int e) { o.v[i][e] -= bf2f(f2bf(o.v[i][e])); });
     store_row(o, p.err + (size_t)t * d, d, lane);
   }
 }
@@ -643,7 +620,7 @@ template <int NC> __global__ __launch_bounds__(256) void layer_end_fwd_k(tfx_ada
     for (int i = 0; i < NC; i++)
 #pragma unroll
       for (int e = 0; e < 8; e++) {
-        const float sc = inst < 0 ? 1.f + s.v[i][e] : sigmoidf_(s.v[i][e]);
+        const float sc = wrapper_scale(s.v[i][e], inst);
         hn.v[i][e] = bf2f(f2bf(hn.v[i][e] + y.v[i][e] * sc));
       }
     store_row(hn, p.out + (size_t)t * d, d, lane);
@@ -724,20 +701,11 @@ template <int NC> __global__ __launch_bounds__(256) void attnres_bwd_k(tfx_attnr
   Row<NC> w, pw;     // w = (1+gamma)*pq ; pw = per-lane partial of d(w)
   {
     Row<NC> pq; load_vec(w, p.gamma, d, lane); load_vec(pq, p.pq, d, lane);
-#pragma unroll
-    for (int i = 0; i < NC; i++)
-#pragma unroll
-      for (int e = 0; e < 8; e++) { w.v[i][e] = (1.f + w.v[i][e]) * pq.v[i][e]; pw.v[i][e] = 0.f; }
+    row_each<NC>([&](int i, int e) { w.v[i][e] = (1.f + w.v[i][e]) * pq.v[i][e]; pw.v[i][e] = 0.f; });
   }
   for (int t = blockIdx.x * WAVES + (threadIdx.x >> 6); t < p.T; t += gridDim.x * WAVES) {
     Row<NC> g; load_row(g, p.g + (size_t)t * d, d, lane);
-    if (p.g2) {
-      Row<NC> g2; load_row(g2, p.g2 + (size_t)t * d, d, lane);
-#pragma unroll
-      for (int i = 0; i < NC; i++)
-#pragma unroll
-        for (int e = 0; e < 8; e++) g.v[i][e] += g2.v[i][e];
-    }
+    if (p.g2) { Row<NC> g2; load_row(g2, p.g2 + (size_t)t * d, d, lane); row_add(g, g2); }
     // pass 1: lane l keeps (score, inverse norm, <g,h_l>) of hidden l   (L <= 64).  Rows are requested PF at a time (raw bf16) before the
     // first of them is reduced: one wave then keeps PF rows in flight instead of one (the kernel is request-latency bound otherwise)
     float s_l = -INFINITY, inv_l = 0.f, da_l = 0.f;
@@ -752,10 +720,7 @@ template <int NC> __global__ __launch_bounds__(256) void attnres_bwd_k(tfx_attnr
         if (l0 + j < p.L) {
           Row<NC> h; widen(h, hr[j]);
           float nsq = 0.f, dt = 0.f, da = 0.f;
-#pragma unroll
-          for (int i = 0; i < NC; i++)
-#pragma unroll
-            for (int e = 0; e < 8; e++) { nsq += h.v[i][e] * h.v[i][e]; dt += h.v[i][e] * w.v[i][e]; da += h.v[i][e] * g.v[i][e]; }
+          row_each<NC>([&](int i, int e) { nsq += h.v[i][e] * h.v[i][e]; dt += h.v[i][e] * w.v[i][e]; da += h.v[i][e] * g.v[i][e]; });
           nsq = wave_sum(nsq); dt = wave_sum(dt); da = wave_sum(da);
           const float inv = 1.f / fmaxf(sqrtf(nsq), 1e-12f);
           if (lane == l0 + j) { s_l = dt * inv; inv_l = inv; da_l = da; }
@@ -784,6 +749,7 @@ template <int NC> __global__ __launch_bounds__(256) void attnres_bwd_k(tfx_attnr
           Row<NC> h, dh; widen(h, hq[b]);
           if (!p.first) widen(dh, dq[b]);
           const float k1 = ds * inv, k2 = ds * sc * inv * inv;
+          // (a plain loop, not row_each: through the helper this kernel takes 8 / 14 / 28 registers more at NC = 1 / 2 / 4)
 #pragma unroll
           for (int i = 0; i < NC; i++)
 #pragma unroll
@@ -799,15 +765,9 @@ template <int NC> __global__ __launch_bounds__(256) void attnres_bwd_k(tfx_attnr
   }
   // d gamma = dw * pq ; d pq = dw * (1 + gamma)
   Row<NC> gm, pq, tmp; load_vec(gm, p.gamma, d, lane); load_vec(pq, p.pq, d, lane);
-#pragma unroll
-  for (int i = 0; i < NC; i++)
-#pragma unroll
-    for (int e = 0; e < 8; e++) tmp.v[i][e] = pw.v[i][e] * pq.v[i][e];
+  row_each<NC>([&](int i, int e) { tmp.v[i][e] = pw.v[i][e] * pq.v[i][e]; });
   flush_col_partials<NC>(tmp, p.dgamma, d, smem);
-#pragma unroll
-  for (int i = 0; i < NC; i++)
-#pragma unroll
-    for (int e = 0; e < 8; e++) tmp.v[i][e] = pw.v[i][e] * (1.f + gm.v[i][e]);
+  row_each<NC>([&](int i, int e) { tmp.v[i][e] = pw.v[i][e] * (1.f + gm.v[i][e]); });
   flush_col_partials<NC>(tmp, p.dpq, d, smem);
 }
 
@@ -835,7 +795,7 @@ template <int NC> __global__ __launch_bounds__(512) void adaln_pre_post_bwd_seg_
 #pragma unroll
       for (int e = 0; e < 8; e++) {
         ag.v[i][e] = 0.f; ab.v[i][e] = 0.f; az.v[i][e] = 0.f;
-        sc.v[i][e] = inst < 0 ? 1.f + sc.v[i][e] : sigmoidf_(sc.v[i][e]);
+        sc.v[i][e] = wrapper_scale(sc.v[i][e], inst);
       }
     constexpr int U = NC == 1 ? 4 : (NC == 2 ? 2 : 1);
     const int tend = t0 + len;
@@ -936,7 +896,7 @@ template <int NC> TFX_DEV float row_dot(const Row<NC>& a, const Row<NC>& b) {
 }
 TFX_DEV float lane_bcast(float v, int l) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l)); }
 
-// register form, kept for A/B (TFX_PULL_VARIANT=1): at most NJ sources, d w partials in registers, w rows in LDS, every row of a token requested
+// register form (the default for depth <= 8, d <= 512): at most NJ sources, d w partials in registers, w rows in LDS, every row of a token requested
 // at once and held in registers until used (two waves per SIMD, bytes in flight only while a wave waits).  DB: the wrapper's bias gradient (column sums
 // of dy) is accumulated here (8 more registers per lane; instantiated both ways so that a caller without a bias does not carry them).  Round 4's form
 // spilled 9 registers into the token loop at NJ = 8; with the segment's scale row in LDS (below) it is 246 (DB) / 238 registers, no spills
@@ -988,7 +948,7 @@ template <int NC, int NJ, bool DB> __global__ __launch_bounds__(512) void attnre
       for (int i = 0; i < NC; i++) {
         f32x4 s0, s1;
 #pragma unroll
-        for (int e = 0; e < 8; e++) { const float v = inst < 0 ? 1.f + sc.v[i][e] : sigmoidf_(sc.v[i][e]); if (e < 4) s0[e] = v; else s1[e - 4] = v; az.v[i][e] = 0.f; }
+        for (int e = 0; e < 8; e++) { const float v = wrapper_scale(sc.v[i][e], inst); if (e < 4) s0[e] = v; else s1[e - 4] = v; az.v[i][e] = 0.f; }
         *(f32x4*)(scl + (i * 2) * 256 + lane * 4) = s0; *(f32x4*)(scl + (i * 2 + 1) * 256 + lane * 4) = s1;
       }
     }
@@ -1292,7 +1252,7 @@ __global__ __launch_bounds__(512) void attnres_pull_dma_k(tfx_attnres_pull_args 
 #pragma unroll
         for (int e = 0; e < 8; e++) {
           const float z = (lane + 64 * i) * 8 < d ? sc.v[i][e] : 0.f;
-          sc.v[i][e] = inst < 0 ? 1.f + z : sigmoidf_(z); az.v[i][e] = 0.f;
+          sc.v[i][e] = wrapper_scale(z, inst); az.v[i][e] = 0.f;
         }
     }
     for (int t = t0; t < tend; t++) {
@@ -1835,10 +1795,7 @@ template <int NC> __global__ __launch_bounds__(256) void cosine_k(tfx_cosine_arg
   for (int t = blockIdx.x * WAVES + (threadIdx.x >> 6); t < p.T; t += gridDim.x * WAVES) {
     Row<NC> x;
     if (p.n_pad > 0 && t % p.n_pad >= p.n_valid) {
-#pragma unroll
-      for (int i = 0; i < NC; i++)
-#pragma unroll
-        for (int e = 0; e < 8; e++) x.v[i][e] = 0.f;
+      row_zero(x);
       store_row(x, p.dpred + (size_t)t * p.ld_d, d, lane);
       continue;
     }
@@ -1846,10 +1803,7 @@ template <int NC> __global__ __launch_bounds__(256) void cosine_k(tfx_cosine_arg
     load_row(x, p.pred + (size_t)t * p.ld_pred, d, lane);
     load_row(y, p.target + (size_t)t * p.ld_target, d, lane);
     float xy = 0.f, xx = 0.f, yy = 0.f;
-#pragma unroll
-    for (int i = 0; i < NC; i++)
-#pragma unroll
-      for (int e = 0; e < 8; e++) { xy += x.v[i][e] * y.v[i][e]; xx += x.v[i][e] * x.v[i][e]; yy += y.v[i][e] * y.v[i][e]; }
+    row_each<NC>([&](int i, int e) { xy += x.v[i][e] * y.v[i][e]; xx += x.v[i][e] * x.v[i][e]; yy += y.v[i][e] * y.v[i][e]; });
     xy = wave_sum(xy); xx = wave_sum(xx); yy = wave_sum(yy);
     const float nx = sqrtf(xx), ny = sqrtf(yy);
     const float inv = 1.f / (fmaxf(nx, 1e-8f) * fmaxf(ny, 1e-8f));
@@ -1857,10 +1811,7 @@ template <int NC> __global__ __launch_bounds__(256) void cosine_k(tfx_cosine_arg
     csum += c;
     // loss = 1 - mean c: d loss / d x = -grad_scale d c / d x; a norm under the clamp does not move with x
     const float ky = -p.grad_scale * inv, kx = nx > 1e-8f ? p.grad_scale * c / xx : 0.f;
-#pragma unroll
-    for (int i = 0; i < NC; i++)
-#pragma unroll
-      for (int e = 0; e < 8; e++) x.v[i][e] = ky * y.v[i][e] + kx * x.v[i][e];
+    row_each<NC>([&](int i, int e) { x.v[i][e] = ky * y.v[i][e] + kx * x.v[i][e]; });
     store_row(x, p.dpred + (size_t)t * p.ld_d, d, lane);
   }
   if (lane == 0) sacc[threadIdx.x >> 6] = csum;               // (wave-uniform: every lane holds the row sums)

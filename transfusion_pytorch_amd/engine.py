@@ -373,7 +373,7 @@ class Plan:
             self.lat[t]['add'] = z(R[t], d)      # additive token rows: the axial positional embedding (T:1384-1403, T:3173-3176), bf16
         self.acc = z(max(8, 2 + 3 * len(md.dim_latents)), dtype=torch.float32)      # [ce sum, ce count, flow sse per type..., velocity sse per type..., weighted recon sse per type...]
         # per layer: the soft-cap plan tfx_qk_norm_rope_fwd derives from the layer's QK-RMSNorm gains (tfx.h) and its attention kernels - forward
-        # and, later, backward - read: polynomial degree and coefficients from the BOUND on the scores, no look at the data.  TFX_SC_PLAN=0: decide from the scores
+        # and, later, backward - read: polynomial degree and coefficients from the BOUND on the scores, no look at the data.
         # Without QK-RMSNorm (md.qk_norm False) nothing bounds the scores: no plan, the attention kernels take their data-dependent form
         self.sc_plan = z(D, 8, dtype=torch.float32) if md.qk_norm else None
         # LASER attention (md.laser = its softclamp value; T:979-983): the attention reads v' = exp(c tanh(v / c)), written by tfx_laser_v_fwd behind the
