@@ -73,7 +73,7 @@ ROWS_CASES = [
 ]
 # [rows kernel: out 3.2e-3 plain, 2.1e-3 LASER; lse 5.2e-6]
 
-# tfx_attn_fwd with n_kv > 0: attn_fwd_pipe_kernel<false> with cache addressing (128-row query tiles of 4 waves x 32 rows, 64-key tiles of two
+# tfx_attn_fwd with n_kv > 0: attn_fwd_pipe_kernel<true> with cache addressing (128-row query tiles of 4 waves x 32 rows, 64-key tiles of two
 # 32-key units); 'trip' and 'pairs' again are the engine's tile_attn plans - one and two rows on the tiled kernel
 TILED_CASES = [
     TRIP,

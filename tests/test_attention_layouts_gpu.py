@@ -3,7 +3,7 @@ blocks at odd offsets, blocks on and across the 64-key / 128-query tile edges, c
 heads, dim_head 32; plan modes 0 / 1 (the training path: the generated dQ asm loop, the dK/dV kernel's mode-0/1 branches) and no plan (mode 2);
 LASER and the fused QK-norm / RoPE backward on a subset.  Per-row metrics (tests/_attn_cases.py ROW_TOL) besides the global ones, in every
 head, sentinel heads in which one key more or less moves a row by O(1), poisoned outputs and guard columns.  Then the forward against a KV cache in the
-compacted layout with long units, and the bit-identity of TFX_ATTN_BWD_PIPE=0 / TFX_ATTN_ASM=1 to the default."""
+compacted layout with long units, and the bit-identity of TFX_ATTN_BWD_PIPE=0 to the default."""
 import os
 import subprocess
 import sys
@@ -142,14 +142,14 @@ def call(fn, a):
 
 # ---------------------------------------------------------------------------------------------- bit-identity of the switches
 def test_attention_switches_are_bit_identical():
-    """tfx.h / attention.hip: TFX_ATTN_BWD_PIPE=0 (the plain-loop dQ kernel) and TFX_ATTN_ASM=1 (the generated forward loop for the unmasked tiles)
-    give the bits of the default.  The library reads each switch once per process: one child per setting (tests/_attn_hash_child.py) hashes
+    """tfx.h / attention.hip: TFX_ATTN_BWD_PIPE=0 (the plain-loop dQ kernel) gives the bits of the default (the generated dQ loop).
+    The library reads the switch once per process: one child per setting (tests/_attn_hash_child.py) hashes
     out, lse, d q~ | d k~ and d v | d gate over long-block layouts in plan modes none / 0 / 1."""
     child = os.path.join(os.path.dirname(os.path.abspath(__file__)), '_attn_hash_child.py')
     outs = []
-    for extra in ({}, {'TFX_ATTN_BWD_PIPE': '0'}, {'TFX_ATTN_ASM': '1'}):
+    for extra in ({}, {'TFX_ATTN_BWD_PIPE': '0'}):
         env = dict(os.environ)
-        env.pop('TFX_ATTN_BWD_PIPE', None); env.pop('TFX_ATTN_ASM', None)
+        env.pop('TFX_ATTN_BWD_PIPE', None)
         env.update(extra)
         r = subprocess.run([sys.executable, child], env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]

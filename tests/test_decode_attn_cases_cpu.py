@@ -31,7 +31,7 @@ def _waves(case):
 
 
 def test_tiled_cases_cover_the_cache_addressing():
-    """attn_fwd_pipe_kernel<false> with n_kv > 0: tile_kv_limit's true maximum, the per-wave kve_min, tile_dma's clamp at n_kv - 1"""
+    """attn_fwd_pipe_kernel<true> with n_kv > 0: tile_kv_limit's true maximum, the per-wave kve_min, tile_dma's clamp at n_kv - 1"""
     assert all(c.units is None for c in TILED_CASES)
     W = [w for c in TILED_CASES for w in _waves(c)]
     assert any(max(w) > w[-1] for _, _, _, w in W)                                   # a wave's largest kv_end not on its last row

@@ -414,16 +414,15 @@ def test_nt_gemm_kernel_selection():
 
 
 def test_generated_attention_loops_match_their_generator(tmp_path):
-    """round 6: the tile loops of the attention kernels that run as generated asm (tools/gen_attn_loops.py: forward unmasked tiles, backward dQ whole loop; soft-cap
-    plan modes 0 / 1) are committed under csrc/.  They must be what the generator writes today; MFMA counts per file (forward: 6 tiles x 16 with the fill and the
-    first unit's missing P.V; dQ: 8 tiles x 24 + fill 8 + drain 4 - 4, + 4 in each of 15 phases for the dQ a stopping wave still owes); the LDS wait tracker never asks for more than the 4-bit counter holds; every fixed register
+    """round 6: the tile loop of the attention backward dQ kernel that runs as generated asm (tools/gen_attn_loops.py: the whole loop; soft-cap plan modes 0 / 1)
+    is committed under csrc/.  The files must be what the generator writes today; MFMA count per file (8 tiles x 24 + fill 8 + drain 4 - 4, + 4 in each of 15 phases for the dQ a stopping wave still owes); the LDS wait tracker never asks for more than the 4-bit counter holds; every fixed register
     the loops name is in the clobber list the kernels hand to hipcc."""
     import re, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     csrc = os.path.join(root, 'transfusion_pytorch_amd', 'csrc')
     subprocess.run([sys.executable, os.path.join(root, 'tools', 'gen_attn_loops.py'), '--outdir', str(tmp_path)], check=True, capture_output=True)
     made = sorted(os.listdir(tmp_path))
-    assert made == ['attn_asm_clobbers.inc', 'attn_dq_loop_m0.inc', 'attn_dq_loop_m1.inc', 'attn_fwd_loop_m0.inc', 'attn_fwd_loop_m1.inc']
+    assert made == ['attn_asm_clobbers.inc', 'attn_dq_loop_m0.inc', 'attn_dq_loop_m1.inc']
     clob = set(re.findall(r'"v(\d+)"', open(os.path.join(csrc, 'attn_asm_clobbers.inc')).read()))
     for name in made:
         new, old = open(tmp_path / name).read(), open(os.path.join(csrc, name)).read()
@@ -431,12 +430,11 @@ def test_generated_attention_loops_match_their_generator(tmp_path):
         if name == 'attn_asm_clobbers.inc':
             continue
         lines = [ln.strip().strip('"').replace('\\n\\t', '') for ln in old.splitlines() if ln.startswith('"')]
-        assert sum(ln.startswith('v_mfma') for ln in lines) == (260 if '_dq_' in name else 96), name     # dQ: + 4 per phase for a wave's first dead phase
+        assert sum(ln.startswith('v_mfma') for ln in lines) == 260, name     # + 4 per phase for a wave's first dead phase
         assert all(int(m) <= 15 for ln in lines for m in re.findall(r'lgkmcnt\((\d+)\)', ln)), name
-        assert sum(ln == 's_barrier' for ln in lines) == (8 if '_dq_' in name else 6), name      # one barrier per tile, in every copy of the unrolled ring
-        if '_dq_' in name:                                                                       # (the forward's fixed registers are bound / clobbered by hand in attention.hip)
-            used = set(re.findall(r'\bv(\d+)\b', ' '.join(lines))) | {str(r) for a, b in re.findall(r'v\[(\d+):(\d+)\]', ' '.join(lines)) for r in range(int(a), int(b) + 1)}
-            assert used <= clob, sorted(used - clob, key=int)
+        assert sum(ln == 's_barrier' for ln in lines) == 8, name      # one barrier per tile, in every copy of the unrolled ring
+        used = set(re.findall(r'\bv(\d+)\b', ' '.join(lines))) | {str(r) for a, b in re.findall(r'v\[(\d+):(\d+)\]', ' '.join(lines)) for r in range(int(a), int(b) + 1)}
+        assert used <= clob, sorted(used - clob, key=int)
 
 
 def test_generated_asm_loops_match_their_generators(tmp_path):

@@ -1,8 +1,8 @@
 // Stand-alone probe of tfx_attn_fwd / tfx_attn_bwd (no PyTorch: starts in seconds on a fresh GPU box).  Built by tools/build_attn_probe.sh into tools/attn_probe.
 //
-//   TFX_ATTN_ASM=0 tools/attn_probe run ref [case ...]   # every case on the hipcc-scheduled kernels: time / hash, outputs dumped to /tmp/attnp_ref_<case>.bin
-//   TFX_ATTN_ASM=1 tools/attn_probe run asm [case ...]   # the same cases with the generated main loops (tools/gen_attn_loops.py)
-//   tools/attn_probe cmp ref asm                         # byte comparison of the dumps (same arithmetic order: bit-identical) + max abs difference
+//   ATTNP_BWD=1 TFX_ATTN_BWD_PIPE=0 tools/attn_probe run ref [case ...]   # every case, backward on the plain-loop dQ kernel: time / hash, outputs dumped to /tmp/attnp_ref_<case>.bin
+//   ATTNP_BWD=1 TFX_ATTN_BWD_PIPE=1 tools/attn_probe run asm [case ...]   # the same cases with the generated dQ loop (tools/gen_attn_loops.py; the default)
+//   tools/attn_probe cmp ref asm                                          # byte comparison of the dumps (same arithmetic order: bit-identical) + max abs difference
 //
 // The kernel choice is an environment switch the library reads once per process, hence two runs.  `bwd` in argv[1] position 2 runs the backward too.
 #include <hip/hip_runtime.h>

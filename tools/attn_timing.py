@@ -32,7 +32,7 @@ e0.record(); capi.call('tfx_attn_fwd', a, st); e1.record(); torch.cuda.synchroni
 print(f'attn_fwd b{b} h{h} n{n}: {e0.elapsed_time(e1) * 1e3:.1f} us')
 s = stamps.view(-1, 5).cpu().double()
 tiles = s[:, 4].sum()
-names = ['wait+barrier+dma issue', 'S=K.Q^T (mfma+frag reads)', 'softcap+exp (valu)', 'P.V (mfma+tr reads)'] if os.environ.get('TFX_ATTN_PIPE') == '0' else ['vmcnt wait + barrier', 'DMA issue', 'stage A: soft-cap (2 units)', 'stage B: exp/pack + 16 MFMA (2 units)']
+names = ['vmcnt wait + barrier', 'DMA issue', 'stage A: soft-cap (2 units)', 'stage B: exp/pack + 16 MFMA (2 units)']
 tot = s[:, :4].sum()
 for i in range(4):
     print(f'  {names[i]:28s} {float(s[:, i].sum() / tiles):8.0f} ticks per wave-tile  ({100 * float(s[:, i].sum() / tot):4.1f} %)')

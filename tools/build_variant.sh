@@ -13,7 +13,7 @@ else
   cp $W/transfusion_pytorch_amd/csrc/* $W/pkg/csrc/
 fi
 OBJS=""
-for s in gemm attention tokenwise decode collective runner; do
+for s in gemm attention tokenwise decode collective muon lora runner; do
   [ -f $W/pkg/csrc/$s.hip ] || continue
   FF=""; [ $s = attention ] && FF="-fno-slp-vectorize"      # (every revision: the product build always passes it, build.py FILE_FLAGS)
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -Wno-unused-result $FF "$@" -c $W/pkg/csrc/$s.hip -o $W/$s.o &

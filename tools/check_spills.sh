@@ -2,8 +2,13 @@
 # register budget of every kernel (VGPRs, spills, LDS): run after ANY kernel edit - a spilling hot loop costs more than any schedule gains
 # usage: bash tools/check_spills.sh            kernels that spill or take more than 128 VGPRs
 #        bash tools/check_spills.sh --all      every kernel, with SGPRs, scratch bytes, the number of instructions and a digest of its assembly text: a listing to
-#                                              join by kernel name with the same listing of another revision (equal digests = the same assembly text);
-#                                              profiles/tokenwise_row_helpers.txt is such a join
+#                                              join by kernel name with the same listing of another revision (equal digests = the same instruction stream).
+#                                              The digest is of the text between the kernel's label and the end of the function, normalised so that it is
+#                                              comparable across revisions: the compiler's comments (from `;` to the end of the line) and the lines they leave
+#                                              empty are dropped, the per-file function index of local labels (.LBB<n>_) becomes a fixed token, and so does
+#                                              the kernel's own mangled name - all three change when another kernel of the file comes or goes, or when a
+#                                              template parameter list changes.  profiles/attn_fwd_asm_removed.txt is such a join; digests from before this
+#                                              normalisation, such as those in profiles/tokenwise_row_helpers.txt, were computed on the raw text
 R=$(cd "$(dirname "$0")/.." && pwd)
 T=$(mktemp -d)
 for f in gemm attention tokenwise lora; do
@@ -24,7 +29,8 @@ for path in sorted(glob.glob(sys.argv[1] + '/*gfx950.s')):
             if m and cur is None: cur = m.group(1); count[cur] = 0; body[cur] = hashlib.md5()
             elif cur and ln.startswith('.Lfunc_end'): cur = None
             elif cur:
-                body[cur].update(ln.encode() + b'\n')
+                norm = re.sub(r'\.LBB\d+_', '.LBB_', ln.split(';')[0].rstrip()).replace(cur, 'KERNEL')
+                if norm: body[cur].update(norm.encode() + b'\n')
                 if re.match(r'^\s+[a-z]', ln): count[cur] += 1
     for m in re.finditer(r'\.group_segment_fixed_size:\s*(\d+).*?\.name:\s*(\S+).*?\.private_segment_fixed_size:\s*(\d+).*?\.sgpr_count:\s*(\d+).*?\.vgpr_count:\s*(\d+)\s*\n\s*\.vgpr_spill_count:\s*(\d+)', txt, re.S):
         lds, name, priv, sg, vg, sp = int(m.group(1)), m.group(2), int(m.group(3)), int(m.group(4)), int(m.group(5)), int(m.group(6))
