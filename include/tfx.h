@@ -509,6 +509,35 @@ int tfx_sample_tokens(const float* logits, int32_t ld, int32_t B, int32_t V, flo
  * there and its argmax takes the first.  temperature < 0 is refused (-3) by both. */
 int tfx_sample_tokens_range(const float* logits, int32_t ld, int32_t B, int32_t V, int32_t V_draw, float temperature, float min_p, const float* uniforms,
                             const int32_t* active, int32_t* out_ids, void* stream);
+/* The range draw behind top-k and top-p (nucleus) filters next to min-p, one launch.  These two filters are NOT the reference's (it has min-p only);
+ * they are pinned to this text.  Per row: V valid fp32 logits, candidates = the columns c < V_draw (V_draw <= V), temperature T > 0, min_p >= 0,
+ * top_k >= 0, top_p > 0;  l_max = the maximum over ALL V columns,  r_c = exp((l_c - l_max) / T).
+ *   top-k  (top_k == 0: off)  l_(k) = the k-th largest candidate logit; a candidate survives iff l_c >= l_(k).  Ties at the k-th place all survive;
+ *          top_k >= V_draw keeps every candidate.  The comparison is on logits, not on r (-0 and +0 are equal).
+ *   top-p  (top_p >= 1: off)  over the top-k survivors S:  M = sum of r over S,  G(x) = sum of r_c over c in S with r_c > x;  c survives iff
+ *          G(r_c) < top_p M - the smallest descending prefix whose mass reaches top_p, ties at its boundary all kept.  A threshold set
+ *          {r_c >= tau_p}, independent of the index order, never empty (the best candidate has G = 0).
+ *   min-p  as above: r_c >= min_p, against the global maximum - which with V_draw < V may lie outside the draw range.
+ * The surviving set is the intersection of the three (= the usual temperature -> top-k -> top-p -> min-p chain: min-p relative to the maximum does
+ * not change under renormalisation), i.e. two thresholds per row: one on the logit, and max(tau_p, min_p) on r.  The mass pass and the inverse-CDF
+ * scan then run as in tfx_sample_tokens_range, in index order, with its fallbacks: rounding at u close to 1 -> the last survivor below V_draw; no
+ * survivor (only from min-p with V_draw < V) -> V_draw.  temperature == 0: the argmax over all V, filters ignored.  r_c is spelled once and the
+ * membership test is the same, bit for bit, in the threshold searches, the mass pass and the scan.  With top_k == 0 and top_p >= 1 the ids are those of
+ * tfx_sample_tokens_range for the same uniforms, exactly.  Returns -3 and launches nothing for temperature < 0, top_k < 0, top_p <= 0 or NaN,
+ * V_draw < 1 or V_draw > V.
+ * Method: both thresholds by a 16-way search over bit patterns, 4 bits per pass - top-k over the order-preserving integer key of the logit (the
+ * largest t with count(key >= t) >= k), top-p over the bit pattern of r (the largest x with G(x) >= top_p M; fp32 addition in a fixed order is
+ * monotone in every term, so the fp32 G does not grow with x).  Passes over the row: 1 (maximum) + 8 (top-k, if on) + 1 + 8 (M and top-p, if on)
+ * + 2 (mass, scan); no host round trip.  Width classes: V <= TFX_SAMPLE_NARROW_MAX - one wave per row, four rows per block; wider - one block of
+ * 16 waves per row, whose first wave alone makes the mass pass and the scan (so "filters off" is tfx_sample_tokens_range at every width).
+ * Rounding of M and G (all terms >= 0, so relative to the sum itself): each thread adds its ceil(V_draw / (64 W)) columns in index order (W = 1 or
+ * 16 waves per row), a 6-step wave tree follows, then the W wave totals are added in wave order:
+ *     |error| <= (ceil(V_draw / (64 W)) + 6 + W - 1) 2^-24     W = 1: 1.3e-6 at 1024 columns;  W = 16: 1.5e-6 at 4100 and 3.2e-6 at 32 000 columns;
+ * r itself carries the error of the hardware exponential, about 2e-6 relative at |argument| <= 20.  A row whose M (or top_p M) underflows to 0 in
+ * fp32 is left unfiltered by top-p; no column of such a row with r == 0 is drawn. */
+enum { TFX_SAMPLE_NARROW_MAX = 1024 };
+int tfx_sample_tokens_filtered(const float* logits, int32_t ld, int32_t B, int32_t V, int32_t V_draw, float temperature, float min_p, int32_t top_k,
+                               float top_p, const float* uniforms, const int32_t* active, int32_t* out_ids, void* stream);
 /* ODE state update of the fixed-grid midpoint solver (torchdiffeq semantics; T:2468-2525) fused with classifier-free
  * guidance (T:2516-2521): f = f_uncond ? f_uncond + cfg_scale * (f_cond - f_uncond) : f_cond;  out = y + a * f   (fp32, n elements) */
 int tfx_ode_axpy(const float* y, const float* f_cond, const float* f_uncond, float cfg_scale, float a, float* out, int64_t n, void* stream);

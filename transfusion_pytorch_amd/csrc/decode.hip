@@ -53,6 +53,166 @@ __global__ __launch_bounds__(256) void sample_tokens_k(const float* logits, int 
   if (lane == 0) out_ids[row] = pick;
 }
 
+// ---- the draw behind top-k / top-p / min-p filters (tfx.h: tfx_sample_tokens_filtered) ----
+// Every filter is a threshold: a column of the draw range survives when its logit key >= key_thr (top-k), the bit pattern of its r >= tau (top-p)
+// and r >= min_p.  The two searches find key_thr and tau by 4 bits per pass over the row; the mass pass and the scan are those of sample_tokens_k
+// with this membership test in place of `r >= min_p`.  NW waves share a row: 1 (four rows per 256-thread block) or 16 (one row per block).
+
+// order-preserving integer key of an fp32 logit (-0 counts as +0: the two compare equal as floats)
+TFX_DEV uint32_t logit_key(float v) {
+  const uint32_t b = __builtin_bit_cast(uint32_t, v + 0.f);
+  return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
+}
+// the one spelling of a column's r = p_c / p_max and of its membership, used by the threshold searches, the mass pass and the scan alike
+TFX_DEV float sample_ratio(float l, float best, float it) { return __expf((l - best) * it); }
+TFX_DEV bool sample_kept(float l, float r, uint32_t key_thr, uint32_t tau, float min_p) {
+  return logit_key(l) >= key_thr && __builtin_bit_cast(uint32_t, r) >= tau && r >= min_p;
+}
+
+TFX_DEV int wave_sum_i(int v) {                          // wave_sum's DPP steps on integers
+#define TFX_DPP_ADD_I(CTRL, ROWMASK) v += __builtin_amdgcn_update_dpp(0, v, CTRL, ROWMASK, 0xf, false)
+  TFX_DPP_ADD_I(0xB1, 0xf); TFX_DPP_ADD_I(0x4E, 0xf); TFX_DPP_ADD_I(0x141, 0xf); TFX_DPP_ADD_I(0x140, 0xf);
+  TFX_DPP_ADD_I(0x142, 0xa); TFX_DPP_ADD_I(0x143, 0xc);
+#undef TFX_DPP_ADD_I
+  return __builtin_amdgcn_readlane(v, 63);
+}
+TFX_DEV float wave_total(float v) { return wave_sum(v); }
+TFX_DEV int wave_total(int v) { return wave_sum_i(v); }
+
+// row total of a thread-strided partial: the wave tree, then (NW > 1) the waves' totals added in wave order.  sm: NW entries.
+template <int NW> TFX_DEV float row_total(float v, float* sm) {
+  v = wave_sum(v);
+  if (NW == 1) return v;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) sm[wave] = v;
+  __syncthreads();
+  float tot = 0.f;
+#pragma unroll
+  for (int w = 0; w < NW; w++) tot += sm[w];
+  __syncthreads();
+  return tot;
+}
+// one search step: a[d], d = 1..15, are this thread's partials of a row quantity that does not grow with d; returns the largest d whose row
+// total is >= bound, 0 when there is none.  Totals as in row_total.  sm: NW x 16 entries, digit: one shared word (both unused with NW == 1).
+template <int NW, typename T> TFX_DEV int top_digit(const T (&a)[16], T bound, T* sm, int* digit) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (NW == 1) {
+    int dg = 0;
+#pragma unroll
+    for (int d = 1; d < 16; d++) if (wave_total(a[d]) >= bound) dg = d;
+    return dg;
+  }
+#pragma unroll
+  for (int d = 1; d < 16; d++) { const T s = wave_total(a[d]); if (lane == 0) sm[wave * 16 + d] = s; }
+  __syncthreads();
+  if (wave == 0) {
+    const bool mine = lane >= 1 && lane < 16;
+    T tot = 0;
+    if (mine) for (int w = 0; w < NW; w++) tot += sm[w * 16 + lane];
+    const unsigned long long m = __ballot(mine && tot >= bound);
+    if (lane == 0) *digit = m ? 63 - __builtin_clzll(m) : 0;
+  }
+  __syncthreads();
+  return *digit;
+}
+
+template <int NW>
+__global__ __launch_bounds__(NW == 1 ? 256 : 64 * NW) void sample_tokens_filtered_k(const float* logits, int ld, int B, int V, int V_draw, float temperature,
+                                                                                  float min_p, int top_k, float top_p, const float* uniforms,
+                                                                                  const int* active, int* out_ids) {
+  constexpr int TPR = 64 * NW;                           // threads per row
+  __shared__ float sm_f[NW * 16];
+  __shared__ int sm_i[NW * 16];
+  __shared__ int sm_digit;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int row = NW == 1 ? blockIdx.x * 4 + wave : blockIdx.x;
+  const int t0 = NW == 1 ? lane : threadIdx.x;           // this thread's first column
+  if (row >= B) return;                                  // (uniform over the threads that share a row, hence over the block when NW > 1)
+  if (active && !active[row]) return;
+  const float* lg = logits + (size_t)row * ld;
+  // pass 1: maximum over all V and its first index
+  float best = -__builtin_inff(); int bi = 0x7fffffff;
+  for (int c = t0; c < V; c += TPR) { const float v = lg[c]; if (v > best) { best = v; bi = c; } }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64);
+    if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+  }
+  if (NW > 1) {
+    if (lane == 0) { sm_f[wave] = best; sm_i[wave] = bi; }
+    __syncthreads();
+    for (int w = 0; w < NW; w++) {
+      const float ov = sm_f[w]; const int oi = sm_i[w];
+      if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+    }
+    __syncthreads();
+  }
+  if (temperature == 0.f) { if (lane == 0 && (NW == 1 || wave == 0)) out_ids[row] = bi; return; }
+  const float it = 1.f / temperature;
+  // top-k: key_thr = the k-th largest key of the draw range = the largest t with count(key >= t) >= k, 4 bits per pass from the top
+  uint32_t key_thr = 0;
+  if (top_k > 0 && top_k < V_draw) {
+    for (int shift = 28; shift >= 0; shift -= 4) {
+      int cnt[16] = {};
+      for (int c = t0; c < V_draw; c += TPR) {
+        const uint32_t k = logit_key(lg[c]);
+#pragma unroll
+        for (int d = 1; d < 16; d++) cnt[d] += k >= (key_thr | (uint32_t)d << shift) ? 1 : 0;
+      }
+      key_thr |= (uint32_t)top_digit<NW, int>(cnt, top_k, sm_i, &sm_digit) << shift;
+    }
+  }
+  // top-p over the top-k survivors: G(x) = sum of r over survivors with bits(r) > x does not grow with x (fp32 addition in a fixed order is
+  // monotone in every term); y = the largest x with G(x) >= top_p M, so the survivors are bits(r) > y, i.e. >= tau = y + 1.  r <= 1 keeps y below
+  // the bit pattern of 1.  A row whose M or top_p M underflows to 0 is left unfiltered by top-p (nothing of it is drawn with r == 0 anyway).
+  uint32_t tau = 0;
+  if (top_p < 1.f) {
+    float m = 0.f;
+    for (int c = t0; c < V_draw; c += TPR) { const float l = lg[c]; m += logit_key(l) >= key_thr ? sample_ratio(l, best, it) : 0.f; }
+    const float P = top_p * row_total<NW>(m, sm_f);
+    if (P > 0.f) {
+      uint32_t y = 0;
+      for (int shift = 28; shift >= 0; shift -= 4) {
+        float g[16] = {};
+        for (int c = t0; c < V_draw; c += TPR) {
+          const float l = lg[c], r = sample_ratio(l, best, it);
+          const uint32_t rb = logit_key(l) >= key_thr ? __builtin_bit_cast(uint32_t, r) : 0u;      // (0 is above no threshold)
+#pragma unroll
+          for (int d = 1; d < 16; d++) g[d] += rb > (y | (uint32_t)d << shift) ? r : 0.f;
+        }
+        y |= (uint32_t)top_digit<NW, float>(g, P, sm_f, &sm_digit) << shift;
+      }
+      tau = y + 1;
+    }
+  }
+  if (NW > 1 && wave != 0) return;                       // the draw is one wave's, in sample_tokens_k's order: filters off = its result to the bit
+  // surviving mass, then the inverse CDF in index order, 64 columns per step with a wave prefix sum (sample_tokens_k's passes 2 and 3)
+  float mass = 0.f;
+  for (int c = lane; c < V_draw; c += 64) {
+    const float l = lg[c], r = sample_ratio(l, best, it);
+    mass += sample_kept(l, r, key_thr, tau, min_p) ? r : 0.f;
+  }
+  mass = wave_sum(mass);
+  const float target = uniforms[row] * mass;
+  float run = 0.f; int pick = -1, last = -1;
+  bool done = false;
+  for (int c0 = 0; c0 < V_draw && !done; c0 += 64) {
+    const int c = c0 + lane;
+    float r = 0.f;
+    if (c < V_draw) { const float l = lg[c]; r = sample_ratio(l, best, it); r = sample_kept(l, r, key_thr, tau, min_p) ? r : 0.f; }
+    float pre = r;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const float t = __shfl_up(pre, o, 64); if (lane >= o) pre += t; }
+    const bool hit = r > 0.f && run + pre > target;
+    const unsigned long long m = __ballot(hit), alive = __ballot(r > 0.f);
+    if (m) { pick = c0 + __builtin_ctzll(m); done = true; }
+    else if (alive) last = c0 + 63 - __builtin_clzll(alive);
+    run += __shfl(pre, 63, 64);
+  }
+  if (!done) pick = last >= 0 ? last : V_draw < V ? V_draw : bi;
+  if (lane == 0) out_ids[row] = pick;
+}
+
 // out = y + a * f with f = f_cond, or f_uncond + cfg * (f_cond - f_uncond) when f_uncond is given (classifier-free guidance, T:2516-2521)
 __global__ void ode_axpy_k(const float* y, const float* fc, const float* fu, float cfg, float a, float* out, long long n) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -306,6 +466,19 @@ int tfx_sample_tokens_range(const float* logits, int32_t ld, int32_t B, int32_t 
   if (!logits || !out_ids || V <= 0 || V_draw <= 0 || V_draw > V || ld < V || (temperature != 0.f && !uniforms)) return -1;
   if (temperature < 0.f) return -3;
   hipLaunchKernelGGL(sample_tokens_k, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)s, logits, ld, B, V, temperature, min_p, uniforms, active, out_ids, V_draw);
+  return (int)hipGetLastError();
+}
+int tfx_sample_tokens_filtered(const float* logits, int32_t ld, int32_t B, int32_t V, int32_t V_draw, float temperature, float min_p, int32_t top_k,
+                               float top_p, const float* uniforms, const int32_t* active, int32_t* out_ids, void* s) {
+  if (temperature < 0.f || top_k < 0 || !(top_p > 0.f) || V_draw < 1 || V_draw > V) return -3;
+  if (B <= 0) return 0;
+  if (!logits || !out_ids || ld < V || (temperature != 0.f && !uniforms)) return -1;
+  if (V <= TFX_SAMPLE_NARROW_MAX)
+    hipLaunchKernelGGL(sample_tokens_filtered_k<1>, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)s, logits, ld, B, V, V_draw, temperature, min_p, top_k,
+                       top_p, uniforms, active, out_ids);
+  else
+    hipLaunchKernelGGL(sample_tokens_filtered_k<16>, dim3(B), dim3(1024), 0, (hipStream_t)s, logits, ld, B, V, V_draw, temperature, min_p, top_k, top_p,
+                       uniforms, active, out_ids);
   return (int)hipGetLastError();
 }
 int tfx_ode_axpy(const float* y, const float* f_cond, const float* f_uncond, float cfg_scale, float a, float* out, int64_t n, void* s) {

@@ -124,30 +124,47 @@ class _Call:                                    # the constants of one `sample_m
     B: int; H: int; use_cfg: bool; stream: int  # H: guidance halves of a forward - 2 under classifier-free guidance (`use_cfg`), else 1
     max_length: int; temperature: float; min_p: float; fixed_shape: tuple | None; init_noise: torch.Tensor | None
     modality_steps: int; cfg_scale: float       # modality_steps: grid points of the solver
+    top_k: int | None = None; top_p: float | None = None     # text filters of tfx_sample_tokens_filtered (None = off)
 
 
-def _sample_text_token(logits, V, temperature, min_p, stream):
-    """sample_text_token (T:597-605) incl. min_p_filter (T:591-595) on the device: `tfx_sample_tokens` over the rows of a 2-d fp32
-    logits tensor (V valid columns).  Returns int32 ids on the device."""
+def _filters_on(top_k, top_p):
+    """whether a (validated) top-k / top-p pair filters at all: None, top_k 0 and top_p >= 1 are off"""
+    return bool(top_k) or (top_p is not None and top_p < 1.)
+
+
+def _draw(logits, V, V_draw, temperature, min_p, top_k, top_p, stream):
+    """one sampler launch over the rows of a 2-d fp32 logits tensor: the launch of old (`tfx_sample_tokens`; `tfx_sample_tokens_range` when a draw
+    range `V_draw` is given) with both filters off, `tfx_sample_tokens_filtered` otherwise.  One `torch.rand(B)` per call at a temperature
+    either way, so a seeded run consumes the generator identically with and without filters.  Returns int32 ids on the device."""
     assert logits.dim() == 2 and logits.dtype == torch.float32 and logits.stride(1) == 1
     B = logits.shape[0]
     out = torch.empty(B, dtype=torch.int32, device=logits.device)
     u = torch.rand(B, device=logits.device) if temperature != 0. else None
-    capi.check(capi.lib().tfx_sample_tokens(logits.data_ptr(), logits.stride(0), B, V, float(temperature), float(min_p), capi.ptr(u), None,
-                                            out.data_ptr(), ctypes.c_void_p(stream)), 'tfx_sample_tokens')
+    L, s = capi.lib(), ctypes.c_void_p(stream)
+    if _filters_on(top_k, top_p):
+        capi.check(L.tfx_sample_tokens_filtered(logits.data_ptr(), logits.stride(0), B, V, V if V_draw is None else V_draw, float(temperature),
+                                                float(min_p), int(top_k or 0), 1. if top_p is None else float(top_p), capi.ptr(u), None, out.data_ptr(), s),
+                   'tfx_sample_tokens_filtered')
+    elif V_draw is None:
+        capi.check(L.tfx_sample_tokens(logits.data_ptr(), logits.stride(0), B, V, float(temperature), float(min_p), capi.ptr(u), None, out.data_ptr(), s),
+                   'tfx_sample_tokens')
+    else:
+        capi.check(L.tfx_sample_tokens_range(logits.data_ptr(), logits.stride(0), B, V, V_draw, float(temperature), float(min_p), capi.ptr(u), None,
+                                             out.data_ptr(), s), 'tfx_sample_tokens_range')
     return out
 
 
-def _pick_text_only(logits, V, N, temperature, min_p, stream):
+def _sample_text_token(logits, V, temperature, min_p, stream, top_k=None, top_p=None):
+    """sample_text_token (T:597-605) incl. min_p_filter (T:591-595) on the device, over the rows of a 2-d fp32 logits tensor (V valid columns);
+    `top_k` / `top_p`: the filters of `tfx_sample_tokens_filtered` (include/tfx.h; not the reference's).  Returns int32 ids on the device."""
+    return _draw(logits, V, None, temperature, min_p, top_k, top_p, stream)
+
+
+def _pick_text_only(logits, V, N, temperature, min_p, stream, top_k=None, top_p=None):
     """the draw of `generate_text_only` (T:2690-2698) on the device: temperature 0 -> argmax over ALL V logits; else the min-p filter over all V
-    logits (threshold relative to the global maximum), then the text-only mask (first N columns), then the draw."""
-    assert logits.dim() == 2 and logits.dtype == torch.float32 and logits.stride(1) == 1
-    B = logits.shape[0]
-    out = torch.empty(B, dtype=torch.int32, device=logits.device)
-    u = torch.rand(B, device=logits.device) if temperature != 0. else None
-    capi.check(capi.lib().tfx_sample_tokens_range(logits.data_ptr(), logits.stride(0), B, V, N if temperature != 0. else V, float(temperature), float(min_p),
-                                                  capi.ptr(u), None, out.data_ptr(), ctypes.c_void_p(stream)), 'tfx_sample_tokens_range')
-    return out.long()
+    logits (threshold relative to the global maximum), then the text-only mask (first N columns), then the draw.  `top_k` / `top_p` count and
+    weigh the text tokens only (the candidates of `tfx_sample_tokens_filtered` are the draw range): the mask comes before them."""
+    return _draw(logits, V, N if temperature != 0. else V, temperature, min_p, top_k, top_p, stream).long()
 
 
 def _ode_axpy(y, f_cond, f_uncond, cfg_scale, a, stream):
@@ -493,7 +510,7 @@ class Sampler:
 
     # ------------------------------------------------------------------ main
     def sample_many(self, prompts, max_length, text_temperature, text_min_p, fixed_modality_shape, force_modality_at_start,
-                    init_modality_noise, modality_steps, cfg_scale, pos_emb_in_decode=False):
+                    init_modality_noise, modality_steps, cfg_scale, pos_emb_in_decode=False, text_top_k=None, text_top_p=None):
         m, md, dev = self.m, self.md, self.dev
         self.pos_emb_in_decode, self._grew = pos_emb_in_decode, False
         m._require_gpu()
@@ -504,7 +521,7 @@ class Sampler:
         # of one buffer (the text steps use the first half through a view)
         use_cfg = cfg_scale != 1.
         c = _Call(B, 2 if use_cfg else 1, use_cfg, m._stream(), max_length, text_temperature, text_min_p, fixed_modality_shape, init_modality_noise,
-                  modality_steps, cfg_scale)
+                  modality_steps, cfg_scale, text_top_k, text_top_p)
 
         # ---- batched prefill (T:2194-2201): prompted modalities conditioned at t = 1, no meta tokens re-added
         max_past = max((s.num_past_modalities for s in states), default=0)
@@ -523,7 +540,7 @@ class Sampler:
         for st in states:
             self._maybe_transition(st, fixed_modality_shape)
         last_rows = torch.tensor([i * n0 + s.cache_len - 1 for i, s in enumerate(states)], device=dev)
-        first = _sample_text_token(plan.logits.index_select(0, last_rows), md.vocab, text_temperature, text_min_p, c.stream).tolist()
+        first = _sample_text_token(plan.logits.index_select(0, last_rows), md.vocab, text_temperature, text_min_p, c.stream, c.top_k, c.top_p).tolist()
         for st, tok in zip(states, first):
             if st.phase != 'text':
                 st.budget(max_length)
@@ -613,7 +630,7 @@ class Sampler:
             toks = None
             if r.is_t.any():
                 lg = p.logits.view(c.H * B, Lq, md.vp)[:B, Lq - 1] if lay.units is None else p.logits.view(p.T, md.vp).index_select(0, p.unit_txt[:B])
-                toks = _sample_text_token(lg, md.vocab, c.temperature, c.min_p, c.stream).tolist()      # host sync
+                toks = _sample_text_token(lg, md.vocab, c.temperature, c.min_p, c.stream, c.top_k, c.top_p).tolist()      # host sync
                 async_steps = 0
             else:
                 async_steps += 1
@@ -736,7 +753,7 @@ class Sampler:
                     ids[i], pos[i], kve[i], rot[i] = st.last_token, i * cache.shape[2] + st.cache_len, st.cache_len + 1, st.tokens_seen
             self._load(p, ids=ids, pos=pos, kve=kve, rot=rot, tok_inst=np.full(B, -1, np.int32))
             self._run(p, c.stream, 0, p.fwd_logits_end)
-            toks = _sample_text_token(p.logits, md.vocab, c.temperature, c.min_p, c.stream).tolist()
+            toks = _sample_text_token(p.logits, md.vocab, c.temperature, c.min_p, c.stream, c.top_k, c.top_p).tolist()
             for st, tok in zip(states, toks):
                 if st.phase == 'text':
                     st.fed(False)
@@ -789,7 +806,7 @@ class Sampler:
         return joint
 
     # ------------------------------------------------------------------ pure-text generation (T:2666-2707)
-    def generate_text_only(self, prompt, seq_len, temperature, min_p):
+    def generate_text_only(self, prompt, seq_len, temperature, min_p, top_k=None, top_p=None):
         """KV-cached greedy / min-p sampling of text only: prefill the prompt once, then one-token decode plans.
         Mirrors the reference exactly: temperature 0 takes the argmax over ALL logits, otherwise min-p filter, then the
         text-only mask (T:2690-2698)."""
@@ -802,7 +819,7 @@ class Sampler:
         if num == 0:
             return out
         stream = m._stream()
-        pick = lambda logits: _pick_text_only(logits, md.vocab, m.num_text_tokens, temperature, min_p, stream)
+        pick = lambda logits: _pick_text_only(logits, md.vocab, m.num_text_tokens, temperature, min_p, stream, top_k, top_p)
         plan, S = m._forward_plain([[row] for row in prompt], torch.ones(B, 1, device=dev), add_meta=False)
         n_pad = S['n']
         maxlen = (max(n_pad, n0 + num) + 64) // 64 * 64

@@ -126,6 +126,23 @@ def _bucket(x: int, min_step: int) -> int:
 _TRAIN_PAD = 64
 
 
+def _check_text_filters(top_k, top_p):
+    """the top-k / top-p arguments of the text samplers (include/tfx.h: tfx_sample_tokens_filtered), checked once for every route.
+    top_k: None or an int >= 0 (0 = off; bool refused); top_p: None or a real number in (0, 1] (1 = off)."""
+    import numbers
+    if top_k is not None:
+        if isinstance(top_k, bool) or not isinstance(top_k, numbers.Integral):
+            raise TypeError(f'top_k must be None or an int >= 0, got {top_k!r}')
+        if top_k < 0:
+            raise ValueError(f'top_k must be >= 0, got {top_k}')
+        top_k = min(int(top_k), 2 ** 31 - 1)                 # (more than any row has columns: every candidate is kept)
+    if top_p is not None:
+        if isinstance(top_p, bool) or not isinstance(top_p, numbers.Real) or not 0. < float(top_p) <= 1.:
+            raise ValueError(f'top_p must be None or a number in (0, 1], got {top_p!r}')
+        top_p = float(top_p)
+    return top_k, top_p
+
+
 def _num_modalities(sample):
     """modality instances of one sample: `(type, tensor)` tuples and bare float tensors (type 0)"""
     return sum(1 for p in sample if isinstance(p, tuple) or (torch.is_tensor(p) and p.is_floating_point()))
@@ -1711,11 +1728,14 @@ class Transfusion(nn.Module):
     @torch.no_grad()
     def sample_many(self, prompts=None, max_length=2048, text_temperature=1., text_min_p=0.1, fixed_modality_shape=None,
                     force_modality_at_start=None, init_modality_noise=None, modality_steps=16, return_unprocessed_modalities=False,
-                    cfg_scale=3., _pos_emb_in_decode=False):
+                    cfg_scale=3., _pos_emb_in_decode=False, text_top_k=None, text_top_p=None):
         """T:2082-2583.  `_pos_emb_in_decode`: with `add_pos_emb`, the reference's two samplers differ - `sample_many` feeds the ODE evaluations
         the bare projected latents (project_to_model, T:2436-2444 / T:2472-2475: no positional embedding), while `sample_one`, going through
-        `forward()`, adds it (T:3179-3180).  Each entry point keeps its own reference's behaviour; prompted modalities carry it in both (T:2194)."""
+        `forward()`, adds it (T:3179-3180).  Each entry point keeps its own reference's behaviour; prompted modalities carry it in both (T:2194).
+        `text_top_k` / `text_top_p`: top-k and nucleus filters of the text draw next to min-p, on the device (include/tfx.h:
+        tfx_sample_tokens_filtered; not the reference's, which has min-p only).  None, 0 and 1.0 are off."""
         from .sampling import Sampler
+        text_top_k, text_top_p = _check_text_filters(text_top_k, text_top_p)
         was_training = self.training
         self.eval()                                              # @temp_eval in the reference
         try:
@@ -1727,7 +1747,8 @@ class Transfusion(nn.Module):
                 plist = prompts if isinstance(prompts, list) else [prompts]
                 outs = [self._sample_one_through_forward(pr, max_length=max_length, text_temperature=text_temperature, text_min_p=text_min_p, cache_kv=False,
                                                          fixed_modality_shape=fixed_modality_shape, force_modality_at_start=force_modality_at_start,
-                                                         init_modality_noise=init_modality_noise, modality_steps=modality_steps, cfg_scale=cfg_scale)
+                                                         init_modality_noise=init_modality_noise, modality_steps=modality_steps, cfg_scale=cfg_scale,
+                                                         text_top_k=text_top_k, text_top_p=text_top_p)
                         for pr in plist]
                 return outs if return_unprocessed_modalities else self.decode_modalities(outs)
             special = any(self.channel_first_latent) or any(e is not None for e in self.modality_encoder) or any(d is not None for d in self.modality_decoder)
@@ -1736,7 +1757,7 @@ class Transfusion(nn.Module):
             out = Sampler(self).sample_many(prompts, max_length=max_length, text_temperature=text_temperature, text_min_p=text_min_p,
                                             fixed_modality_shape=fixed_modality_shape, force_modality_at_start=force_modality_at_start,
                                             init_modality_noise=init_modality_noise, modality_steps=modality_steps, cfg_scale=cfg_scale,
-                                            pos_emb_in_decode=_pos_emb_in_decode)
+                                            pos_emb_in_decode=_pos_emb_in_decode, text_top_k=text_top_k, text_top_p=text_top_p)
             if special:
                 out = [[(p[0], self._from_channel_last(p[0], p[1])) if isinstance(p, tuple) else p for p in sample] for sample in out]
                 if not return_unprocessed_modalities:
@@ -1763,7 +1784,8 @@ class Transfusion(nn.Module):
 
     @torch.no_grad()
     def sample_one(self, prompt=None, max_length=2048, text_temperature=1., text_min_p=0.1, cache_kv=None, fixed_modality_shape=None,
-                   force_modality_at_start=None, init_modality_noise=None, modality_steps=16, return_unprocessed_modalities=False, cfg_scale=3.):
+                   force_modality_at_start=None, init_modality_noise=None, modality_steps=16, return_unprocessed_modalities=False, cfg_scale=3.,
+                   text_top_k=None, text_top_p=None):
         """T:1845-1858.  The reference asserts sample_many == per-prompt sample_one (tests/test_transfusion.py:758-808); here
         sample_one IS the batch-of-one case of the KV-cached decoder.
         `cache_kv`: None (the default here; the reference's default is False) and True run that decoder - it is always KV-cached.  An EXPLICIT
@@ -1776,25 +1798,29 @@ class Transfusion(nn.Module):
             try:
                 out = self._sample_one_through_forward(prompt, max_length=max_length, text_temperature=text_temperature, text_min_p=text_min_p, cache_kv=False,
                                                        fixed_modality_shape=fixed_modality_shape, force_modality_at_start=force_modality_at_start,
-                                                       init_modality_noise=init_modality_noise, modality_steps=modality_steps, cfg_scale=cfg_scale)
+                                                       init_modality_noise=init_modality_noise, modality_steps=modality_steps, cfg_scale=cfg_scale,
+                                                       text_top_k=text_top_k, text_top_p=text_top_p)
                 return out if return_unprocessed_modalities else self.decode_modalities(out)
             finally:
                 self.train(was_training)
         return self.sample_many([prompt], max_length=max_length, text_temperature=text_temperature, text_min_p=text_min_p,
                                 fixed_modality_shape=fixed_modality_shape, force_modality_at_start=force_modality_at_start,
                                 init_modality_noise=init_modality_noise, modality_steps=modality_steps,
-                                return_unprocessed_modalities=return_unprocessed_modalities, cfg_scale=cfg_scale, _pos_emb_in_decode=True)[0]
+                                return_unprocessed_modalities=return_unprocessed_modalities, cfg_scale=cfg_scale, _pos_emb_in_decode=True,
+                                text_top_k=text_top_k, text_top_p=text_top_p)[0]
 
     sample = sample_one
 
     @torch.no_grad()
     def _sample_one_through_forward(self, prompt=None, max_length=2048, text_temperature=1., text_min_p=0.1, cache_kv=False, fixed_modality_shape=None,
-                                    force_modality_at_start=None, init_modality_noise=None, modality_steps=16, cfg_scale=3.):
+                                    force_modality_at_start=None, init_modality_noise=None, modality_steps=16, cfg_scale=3.,
+                                    text_top_k=None, text_top_p=None):
         """The reference's `sample_one` loop (T:1858-2075) written against the PUBLIC decode contract of `forward()` - one `forward(...)` per
         text token (T:1917-1924) and per ODE evaluation (T:1998-2006, T:2021-2029), with (`cache_kv=True`) or without the kv cache it returns.
         `sample_one` itself runs the batched KV-cached decoder; this loop exists so that the contract has a caller (the reference's
         cache-equivalence tests go through it, tests/test_transfusion.py:578-662) - tests/test_decode_contract_gpu.py compares the three."""
         from .sampling import Sampler, _sample_text_token, _ode_solve
+        text_top_k, text_top_p = _check_text_filters(text_top_k, text_top_p)
         was_training = self.training
         self.eval()
         try:
@@ -1816,7 +1842,8 @@ class Transfusion(nn.Module):
                     logits = self.forward([sample], return_loss=False, cache=cache, decode_length=1, decoding_text_or_modality='text',
                                           return_kv_cache=cache_kv, times=torch.ones(1, max(num_past, 1), device=dev))
                     logits, new_cache = logits if cache_kv else (logits, None)
-                    tok = int(_sample_text_token(logits[0, -1:].float().contiguous(), self.md.vocab, text_temperature, text_min_p, stream)[0])
+                    tok = int(_sample_text_token(logits[0, -1:].float().contiguous(), self.md.vocab, text_temperature, text_min_p, stream,
+                                                 text_top_k, text_top_p)[0])
                     sample[-1] = torch.cat((sample[-1], torch.tensor([tok], device=dev)))
                     st.curr_seq = sample[-1].tolist()
                     curr_length += 1
@@ -1889,21 +1916,24 @@ class Transfusion(nn.Module):
         return EMA(self, beta=beta, forward_method_names=('sample', 'sample_one', 'sample_many', 'generate_text_only', 'generate_modality_only'))
 
     @torch.no_grad()
-    def generate_text_only(self, prompt, seq_len, temperature=1.0, min_p=0.1, cache_kv=True):
+    def generate_text_only(self, prompt, seq_len, temperature=1.0, min_p=0.1, cache_kv=True, top_k=None, top_p=None):
         """T:2666-2707.  Returns the generated ids (b, seq_len - prompt_len).  cache_kv=True: the KV-cached decoder (prefill + one-row decode
-        steps); cache_kv=False: the reference's un-cached loop - `forward_text` over the whole sequence for every new token (T:2686-2698)."""
+        steps); cache_kv=False: the reference's un-cached loop - `forward_text` over the whole sequence for every new token (T:2686-2698).
+        `top_k` / `top_p`: as `sample_many`'s `text_top_k` / `text_top_p`; they come after the text-only mask, so they count and weigh text tokens only
+        (min-p stays relative to the maximum over all logits, as in the reference)."""
         from .sampling import Sampler, _pick_text_only
+        top_k, top_p = _check_text_filters(top_k, top_p)
         was_training = self.training
         self.eval()
         try:
             if cache_kv:
-                return Sampler(self).generate_text_only(prompt, seq_len, temperature, min_p)
+                return Sampler(self).generate_text_only(prompt, seq_len, temperature, min_p, top_k, top_p)
             out = prompt.to(self.device)
             stream = self._stream()
             for _ in range(max(seq_len - prompt.shape[-1], 0)):
                 logits = self.forward_text(out, return_loss=False)                         # (b, n, vocabulary)
                 last = logits[:, -1].float().contiguous()
-                tok = _pick_text_only(last, last.shape[-1], self.num_text_tokens, temperature, min_p, stream).to(out.dtype)
+                tok = _pick_text_only(last, last.shape[-1], self.num_text_tokens, temperature, min_p, stream, top_k, top_p).to(out.dtype)
                 out = torch.cat((out, tok.reshape(-1, 1)), dim=-1)
             return out[:, prompt.shape[-1]:]
         finally:
