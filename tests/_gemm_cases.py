@@ -250,7 +250,13 @@ NT_CASES = (
     _nt(1, [(1025, 132, 64, 'BF16', True, None, 0, 1.0, 6), (1151, 264, 192, 'F32', True, None, 0, 1.0, 5), (1151, 132, 192, 'RESID', False, 'rowmap', 0, 1.0, 5)]) +
     _nt(2, [(1151, 264, 256, 'BF16', False, None, 0, 1.0, 5), (1025, 132, 320, 'SILU', True, None, 0, 1.0, 6)]) +
     _nt(5, [(130, 200, 256, 'BF16', True, None, 0, 1.0, 5), (65, 200, 512, 'F32', False, None, 0, 1.0, 6)]) +
-    _nt(4, [(130, 200, 128, 'RESID', True, None, 0, 1.0, 5)]))
+    _nt(4, [(130, 200, 128, 'RESID', True, None, 0, 1.0, 5)]) +
+    # the K rings of the 4-wave LDS-DMA kernels, filled and wrapped (csrc/nt_ring.h).  Skinny, 6 slots: 5 / 6 / 7 / 8 K-tiles = the deepest wait, a prologue that
+    # exactly fills the ring, the first refill, the wrap onto slots 0 and 1 (a2_last: the second source starts in tile 7 = slot 1).  N = 5512: 3 x 87 = 261
+    # tiles of 64 x 64, one more than the decode kernel takes.  Two slots with one refill (2 K-tiles); four slots wrapped and drained (7 K-tiles).
+    _nt(4, [(130, 5512, 320, 'BF16', True), (130, 5512, 384, 'F32'), (130, 5512, 448, 'BF16', False, 'a_rowmap'), (130, 5512, 512, 'BF16', False, 'a2_last')]) +
+    _nt(1, [(1025, 132, 128, 'BF16')]) +
+    _nt(2, [(1151, 264, 448, 'BF16', True)]))
 NT_STAGED_GEGLU = [c for c in NT_CASES if c.epi.startswith('GEGLU')]      # on kind 0 in a child with TFX_GEMM_GLDS=0
 
 # The 256 x 256 family (child process, TFX_NT_PP_MIN=1): one to five K tiles = every entry path of the generated loops; N = 260: the one-wave kernel's direct store.

@@ -61,7 +61,7 @@ def run_group(problems, alpha, beta):
     for i, (a, pr) in enumerate(zip(arr, problems)):
         M, K = pr['P'].shape
         N = pr['Q'].shape[0]
-        Mp, Np, Kp = pad128(M), pad128(N), pad128(K)
+        Mp, Np, Kp = pad128(M), pad128(N), pad128(K) if not pr.get('k64') else -(-K // 64) * 64      # k64: K padded to the kernel's own multiple (tfx.h)
 
         def padded(t, r, c):
             o = torch.zeros(r, c, dtype=BF, device=DEV)
@@ -128,6 +128,9 @@ def test_grouped_products_asymmetric_ragged():
     check_group('update', [dict(P=rn(2730, 512), Q=rn(512, 512), Z=rn(2730, 512), ct=True), dict(P=rn(128, 32), Q=rn(32, 32), Z=rn(128, 32), ct=True),
                            dict(P=rn(1365, 340), Q=rn(340, 340), Z=rn(1365, 340), ct=True, sz=0.61, sa=0.61),
                            dict(P=rn(96, 96), Q=rn(96, 96), Z=rn(96, 96), ct=True)], NS[0], 1.)
+    # the 2-slot K ring: the groups above walk 2, 6, 8, 22 and 44 K-tiles (workspace matrices are padded to 128).  One tile = no refill; three = the
+    # shortest odd walk, which ends on slot 0
+    check_group('ring', [dict(P=rn(96, 64), Q=rn(128, 64), k64=True), dict(P=rn(128, 180), Q=rn(340, 180), k64=True, sa=0.37)], 0., 1.)
 
 
 # ---------------------------------------------------------------------------------------------------------------- 2. orthogonalisation

@@ -11,7 +11,7 @@
 #                                              normalisation, such as those in profiles/tokenwise_row_helpers.txt, were computed on the raw text
 R=$(cd "$(dirname "$0")/.." && pwd)
 T=$(mktemp -d)
-for f in gemm attention tokenwise lora; do
+for f in gemm attention tokenwise lora muon decode; do
   FF=""; [ $f = attention ] && FF="-fno-slp-vectorize"      # build.py FILE_FLAGS
   (cd $R/transfusion_pytorch_amd/csrc && hipcc --offload-arch=gfx950 -O3 -std=c++17 -munsafe-fp-atomics -fPIC $FF -I../../include -c $f.hip -o $T/$f.o -save-temps=obj 2>/dev/null)
 done

@@ -9,6 +9,7 @@
 // (row scatter map) is one lookup per lane.
 #include "tfx_common.h"
 #include "tfx_kernels.h"
+#include "nt_ring.h"
 #include <type_traits>
 #include <cmath>
 #include <cstring>
@@ -1014,10 +1015,6 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(GemmTN p) {
 // swizzle is applied to the SOURCE address (each lane fetches the chunk its LDS slot must hold) and to the
 // read address - same involution on both sides (cdna_hip_programming.md rule 21).
 // ------------------------------------------------------------------------------------------------
-typedef __attribute__((address_space(1))) const void gbl_void_t;
-TFX_DEV void glds16(const bf16* g, bf16* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((gbl_void_t*)g, (lds_void_t*)lds_wave_base, 16, 0, 0);
-}
 
 // Cold-operand prefetch (tfx.h tfx_gemm_nt_args.prefetch): blocks [grid0, gridDim) of a launch touch the next GEMM's weights - one dword per 64 bytes,
 // 64 KiB per block, all of a thread's loads in flight at once - and leave: the lines then sit in the Infinity Cache (memory side: whichever XCD asks).
@@ -1044,204 +1041,22 @@ static int prefetch_blocks(const GemmNT& p) {
   return (int)(n < 512 ? n : 512);
 }
 
-template <int EPI>
-__global__ __launch_bounds__(256, 2) void gemm_nt_glds_kernel(GemmNT p, int grid0) {
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  if (prefetch_block(p, grid0)) return;                           // (block-uniform, before any barrier)
-  bf16* As = (bf16*)smem_raw;                 // [2][128*64], row r chunk c' holds global chunk c' ^ ((r >> 1) & 7): conflict-free for the ds_read_b128 lane groups
-  bf16* Bs = As + 2 * BM * BK;
-
-  const int t = threadIdx.x, l = t & 63, hi = l >> 5;
-  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int wm = w >> 1, wn = w & 1;
-  const int ntn = (p.N + BN - 1) / BN;
-  const int bid = xcd_remap(blockIdx.x, grid0);
-  const int m0 = (bid / ntn) * BM, n0 = (bid % ntn) * BN;
-  const int nk = p.K / BK;
-
-  // wave w stages rows [32w, 32w+32) of both tiles: 4 DMA pieces of 8 rows x 128 B each
-  const bf16 *ga[4], *ga2[4], *gb[4];
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    const int row = w * 32 + j * 8 + (l >> 3);
-    const int c = (l & 7) ^ ((row >> 1) & 7);
-    int rm = min(m0 + row, p.M - 1);
-    if (p.a_rowmap) rm = p.a_rowmap[rm];
-    const int rn = min(n0 + row, p.N - 1);
-    ga[j] = p.A + (size_t)rm * p.lda + c * 8;
-    ga2[j] = p.A2 ? p.A2 + (size_t)rm * p.lda2 + c * 8 : nullptr;
-    gb[j] = p.B + (size_t)rn * p.ldb + c * 8;
-  }
-  auto issue = [&](int kt, int buf) {
-    const int k0 = kt * BK;
-    const bool second = p.A2 && k0 >= p.K1;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      glds16(second ? ga2[j] + (k0 - p.K1) : ga[j] + k0, As + buf * BM * BK + (w * 32 + j * 8) * BK);
-      glds16(gb[j] + k0, Bs + buf * BN * BK + (w * 32 + j * 8) * BK);
-    }
-  };
-
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; i++)
-#pragma unroll
-    for (int j = 0; j < 2; j++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
-
-  issue(0, 0);
-  const int arow0 = wm * 64 + (l & 31), brow0 = wn * 64 + (l & 31);
-  // fragment addresses (bytes folded by the compiler): row r, k-step ks -> chunk (2*ks + hi) ^ ((r >> 1) & 7)
-  auto ldfrag = [&](const bf16* base, int r, int ks) { return *(const bf16x8*)(base + r * BK + (((ks * 2 + hi) ^ ((r >> 1) & 7)) << 3)); };
-  for (int kt = 0; kt < nk; kt++) {
-    const int cur = kt & 1;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this wave's pieces of tile kt have landed
-    __builtin_amdgcn_s_barrier();                            // ... everyone's have, and everyone finished reading the other buffer
-    if (kt + 1 < nk) issue(kt + 1, cur ^ 1);                 // DMA of tile kt+1 overlaps the MFMAs of tile kt
-    const bf16* as = As + cur * BM * BK;
-    const bf16* bs = Bs + cur * BN * BK;
-    bf16x8 af[2][2], bfr[2][2];                              // register double-buffered fragments: reads of k-step ks+1 fly under the MFMAs of ks
-#pragma unroll
-    for (int i = 0; i < 2; i++) { af[0][i] = ldfrag(as, arow0 + i * 32, 0); bfr[0][i] = ldfrag(bs, brow0 + i * 32, 0); }
-#pragma unroll
-    for (int ks = 0; ks < 4; ks++) {
-      const int c = ks & 1;
-      if (ks + 1 < 4) {
-#pragma unroll
-        for (int i = 0; i < 2; i++) { af[c ^ 1][i] = ldfrag(as, arow0 + i * 32, ks + 1); bfr[c ^ 1][i] = ldfrag(bs, brow0 + i * 32, ks + 1); }
-      }
-      __builtin_amdgcn_sched_barrier(0);                     // keep the prefetch ahead of this k-step's MFMAs (distinct registers)
-#pragma unroll
-      for (int i = 0; i < 2; i++)
-#pragma unroll
-        for (int j = 0; j < 2; j++)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bfr[c][j], af[c][i], acc[i][j], 0, 0, 0);
-    }
-  }
-
-  __builtin_amdgcn_s_barrier();                                  // every wave is done with the operand tiles: LDS becomes staging space
-  nt_epilogue<EPI, 2>(p, acc, m0 + wm * 64, n0 + wn * 64, As + w * 8192);   // 16 KiB per wave of the 64 KiB ring
-}
-
-// ------------------------------------------------------------------------------------------------
-// Mid-size NT: at most ONE 128 x 128 tile per CU (mixed decode steps at samples x (modality length + 1) rows, prefills, latent projections,
-// conditioning MLPs).  The 2-stage kernel above is then alone on its CU and every K-tile waits out a full memory round trip (1.4 us per tile
-// measured at M = 640, N = 5504, K = 1024 - 15 % of the MFMA rate).  Same tile, fragments, accumulation order and epilogue, but a 4-slot ring of
-// 32 KiB stages (three K-tiles of LDS-DMA in flight, counted vmcnt: 8 instructions per wave and tile), one block per CU.
-// ------------------------------------------------------------------------------------------------
-constexpr int MD_ST = 4;
-constexpr int MD_STAGE = (BM + BN) * BK;                // elements per ring slot: A [128][64] then B [128][64]
-
-template <int EPI>
-__global__ __launch_bounds__(256, 1) void gemm_nt_mid_kernel(GemmNT p, int grid0) {
+// One block of the 4-wave LDS-DMA kernels: a (64 MI) x 128 tile through nt_ring.h's K loop (ring of ST slots), then nt_epilogue with the ring as its
+// staging space (16 KiB per wave).  Here: which rows a lane fetches - clamped to the matrix, gathered through a_rowmap, A split at K1 into A | A2.
+template <int EPI, int MI, int ST, bool ASM_DMA>
+TFX_DEV void nt_ring_block(const GemmNT& p, int grid0) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   if (prefetch_block(p, grid0)) return;                           // (block-uniform, before any barrier)
   bf16* ring = (bf16*)smem_raw;
-
-  const int t = threadIdx.x, l = t & 63, hi = l >> 5;
-  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int wm = w >> 1, wn = w & 1;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int ntn = (p.N + BN - 1) / BN;
-  const int bid = xcd_remap(blockIdx.x, grid0);
-  const int m0 = (bid / ntn) * BM, n0 = (bid % ntn) * BN;
-  const int nk = p.K / BK;
+  const int bid = MI == 2 ? xcd_remap(blockIdx.x, grid0) : blockIdx.x;
+  const int m0 = (bid / ntn) * 64 * MI, n0 = (bid % ntn) * BN;
 
-  const bf16 *ga[4], *ga2[4], *gb[4];
+  const bf16 *ga[2 * MI], *ga2[2 * MI], *gb[4];
 #pragma unroll
-  for (int j = 0; j < 4; j++) {
-    const int row = w * 32 + j * 8 + (l >> 3);
-    const int c = (l & 7) ^ ((row >> 1) & 7);
-    int rm = min(m0 + row, p.M - 1);
-    if (p.a_rowmap) rm = p.a_rowmap[rm];
-    const int rn = min(n0 + row, p.N - 1);
-    ga[j] = p.A + (size_t)rm * p.lda + c * 8;
-    ga2[j] = p.A2 ? p.A2 + (size_t)rm * p.lda2 + c * 8 : nullptr;
-    gb[j] = p.B + (size_t)rn * p.ldb + c * 8;
-  }
-  auto issue = [&](int kt) {                               // 8 DMA instructions per wave and K-tile
-    const int k0 = kt * BK;
-    bf16* slot = ring + (kt % MD_ST) * MD_STAGE;
-    const bool second = p.A2 && k0 >= p.K1;
-#pragma unroll
-    for (int j = 0; j < 4; j++) glds16_asm(second ? ga2[j] + (k0 - p.K1) : ga[j] + k0, slot + (w * 32 + j * 8) * BK);
-#pragma unroll
-    for (int j = 0; j < 4; j++) glds16_asm(gb[j] + k0, slot + BM * BK + (w * 32 + j * 8) * BK);
-  };
-
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; i++)
-#pragma unroll
-    for (int j = 0; j < 2; j++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
-
-  for (int kt = 0; kt < min(MD_ST - 1, nk); kt++) issue(kt);
-  const int arow0 = wm * 64 + (l & 31), brow0 = wn * 64 + (l & 31);
-  auto ldfrag = [&](const bf16* base, int r, int ks) { return *(const bf16x8*)(base + r * BK + (((ks * 2 + hi) ^ ((r >> 1) & 7)) << 3)); };
-  for (int kt = 0; kt < nk; kt++) {
-    const int ahead = min(MD_ST - 2, nk - 1 - kt);           // K-tiles after kt that may still be in flight (in-order counter)
-    switch (ahead) {
-      case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-      case 1: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-      default: asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); break;
-    }
-    __builtin_amdgcn_s_barrier();                            // tile kt has landed for everyone, and everyone finished reading slot (kt - 1) % MD_ST
-    if (kt + MD_ST - 1 < nk) issue(kt + MD_ST - 1);          // refill the slot read in the previous iteration
-    const bf16* as = ring + (kt % MD_ST) * MD_STAGE;
-    const bf16* bs = as + BM * BK;
-    bf16x8 af[2][2], bfr[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; i++) { af[0][i] = ldfrag(as, arow0 + i * 32, 0); bfr[0][i] = ldfrag(bs, brow0 + i * 32, 0); }
-#pragma unroll
-    for (int ks = 0; ks < 4; ks++) {
-      const int c = ks & 1;
-      if (ks + 1 < 4) {
-#pragma unroll
-        for (int i = 0; i < 2; i++) { af[c ^ 1][i] = ldfrag(as, arow0 + i * 32, ks + 1); bfr[c ^ 1][i] = ldfrag(bs, brow0 + i * 32, ks + 1); }
-      }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int i = 0; i < 2; i++)
-#pragma unroll
-        for (int j = 0; j < 2; j++)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bfr[c][j], af[c][i], acc[i][j], 0, 0, 0);
-    }
-  }
-
-  __builtin_amdgcn_s_barrier();                                  // the ring becomes staging space: 16 KiB per wave
-  nt_epilogue<EPI, 2>(p, acc, m0 + wm * 64, n0 + wn * 64, ring + w * 8192);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Skinny NT (decode steps, time-conditioning MLPs: M <= 512 rows).  With a handful of 64-row blocks the 2-stage kernel
-// above is pure latency: every K-tile waits one full memory round trip (12.9 us for M = 64, K = 512).  Here a block owns a
-// 64 x 128 tile and keeps SK_ST - 1 K-tiles of LDS-DMA in flight (a 6-slot ring of 24 KiB stages = the whole K = 512 panel
-// is requested up front), one wave per 32 x 64 sub-tile, same LDS layout / fragments / epilogues as the kernel above.
-// ------------------------------------------------------------------------------------------------
-constexpr int SK_BM = 64, SK_BN = 128, SK_ST = 6;
-constexpr int SK_STAGE = (SK_BM + SK_BN) * BK;          // elements per ring slot: A [64][64] then B [128][64]
-
-template <int EPI>
-__global__ __launch_bounds__(256, 1) void gemm_nt_skinny_kernel(GemmNT p, int grid0) {
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  if (prefetch_block(p, grid0)) return;                           // (block-uniform, before any barrier)
-  bf16* ring = (bf16*)smem_raw;
-
-  const int t = threadIdx.x, l = t & 63, hi = l >> 5;
-  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int wm = w >> 1, wn = w & 1;
-  const int ntn = (p.N + SK_BN - 1) / SK_BN;
-  const int m0 = (blockIdx.x / ntn) * SK_BM, n0 = (blockIdx.x % ntn) * SK_BN;
-  const int nk = p.K / BK;
-
-  // wave w stages rows [16w, 16w+16) of the A slot (2 DMA pieces of 8 rows x 128 B) and rows [32w, 32w+32) of the B slot (4 pieces)
-  const bf16 *ga[2], *ga2[2], *gb[4];
-#pragma unroll
-  for (int j = 0; j < 2; j++) {
-    const int row = w * 16 + j * 8 + (l >> 3);
-    const int c = (l & 7) ^ ((row >> 1) & 7);
+  for (int j = 0; j < 2 * MI; j++) {
+    const int row = ring_src_row(w, j, 16 * MI), c = ring_src_chunk(row);
     int rm = min(m0 + row, p.M - 1);
     if (p.a_rowmap) rm = p.a_rowmap[rm];
     ga[j] = p.A + (size_t)rm * p.lda + c * 8;
@@ -1249,58 +1064,33 @@ __global__ __launch_bounds__(256, 1) void gemm_nt_skinny_kernel(GemmNT p, int gr
   }
 #pragma unroll
   for (int j = 0; j < 4; j++) {
-    const int row = w * 32 + j * 8 + (l >> 3);
-    const int c = (l & 7) ^ ((row >> 1) & 7);
+    const int row = ring_src_row(w, j, 32), c = ring_src_chunk(row);
     gb[j] = p.B + (size_t)min(n0 + row, p.N - 1) * p.ldb + c * 8;
   }
-  auto issue = [&](int kt) {                               // 6 DMA instructions per wave and K-tile
-    const int k0 = kt * BK;
-    bf16* slot = ring + (kt % SK_ST) * SK_STAGE;
-    const bool second = p.A2 && k0 >= p.K1;
-#pragma unroll
-    for (int j = 0; j < 2; j++) glds16_asm(second ? ga2[j] + (k0 - p.K1) : ga[j] + k0, slot + (w * 16 + j * 8) * BK);
-#pragma unroll
-    for (int j = 0; j < 4; j++) glds16_asm(gb[j] + k0, slot + SK_BM * BK + (w * 32 + j * 8) * BK);
-  };
-
-  f32x16 acc[1][2];
-#pragma unroll
-  for (int j = 0; j < 2; j++)
-#pragma unroll
-    for (int r = 0; r < 16; r++) acc[0][j][r] = 0.f;
-
-  for (int kt = 0; kt < min(SK_ST - 1, nk); kt++) issue(kt);
-  const int arow = wm * 32 + (l & 31), brow0 = wn * 64 + (l & 31);
-  auto ldfrag = [&](const bf16* base, int r, int ks) { return *(const bf16x8*)(base + r * BK + (((ks * 2 + hi) ^ ((r >> 1) & 7)) << 3)); };
-  for (int kt = 0; kt < nk; kt++) {
-    // K-tiles kt+1 .. kt+ahead of this wave are still allowed in flight (6 instructions each, in-order counter)
-    const int ahead = min(SK_ST - 2, nk - 1 - kt);
-    switch (ahead) {
-      case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-      case 1: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-      case 2: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-      case 3: asm volatile("s_waitcnt vmcnt(18)" ::: "memory"); break;
-      default: asm volatile("s_waitcnt vmcnt(24)" ::: "memory"); break;
-    }
-    __builtin_amdgcn_s_barrier();                            // tile kt has landed for everyone, and everyone finished reading slot (kt - 1) % SK_ST
-    if (kt + SK_ST - 1 < nk) issue(kt + SK_ST - 1);          // refill the slot read in the previous iteration
-    const bf16* as = ring + (kt % SK_ST) * SK_STAGE;
-    const bf16* bs = as + SK_BM * BK;
-#pragma unroll
-    for (int ks = 0; ks < 4; ks++) {
-      const bf16x8 af = ldfrag(as, arow, ks);
-#pragma unroll
-      for (int j = 0; j < 2; j++)
-        acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ldfrag(bs, brow0 + j * 32, ks), af, acc[0][j], 0, 0, 0);
-    }
-  }
-
-  __builtin_amdgcn_s_barrier();                                  // the ring becomes staging space: 16 KiB per wave
-  nt_epilogue<EPI, 1>(p, acc, m0 + wm * 32, n0 + wn * 64, ring + w * 8192);
+  f32x16 acc[MI][2];
+  nt_ring_loop<MI, ST, ASM_DMA>(ring, p.K / BK, acc,
+                                [&](int j, int k0) { const bool second = p.A2 && k0 >= p.K1; return (second ? ga2[j] : ga[j]) + (second ? k0 - p.K1 : k0); },
+                                [&](int j, int k0) { return gb[j] + k0; });
+  __builtin_amdgcn_s_barrier();                                   // every wave is done with the operand tiles: the ring becomes staging space
+  nt_epilogue<EPI, MI>(p, acc, m0 + (w >> 1) * 32 * MI, n0 + (w & 1) * 64, ring + w * 8192);
 }
 
+// The three forms (nt_plan chooses).  Same fragments, accumulation order and epilogue; what differs is how many K-tiles of DMA a block keeps in flight:
+//   glds    2 slots of 32 KiB, two blocks per CU, the builtin DMA: the throughput form
+//   mid     at most ONE 128 x 128 tile per CU (mixed decode steps at samples x (modality length + 1) rows, prefills, latent projections, conditioning
+//           MLPs): the 2-slot form is then alone on its CU and every K-tile waits out a full memory round trip (1.4 us per tile measured at M = 640,
+//           N = 5504, K = 1024 - 15 % of the MFMA rate).  4 slots, three K-tiles in flight, one block per CU
+//   skinny  M <= 512 rows (decode steps, time-conditioning MLPs): with a handful of 64-row blocks the 2-slot form is pure latency (12.9 us for M = 64,
+//           K = 512).  A 64 x 128 tile, one wave per 32 x 64 sub-tile, 6 slots of 24 KiB = the whole K = 512 panel is requested up front
+constexpr int GL_ST = 2, MD_ST = 4, SK_ST = 6;
+constexpr int SK_BM = 64, SK_BN = BN;
+static_assert(BN == RING_BN && BK == RING_BK && BM == 2 * SK_BM, "nt_ring.h's tile");
+template <int EPI> __global__ __launch_bounds__(256, 2) void gemm_nt_glds_kernel(GemmNT p, int grid0) { nt_ring_block<EPI, 2, GL_ST, false>(p, grid0); }
+template <int EPI> __global__ __launch_bounds__(256, 1) void gemm_nt_mid_kernel(GemmNT p, int grid0) { nt_ring_block<EPI, 2, MD_ST, true>(p, grid0); }
+template <int EPI> __global__ __launch_bounds__(256, 1) void gemm_nt_skinny_kernel(GemmNT p, int grid0) { nt_ring_block<EPI, 1, SK_ST, true>(p, grid0); }
+
 // Decode-step form of the skinny kernel.  At M = 64 ... 256 rows the weights are what is streamed, a launch has a handful of tiles, and its time is
-// ONE block's walk over K: ~0.36 us per 64-wide K-tile in the kernel above whatever the ring depth or tile width (measured: 5 or 8 tiles in flight,
+// ONE block's walk over K: ~0.36 us per 64-wide K-tile in the skinny form above whatever the ring depth or tile width (measured: 5 or 8 tiles in flight,
 // 64 x 128 or 64 x 64 tiles - the same 23 us at K = 2752) - a wave's barrier -> fragment reads -> four dependent MFMAs per accumulator is a serial
 // chain with nothing to overlap it.  So K is split ACROSS THE FOUR WAVES of a block: a 64 x 64 output tile, wave w walks K quarter w in 32-wide
 // slabs through its OWN 4-slot LDS-DMA ring (8 KiB slots, three slabs in flight, no barrier in the loop - the ring is private), and the four
@@ -2355,36 +2145,24 @@ template <int EPI> static void launch_ow(const GemmNT& p, int grid, hipStream_t 
   ensure_smem_attr((const void*)gemm_nt_ow_kernel<EPI>, 2 * (BM2 * BK + BN2 * BK) * 2 + GTAB_N * 8, attr_ow);
   hipLaunchKernelGGL(gemm_nt_ow_kernel<EPI>, dim3(grid), dim3(256), smem, s, p, PP_STAGGER, gtab);
 }
+// a launch of the LDS-DMA kernels with prefetch blocks: the product's `grid` blocks, then the blocks that touch the next product's weights
+template <void (*KERNEL)(GemmNT, int)> static void launch_dma(int lds_bytes, const GemmNT& p, int grid, hipStream_t s) {
+  static uint32_t attr = 0;                                       // (one per kernel)
+  ensure_smem_attr((const void*)KERNEL, lds_bytes, attr);
+  hipLaunchKernelGGL(KERNEL, dim3(grid + prefetch_blocks(p)), dim3(256), lds_bytes, s, p, grid);
+}
+constexpr int SD_BYTES = 4 * SD_ST * SD_SLOT * 2;                 // the decode kernel's four private rings
 template <int EPI> static int launch_nt(const GemmNT& p, hipStream_t s) {
   const NtPlan pl = nt_plan(p);
-  const int smem = 2 * (BM * BK + BN * BK) * 2;
   switch (pl.kind) {
-    case NT_DECODE: {
-      static uint32_t attr_sd = 0;
-      const int smem_sd = 4 * SD_ST * SD_SLOT * 2;
-      ensure_smem_attr((const void*)gemm_nt_decode_kernel<EPI>, smem_sd, attr_sd);
-      hipLaunchKernelGGL(gemm_nt_decode_kernel<EPI>, dim3(pl.grid + prefetch_blocks(p)), dim3(256), smem_sd, s, p, pl.grid);
-      break;
-    }
-    case NT_SKINNY: {
-      static uint32_t attr_sk = 0;
-      const int smem_sk = SK_ST * SK_STAGE * 2;
-      ensure_smem_attr((const void*)gemm_nt_skinny_kernel<EPI>, smem_sk, attr_sk);
-      hipLaunchKernelGGL(gemm_nt_skinny_kernel<EPI>, dim3(pl.grid + prefetch_blocks(p)), dim3(256), smem_sk, s, p, pl.grid);
-      break;
-    }
+    case NT_DECODE: launch_dma<gemm_nt_decode_kernel<EPI>>(SD_BYTES, p, pl.grid, s); break;
+    case NT_SKINNY: launch_dma<gemm_nt_skinny_kernel<EPI>>(ring_bytes<1, SK_ST>, p, pl.grid, s); break;
     case NT_PP: launch_pp<EPI>(p, pl.grid, s); break;
     case NT_OW: if constexpr (EPI == EPI_BF16 || EPI == EPI_F32) launch_ow<EPI>(p, pl.grid, s); break;        // (nt_ow_takes: these two epilogues only)
     case NT_OWP: if constexpr (EPI == EPI_BF16) launch_owp<EPI>(p, pl.grid, s); break;
-    case NT_MID: {
-      static uint32_t attr_md = 0;
-      const int smem_md = MD_ST * MD_STAGE * 2;
-      ensure_smem_attr((const void*)gemm_nt_mid_kernel<EPI>, smem_md, attr_md);
-      hipLaunchKernelGGL(gemm_nt_mid_kernel<EPI>, dim3(pl.grid + prefetch_blocks(p)), dim3(256), smem_md, s, p, pl.grid);
-      break;
-    }
-    case NT_GLDS: hipLaunchKernelGGL(gemm_nt_glds_kernel<EPI>, dim3(pl.grid + prefetch_blocks(p)), dim3(256), smem, s, p, pl.grid); break;
-    default: hipLaunchKernelGGL(gemm_nt_kernel<EPI>, dim3(pl.grid), dim3(256), smem, s, p); break;
+    case NT_MID: launch_dma<gemm_nt_mid_kernel<EPI>>(ring_bytes<2, MD_ST>, p, pl.grid, s); break;
+    case NT_GLDS: launch_dma<gemm_nt_glds_kernel<EPI>>(ring_bytes<2, GL_ST>, p, pl.grid, s); break;
+    default: hipLaunchKernelGGL(gemm_nt_kernel<EPI>, dim3(pl.grid), dim3(256), 2 * (BM * BK + BN * BK) * 2, s, p); break;
   }
   return (int)hipGetLastError();
 }
@@ -2410,11 +2188,8 @@ static int gemm_nt_qknr(const GemmNT& p, hipStream_t s) {
   if (p.qk_heads <= 0 || !p.C2 || !p.qk_gamma_q != !p.qk_gamma_k || !p.qk_rot_pos || !p.qk_cos || !p.qk_sin) return -5;      // (both gains or neither: tfx.h)
   if (qknr_fusable(p)) {
     const NtPlan pl = nt_plan(p);
-    if (pl.kind == NT_PP) { launch_pp<EPI_QKNR>(p, pl.grid, s); return (int)hipGetLastError(); }
-    static uint32_t attr_sd = 0;
-    const int smem_sd = 4 * SD_ST * SD_SLOT * 2;
-    ensure_smem_attr((const void*)gemm_nt_decode_kernel<EPI_QKNR>, smem_sd, attr_sd);
-    hipLaunchKernelGGL(gemm_nt_decode_kernel<EPI_QKNR>, dim3(pl.grid + prefetch_blocks(p)), dim3(256), smem_sd, s, p, pl.grid);
+    if (pl.kind == NT_PP) launch_pp<EPI_QKNR>(p, pl.grid, s);
+    else launch_dma<gemm_nt_decode_kernel<EPI_QKNR>>(SD_BYTES, p, pl.grid, s);
     return (int)hipGetLastError();
   }
   GemmNT q = p; q.epi = EPI_BF16; q.C2 = nullptr;
@@ -2449,6 +2224,12 @@ template <bool SUM, int FA, int FB, int WN, int WK, int NST> static void launch_
   static uint32_t attr = 0;
   ensure_smem_attr((const void*)gemm_tn_wide_kernel<SUM, FA, FB, WN, WK, NST>, smem, attr);
   hipLaunchKernelGGL((gemm_tn_wide_kernel<SUM, FA, FB, WN, WK, NST>), dim3(grid), dim3(64 * WN * WK), smem, s, q);
+}
+// a launch of the one-wave-per-SIMD TN kernels (plain, group, table): 128 KiB of LDS
+template <auto KERNEL, class... Args> static void launch_tn_ow(int grid, hipStream_t s, const Args&... a) {
+  static uint32_t attr = 0;                                       // (one per kernel)
+  ensure_smem_attr((const void*)KERNEL, 131072, attr);
+  hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(256), 131072, s, a...);
 }
 
 // what gemm_tn launches for a shape: kernel form (-1 register-staged fallback, 0 = 128 x 128 / 4 waves, 2 = 256 x 256 / 8 waves), output tiles,
@@ -2603,9 +2384,8 @@ int gemm_tn(const GemmTN& p, hipStream_t s) {
     if (tp.ok) {
       const uint32_t* recs = (const uint32_t*)p.table;
       const int* tile_end = (const int*)((const GemmTN*)p.table + p.table_count);
-      static uint32_t attr_t0 = 0, attr_t1 = 0;
-      if (tp.sum) { ensure_smem_attr((const void*)gemm_tn_ow_table_kernel<true>, 131072, attr_t1); hipLaunchKernelGGL(gemm_tn_ow_table_kernel<true>, dim3(tp.grid), dim3(256), 131072, s, recs, tile_end, p.table_count, p.M, tp.splits); }
-      else { ensure_smem_attr((const void*)gemm_tn_ow_table_kernel<false>, 131072, attr_t0); hipLaunchKernelGGL(gemm_tn_ow_table_kernel<false>, dim3(tp.grid), dim3(256), 131072, s, recs, tile_end, p.table_count, p.M, tp.splits); }
+      if (tp.sum) launch_tn_ow<gemm_tn_ow_table_kernel<true>>(tp.grid, s, recs, tile_end, p.table_count, p.M, tp.splits);
+      else launch_tn_ow<gemm_tn_ow_table_kernel<false>>(tp.grid, s, recs, tile_end, p.table_count, p.M, tp.splits);
       return (int)hipGetLastError();
     }
     for (int i = 0; i < p.table_count; i++) {                            // a member the one-wave kernel does not take: the records one by one
@@ -2621,9 +2401,8 @@ int gemm_tn(const GemmTN& p, hipStream_t s) {
       bool sum = false;
       for (int i = 0; i < gp.count; i++) sum = sum || gp.g.p[i].colsum != nullptr;
       const int ramp = tn_ramp(p.M, gp.tiles, gp.splits);
-      static uint32_t attr_g0 = 0, attr_g1 = 0;
-      if (sum) { ensure_smem_attr((const void*)gemm_tn_ow_group_kernel<true>, 131072, attr_g1); hipLaunchKernelGGL(gemm_tn_ow_group_kernel<true>, dim3(gp.grid), dim3(256), 131072, s, gp.g, ramp); }
-      else { ensure_smem_attr((const void*)gemm_tn_ow_group_kernel<false>, 131072, attr_g0); hipLaunchKernelGGL(gemm_tn_ow_group_kernel<false>, dim3(gp.grid), dim3(256), 131072, s, gp.g, ramp); }
+      if (sum) launch_tn_ow<gemm_tn_ow_group_kernel<true>>(gp.grid, s, gp.g, ramp);
+      else launch_tn_ow<gemm_tn_ow_group_kernel<false>>(gp.grid, s, gp.g, ramp);
       return (int)hipGetLastError();
     }
     int guard = 0;
@@ -2643,20 +2422,13 @@ int gemm_tn(const GemmTN& p, hipStream_t s) {
   q.splits = pl.splits;
   const int kind = pl.kind, grid = pl.grid;
   if (kind == 3) {
-    static uint32_t attr_tnow = 0;
     // ramp (tn_block_ramp): the finish times of the chunks should spread over about the time the launch's atomics take, tiles x chunks x 0.2 us (256 KiB at
     // 1.25 TB/s), i.e. d = 0.2 us x tiles / (a step's 1.35 us) steps of 64 rows per chunk index.  Measured
     // (gpurun_out/ow31.txt, steady state): -3.5 ... -7.8 % on the 11-20-chunk launches of config 2 at factor 1, worse at 0.5 / 1.5 / 2, nothing to +1 % on the
     // 2-5-chunk launches - so from 8 chunks on
     const int ramp = tn_ramp(q.M, pl.tiles, q.splits);
-    if (q.colsum) {
-      static uint32_t attr_tnows = 0;
-      ensure_smem_attr((const void*)gemm_tn_ow_kernel<true>, 131072, attr_tnows);
-      hipLaunchKernelGGL(gemm_tn_ow_kernel<true>, dim3(grid), dim3(256), 131072, s, q, ramp);
-    } else {
-      ensure_smem_attr((const void*)gemm_tn_ow_kernel<false>, 131072, attr_tnow);
-      hipLaunchKernelGGL(gemm_tn_ow_kernel<false>, dim3(grid), dim3(256), 131072, s, q, ramp);
-    }
+    if (q.colsum) launch_tn_ow<gemm_tn_ow_kernel<true>>(grid, s, q, ramp);
+    else launch_tn_ow<gemm_tn_ow_kernel<false>>(grid, s, q, ramp);
   } else if (kind == 2) {
     if (q.colsum) launch_tn_wide<true, 2, 4, 4, 2, 4>(q, grid, s);
     else launch_tn_wide<false, 2, 4, 4, 2, 4>(q, grid, s);

@@ -15,18 +15,14 @@
 // all-reduced gradient redundantly and must stay identical).
 #include "tfx_common.h"
 #include "tfx_kernels.h"
+#include "nt_ring.h"
 #include <cmath>
 
 namespace {
 
-constexpr int BM = 128, BN = 128, BK = 64;
+constexpr int BM = 128, BN = RING_BN, BK = RING_BK;
 constexpr int PB = 64;                        // prep / apply walk the fp32 matrices in 64 x 64 blocks
 constexpr int SUMSQ_DET_BLOCKS = TFX_SUMSQ_DET_PARTIALS;
-
-typedef __attribute__((address_space(1))) const void gbl_void_t;
-TFX_DEV void glds16(const bf16* g, bf16* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((gbl_void_t*)g, (lds_void_t*)lds_wave_base, 16, 0, 0);
-}
 
 // sum of a block's 256 per-thread values in a fixed order: DPP wave sums, then the 4 wave totals front to back (every thread gets the total)
 TFX_DEV float block_sum256(float s, float* sacc) {
@@ -40,78 +36,30 @@ TFX_DEV float block_sum256(float s, float* sacc) {
 
 // ------------------------------------------------------------------------------------------------
 // grouped NT product: C = alpha sz Z + beta sa P . Q^T over a problem table; tile 128 x 128, 4 waves (2 x 2) of 64 x 64 = 2 x 2
-// v_mfma_f32_32x32x16_bf16, operands staged by LDS-DMA into a 2-slot ring (gemm_nt_glds_kernel's pipeline and swizzle: row r, 16-byte chunk c'
-// holds global chunk c' ^ ((r >> 1) & 7)).  Operands are multiplied swapped, so a lane owns one output row and runs of 4 columns.
+// v_mfma_f32_32x32x16_bf16, operands staged by LDS-DMA into a 2-slot ring: nt_ring.h's K loop, as gemm.hip's glds form runs it, on operands that
+// need no clamp.  Operands are multiplied swapped, so a lane owns one output row and runs of 4 columns.
 // ------------------------------------------------------------------------------------------------
+constexpr int GEMM_ST = 2;
 __global__ __launch_bounds__(256, 2) void muon_gemm_kernel(const tfx_muon_gemm_problem* tab, const int32_t* tile_prob, int ntiles, float alpha, float beta) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  bf16* As = (bf16*)smem_raw;                 // [2][128 * 64]
-  bf16* Bs = As + 2 * BM * BK;
-
-  const int t = threadIdx.x, l = t & 63, hi = l >> 5;
-  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int l = threadIdx.x & 63, hi = l >> 5;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wm = w >> 1, wn = w & 1;
   const int bid = xcd_remap(blockIdx.x, ntiles);
   const tfx_muon_gemm_problem p = tab[tile_prob[bid]];
   const int lt = bid - p.tile0;
   const int ntn = p.N / BN;
   const int m0 = (lt / ntn) * BM, n0 = (lt % ntn) * BN;
-  const int nk = p.K / BK;
 
-  // wave w stages rows [32w, 32w + 32) of both tiles: 4 DMA pieces of 8 rows x 128 B each
   const bf16 *ga[4], *gb[4];
 #pragma unroll
   for (int j = 0; j < 4; j++) {
-    const int row = w * 32 + j * 8 + (l >> 3);
-    const int c = (l & 7) ^ ((row >> 1) & 7);
+    const int row = ring_src_row(w, j, 32), c = ring_src_chunk(row);
     ga[j] = p.P + (size_t)(m0 + row) * p.ldp + c * 8;
     gb[j] = p.Q + (size_t)(n0 + row) * p.ldq + c * 8;
   }
-  auto issue = [&](int kt, int buf) {
-    const int k0 = kt * BK;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      glds16(ga[j] + k0, As + buf * BM * BK + (w * 32 + j * 8) * BK);
-      glds16(gb[j] + k0, Bs + buf * BN * BK + (w * 32 + j * 8) * BK);
-    }
-  };
-
   f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; i++)
-#pragma unroll
-    for (int j = 0; j < 2; j++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
-
-  issue(0, 0);
-  const int arow0 = wm * 64 + (l & 31), brow0 = wn * 64 + (l & 31);
-  auto ldfrag = [&](const bf16* base, int r, int ks) { return *(const bf16x8*)(base + r * BK + (((ks * 2 + hi) ^ ((r >> 1) & 7)) << 3)); };
-  for (int kt = 0; kt < nk; kt++) {
-    const int cur = kt & 1;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this wave's pieces of tile kt have landed
-    __builtin_amdgcn_s_barrier();                            // ... everyone's have, and everyone finished reading the other buffer
-    if (kt + 1 < nk) issue(kt + 1, cur ^ 1);                 // DMA of tile kt + 1 overlaps the MFMAs of tile kt
-    const bf16* as = As + cur * BM * BK;
-    const bf16* bs = Bs + cur * BN * BK;
-    bf16x8 af[2][2], bfr[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; i++) { af[0][i] = ldfrag(as, arow0 + i * 32, 0); bfr[0][i] = ldfrag(bs, brow0 + i * 32, 0); }
-#pragma unroll
-    for (int ks = 0; ks < 4; ks++) {
-      const int c = ks & 1;
-      if (ks + 1 < 4) {
-#pragma unroll
-        for (int i = 0; i < 2; i++) { af[c ^ 1][i] = ldfrag(as, arow0 + i * 32, ks + 1); bfr[c ^ 1][i] = ldfrag(bs, brow0 + i * 32, ks + 1); }
-      }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int i = 0; i < 2; i++)
-#pragma unroll
-        for (int j = 0; j < 2; j++)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bfr[c][j], af[c][i], acc[i][j], 0, 0, 0);
-    }
-  }
+  nt_ring_loop<2, GEMM_ST, false>((bf16*)smem_raw, p.K / BK, acc, [&](int j, int k0) { return ga[j] + k0; }, [&](int j, int k0) { return gb[j] + k0; });
 
   // epilogue: accumulator register 4 g + e of acc[i][j] is row m_w + 32 i + (l & 31), column n_w + 32 j + 8 g + 4 hi + e
   const float sz = alpha * (p.scale_z ? *p.scale_z : 1.f), sa = beta * (p.scale_acc ? *p.scale_acc : 1.f);
@@ -287,7 +235,7 @@ int tfx_muon_step_launches(int32_t ns_steps, int32_t nmat) {
 int tfx_muon_gemm(const tfx_muon_gemm_problem* table, const int32_t* tile_prob, int32_t ntiles, float alpha, float beta, void* s) {
   if (ntiles == 0) return 0;
   if (!table || !tile_prob || ntiles < 0) return -1;
-  const int smem = 2 * (BM * BK + BN * BK) * 2;
+  const int smem = ring_bytes<2, GEMM_ST>;
   static uint32_t attr = 0;
   ensure_smem_attr((const void*)muon_gemm_kernel, smem, attr);
   hipLaunchKernelGGL(muon_gemm_kernel, dim3((unsigned)ntiles), dim3(256), smem, ST(s), table, tile_prob, (int)ntiles, alpha, beta); RET();

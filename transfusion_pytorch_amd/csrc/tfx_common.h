@@ -186,6 +186,11 @@ TFX_DEV void glds16_asm(const bf16* g, const bf16* lds_wave_base) {
   const unsigned lds_addr = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_void_t*)lds_wave_base);
   asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(lds_addr) : "memory");
 }
+// the same DMA as the builtin, which hipcc does count (and drains with vmcnt(0) before the next barrier or LDS read)
+typedef __attribute__((address_space(1))) const void gbl_void_t;
+TFX_DEV void glds16(const bf16* g, bf16* lds_wave_base) {
+  __builtin_amdgcn_global_load_lds((gbl_void_t*)g, (lds_void_t*)lds_wave_base, 16, 0, 0);
+}
 
 // Phi(g) = 0.5 (1 + erf(g / sqrt 2)) from the exponential the GELU derivative needs anyway: erf(x) = 1 - poly(t) exp(-x^2),
 // t = 1 / (1 + 0.3275911 x), x >= 0 (Abramowitz-Stegun 7.1.26, |error| <= 1.5e-7) - with x = |g| / sqrt 2 the exponential is
