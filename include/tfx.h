@@ -580,6 +580,26 @@ int tfx_ode_rk_stage(const float* y, const float* k, const float* ctl, int32_t B
                      const int32_t* rows0, void* stream);
 int tfx_ode_rk_update(float* y, float* k, const float* ctl, int32_t B, int32_t Lc, int32_t dmax, const float* pred, int32_t H, int32_t Lq, int32_t dl,
                       float cfg_scale, const float* sel, const int32_t* rows0, void* stream);
+/* Adams-Bashforth multistep rules on the same grid (ode.py: ab2 / ab3 / ab4 = order P): the first P - 1 steps are steps of a tableau rule above whose
+ * stage-0 derivative is also kept in a ring of TFX_ODE_AB_HIST slots; every later step is ONE evaluation g = guided derivative at (t_n, y_n) and
+ *   acc = y;  [state machine: the k terms j < q ascending, as above;]  for j = 0, 1, 2 in table order: if (w_j != 0) acc = fmaf(w_j, h_j, acc);
+ *   new state = fmaf(w_g, g, acc);  g -> its slot
+ * A history term whose weight is exactly 0 is skipped and its slot is NOT read.  Every read of an element comes before its writes, so the slot that
+ * receives g may be one of the slots read (ab4: g_n replaces g_{n-3}).
+ *
+ * tfx_ode_ab_axpy - the dense form (n elements): h_j may be NULL when w_j == 0; g -> g_out (optional, may alias one h_j), the new state -> out.
+ *   Returns 0 without a launch when n <= 0, -1 (y / f_cond / out missing), -3 (a nonzero w_j with h_j NULL).
+ * tfx_ode_ab_update - tfx_ode_rk_update with the ring: hist fp32 [3][B][Lc][dmax]; ctl fp32 [16][B], rows 0..8 as tfx_ode_rk_update reads them,
+ *     ctl[9] the slot that receives g (negative = none)   ctl[10..12] the slots read   ctl[13..15] their weights
+ *   modes 1 and 2 with ctl[9] >= 0: g is also written to hist[slot];  mode 2: the history terms join the update as above.  Everything else - sel,
+ *   rows0, H, columns >= dl, modes 0 and 3, the stage index clamp - as tfx_ode_rk_update; slot indices are clamped to [0, 2] likewise (the table
+ *   lives on the device).  With ctl[9] negative and three zero weights the results are tfx_ode_rk_update's bits and hist is not touched.
+ *   The inputs are staged by tfx_ode_rk_stage from rows 0..4 of the same block: a multistep evaluation is mode 2 at stage 0, its input y. */
+enum { TFX_ODE_AB_HIST = 3 };
+int tfx_ode_ab_axpy(const float* y, const float* h0, const float* h1, const float* h2, float w0, float w1, float w2, float wg, const float* f_cond,
+                    const float* f_uncond, float cfg_scale, float* g_out, float* out, int64_t n, void* stream);
+int tfx_ode_ab_update(float* y, float* k, float* hist, const float* ctl, int32_t B, int32_t Lc, int32_t dmax, const float* pred, int32_t H, int32_t Lq,
+                      int32_t dl, float cfg_scale, const float* sel, const int32_t* rows0, void* stream);
 
 /* ---- parameter plumbing ---------------------------------------------------------------------- */
 /* dst[r][c] (bf16, ld_dst, Rd rows, Cd cols) = src[rowmap ? rowmap[r] : r][c] or 0 when out of range / map < 0 */

@@ -1,5 +1,6 @@
 """Throughput of the KV-cached decode twin (sample_many / generate_text_only) on one GPU: tokens per second, host-bound or not.
    python tools/bench_sample.py [--dim 512 --depth 8 --batch 64 --new 64] [--ode-method euler --modality-steps 31]
+   python tools/bench_sample.py --config5 --ode-method ab4 --modality-steps 16    # a multistep rule: 24 forwards per modality against midpoint's 30
    python tools/bench_sample.py --config5 --ode-method rk4 --modality-steps 9      # sample_many alone, at the configuration `bench.py --sample` times
    python tools/bench_sample.py --config5 --temperature 1 --top-k 40 --top-p 0.9   # the text draw behind the top-k / top-p filters (a temperature: greedy ignores them)"""
 import argparse, os, sys, time
@@ -10,8 +11,8 @@ from transfusion_pytorch_amd import Transfusion
 ap = argparse.ArgumentParser()
 ap.add_argument('--dim', type=int, default=512); ap.add_argument('--depth', type=int, default=8)
 ap.add_argument('--batch', type=int, default=64); ap.add_argument('--new', type=int, default=64); ap.add_argument('--prompt', type=int, default=128)
-ap.add_argument('--ode-method', default='midpoint', help='fixed-grid solver of the modality phases: euler, midpoint, heun2, heun3, rk4 (ode.py)')
-ap.add_argument('--modality-steps', type=int, default=8, help='grid points of the solver: stages x (modality-steps - 1) forwards per modality')
+ap.add_argument('--ode-method', default='midpoint', help='fixed-grid solver of the modality phases: euler, midpoint, heun2, heun3, rk4, or a multistep rule ab2, ab3, ab4 (ode.py)')
+ap.add_argument('--modality-steps', type=int, default=8, help='grid points of the solver: stages x (modality-steps - 1) forwards per modality (ab2 / ab3 / ab4: one per step after the start-up steps)')
 ap.add_argument('--config5', action='store_true', help='time sample_many alone at SURVEY 8(d) config 5 (dim 1024, depth 24, 64 mixed prompts, '
                 'max_length 256, cfg 3, greedy text, a forced modality at the start), as `bench.py --sample` does for midpoint with 16 grid points')
 ap.add_argument('--top-k', type=int, default=None, help='top-k filter of the text draw (tfx_sample_tokens_filtered); needs a temperature')
@@ -24,7 +25,7 @@ if (a.top_k or (a.top_p is not None and a.top_p < 1.)) and temp == 0.:
 torch.manual_seed(0)
 okw = dict(odeint_kwargs=dict(atol=1e-5, rtol=1e-5, method=a.ode_method))
 if a.config5:
-    from transfusion_pytorch_amd.ode import TABLEAUS
+    from transfusion_pytorch_amd.ode import ode_schedule
     m = Transfusion(num_text_tokens=256, dim_latent=384, modality_default_shape=(4,), transformer=dict(dim=1024, depth=24), **okw).cuda().eval()
     g = torch.Generator(device='cuda').manual_seed(1234)
     prompts = []
@@ -41,7 +42,7 @@ if a.config5:
         res = m.sample_many(prompts, **kw)
         torch.cuda.synchronize(); secs.append(time.perf_counter() - t0)
     nmod = sum(sum(isinstance(p, tuple) for p in s) for s in res) - sum(sum(isinstance(q, tuple) for q in (p if isinstance(p, list) else [p])) for p in prompts)
-    evals = len(TABLEAUS[a.ode_method].c) * (a.modality_steps - 1)
+    evals = len(ode_schedule(a.ode_method, a.modality_steps))
     print(f'sample_many config5_forced {a.ode_method} S={a.modality_steps} ({evals} evaluations per modality), '
           f'temperature {temp} top_k {a.top_k} top_p {a.top_p}: first call {secs[0]:.3f} s, repeat call {secs[1]:.3f} s, {nmod} decoded modalities')
     sys.exit(0)

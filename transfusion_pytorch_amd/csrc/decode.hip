@@ -326,6 +326,58 @@ __global__ void ode_rk_update_k(float* y, float* k, const float* ctl, int B, int
   y[at] = fmaf(ctl[(5 + q) * B + i], g, rk_accumulate(y[at], k + at, stride, q, wb));
 }
 
+// ---- Adams-Bashforth multistep rules on top of the tableau kernels (tfx.h: tfx_ode_ab_axpy / tfx_ode_ab_update) ----
+// History terms in table order after the k terms, one fmaf each, a zero weight = the term is skipped and its slot is not read; the g term last.
+TFX_DEV int ab_slot_index(float s) { const int v = (int)s; return v < 0 ? 0 : v > TFX_ODE_AB_HIST - 1 ? TFX_ODE_AB_HIST - 1 : v; }
+
+struct AbHistory { const float* h[TFX_ODE_AB_HIST]; float w[TFX_ODE_AB_HIST]; };
+
+__global__ void ode_ab_axpy_k(const float* y, AbHistory hs, float wg, const float* fc, const float* fu, float cfg, float* g_out, float* out, long long n) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float g = fc[i];
+  if (fu) g = rk_guided(g, fu[i], cfg);
+  float acc = y[i];
+#pragma unroll
+  for (int j = 0; j < TFX_ODE_AB_HIST; j++)
+    if (hs.w[j] != 0.f) acc = fmaf(hs.w[j], hs.h[j][i], acc);
+  out[i] = fmaf(wg, g, acc);                                 // every read of element i is done: g_out may be one of the h_j
+  if (g_out) g_out[i] = g;
+}
+
+// ode_rk_update_k with the history ring.  ctl: [16][B] = the 9 rows of ode_rk_update_k, the slot that receives g, 3 slots read, their 3 weights
+__global__ void ode_ab_update_k(float* y, float* k, float* hist, const float* ctl, int B, int Lc, int dmax, const float* pred, int H, int Lq, int dl,
+                                float cfg, const float* sel, const int32_t* rows0) {
+  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (long long)B * Lc * dl) return;
+  const int c = (int)(e % dl), j = (int)((e / dl) % Lc), i = (int)(e / ((long long)dl * Lc));
+  const int mode = (int)ctl[i];
+  if ((mode != 1 && mode != 2) || (sel && sel[i] == 0.f)) return;
+  const int q = rk_stage_index(ctl[B + i]);
+  if (mode == 1 && q >= TFX_ODE_MAX_STAGES - 1) return;
+  const int rc = rows0 ? rows0[i] : i * Lq;
+  if (rc < 0) return;
+  float g = pred[((size_t)rc + j) * dl + c];
+  if (H == 2) {
+    const int ru = rows0 ? rows0[B + i] : (B + i) * Lq;
+    if (ru < 0) return;
+    g = rk_guided(g, pred[((size_t)ru + j) * dl + c], cfg);
+  }
+  const size_t at = ((size_t)i * Lc + j) * dmax + c, stride = (size_t)B * Lc * dmax;
+  const float to = ctl[9 * B + i];
+  float* keep = to >= 0.f ? hist + (size_t)ab_slot_index(to) * stride + at : nullptr;
+  if (mode == 1) { k[(size_t)q * stride + at] = g; if (keep) *keep = g; return; }
+  const float wb[3] = {ctl[5 * B + i], ctl[6 * B + i], ctl[7 * B + i]};
+  float acc = rk_accumulate(y[at], k + at, stride, q, wb);
+#pragma unroll
+  for (int s = 0; s < TFX_ODE_AB_HIST; s++) {
+    const float w = ctl[(13 + s) * B + i];
+    if (w != 0.f) acc = fmaf(w, hist[(size_t)ab_slot_index(ctl[(10 + s) * B + i]) * stride + at], acc);
+  }
+  y[at] = fmaf(ctl[(5 + q) * B + i], g, acc);                // every read of the element is done: `keep` may be a slot just read
+  if (keep) *keep = g;
+}
+
 // R x C block of a fp32 matrix -> bf16 block of another matrix (8 elements per thread)
 __global__ void cast_block_k(const float* src, int ld_src, bf16* dst, int ld_dst, int R, int C8) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -528,6 +580,26 @@ int tfx_ode_rk_update(float* y, float* k, const float* ctl, int32_t B, int32_t L
   if (!y || !k || !ctl || !pred || H < 1 || H > 2 || Lq < Lc || dl > dmax) return -1;
   const long long n = (long long)B * Lc * dl;
   hipLaunchKernelGGL(ode_rk_update_k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)s, y, k, ctl, B, Lc, dmax, pred, H, Lq, dl, cfg_scale, sel, rows0);
+  return (int)hipGetLastError();
+}
+int tfx_ode_ab_axpy(const float* y, const float* h0, const float* h1, const float* h2, float w0, float w1, float w2, float wg, const float* f_cond,
+                    const float* f_uncond, float cfg_scale, float* g_out, float* out, int64_t n, void* s) {
+  if (n <= 0) return 0;
+  if (!y || !f_cond || !out) return -1;
+  const tfx::AbHistory hs = {{h0, h1, h2}, {w0, w1, w2}};
+  for (int j = 0; j < TFX_ODE_AB_HIST; j++)
+    if (hs.w[j] != 0.f && !hs.h[j]) return -3;
+  hipLaunchKernelGGL(ode_ab_axpy_k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)s, y, hs, wg, f_cond, f_uncond, cfg_scale, g_out, out,
+                     (long long)n);
+  return (int)hipGetLastError();
+}
+int tfx_ode_ab_update(float* y, float* k, float* hist, const float* ctl, int32_t B, int32_t Lc, int32_t dmax, const float* pred, int32_t H, int32_t Lq,
+                      int32_t dl, float cfg_scale, const float* sel, const int32_t* rows0, void* s) {
+  if (B <= 0 || Lc <= 0 || dl <= 0) return 0;
+  if (!y || !k || !hist || !ctl || !pred || H < 1 || H > 2 || Lq < Lc || dl > dmax) return -1;
+  const long long n = (long long)B * Lc * dl;
+  hipLaunchKernelGGL(ode_ab_update_k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)s, y, k, hist, ctl, B, Lc, dmax, pred, H, Lq, dl, cfg_scale,
+                     sel, rows0);
   return (int)hipGetLastError();
 }
 int tfx_scale_bf16_copy(const tfx_bf16* src, tfx_bf16* dst, int64_t n, float scale, void* s) {

@@ -316,7 +316,7 @@ class Plan:
         self.row_tok = {t: z(r, dtype=torch.int32) for t, r in R.items()}
         self.rowbuf = None
         if cache is not None and R and len(set(R.values())) == 1:
-            # decode plans: the per-step row maps of all types (row_tok, then row_src) and a small fp32 control area (`ctl_rows` per-sample rows: 2 for the midpoint solver, 9 for the Runge-Kutta table) live in ONE buffer, so a step
+            # decode plans: the per-step row maps of all types (row_tok, then row_src) and a small fp32 control area (`ctl_rows` per-sample rows: 2 for the midpoint solver, 9 for the Runge-Kutta table, 16 for the multistep rules) live in ONE buffer, so a step
             # uploads them with one copy
             r = next(iter(R.values()))
             self.row_stride = rs = (r + 3) // 4 * 4                       # 16-byte aligned rows

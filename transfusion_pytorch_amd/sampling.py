@@ -34,7 +34,7 @@ import torch
 
 from . import capi
 from .engine import Plan
-from .ode import ode_control, ode_schedule
+from .ode import HIST_SLOTS, MULTISTEP, ode_control, ode_schedule
 
 
 def _flat_len(parts):
@@ -198,9 +198,42 @@ def _ode_rk_solve(method, modality_steps, y, velocity, cfg_scale, stream):
     return y
 
 
+def _ode_ab_axpy(y, Hist, ev, f_cond, f_uncond, cfg_scale, stream):
+    """one multistep step in dense form (tfx_ode_ab_axpy, one launch): y + sum_j ev.hw[j] Hist[ev.hr[j]] + ev.w[0] g is returned, the guided derivative
+    g goes to Hist[ev.store] (a slot the same launch may read) unless no later step reads it.  Hist: fp32 [3, *y.shape]"""
+    out = torch.empty_like(y)
+    pad = HIST_SLOTS - len(ev.hr)
+    capi.check(capi.lib().tfx_ode_ab_axpy(y.data_ptr(), *(Hist[s].data_ptr() for s in ev.hr), *(None,) * pad, *ev.hw, *(0.,) * pad, ev.w[0], f_cond.data_ptr(),
+                                          capi.ptr(f_uncond), float(cfg_scale), Hist[ev.store].data_ptr() if ev.store >= 0 else None, out.data_ptr(),
+                                          y.numel(), ctypes.c_void_p(stream)), 'tfx_ode_ab_axpy')
+    return out
+
+
+def _ode_ab_solve(method, modality_steps, y, velocity, cfg_scale, stream):
+    """the dense loop of the Adams-Bashforth rules: the start-up steps are `_ode_rk_solve`'s launches (their stage-0 derivative copied from K[0] to its
+    history slot on the device), every later step is one evaluation and one tfx_ode_ab_axpy"""
+    y = y.contiguous()
+    K, Hist = (torch.empty(3, *y.shape, device=y.device, dtype=torch.float32) for _ in range(2))
+    x = y
+    for ev in ode_schedule(method, modality_steps):
+        fc, fu = velocity(ev.t, x)
+        if ev.hr:
+            x = _ode_ab_axpy(y, Hist, ev, fc, fu, cfg_scale, stream)
+        else:
+            x = _ode_rk_axpy(y, K, ev, fc, fu, cfg_scale, stream)
+            if ev.store >= 0:
+                Hist[ev.store].copy_(K[0])
+        if ev.last:
+            y = x
+    return y
+
+
 def _ode_solve(method, modality_steps, y, velocity, cfg_scale, stream):
     """one solve of the dense sampling paths over the grid linspace(0, 1, modality_steps), `velocity` as in `_ode_rk_solve`.  The midpoint rule keeps
-    its own kernel: y_mid = y + dt / 2 f(t0, y), y <- y + dt f(t0 + dt / 2, y_mid), one tfx_ode_axpy each; every other rule is `_ode_rk_solve`."""
+    its own kernel: y_mid = y + dt / 2 f(t0, y), y <- y + dt f(t0 + dt / 2, y_mid), one tfx_ode_axpy each; the multistep rules are `_ode_ab_solve`,
+    every other rule is `_ode_rk_solve`."""
+    if method in MULTISTEP:
+        return _ode_ab_solve(method, modality_steps, y, velocity, cfg_scale, stream)
     if method != 'midpoint':
         return _ode_rk_solve(method, modality_steps, y, velocity, cfg_scale, stream)
     x = y = y.contiguous()
@@ -313,12 +346,14 @@ _COMPACT_STEP = int(os.environ.get('TFX_DECODE_COMPACT_STEP', '128'))     # row-
 
 class _Blocks:
     """continuous schedule: the blocks being decoded.  Y [B][Lc][dmax] is the ODE state of every sample, Ym the midpoint state or (tableau rules) K, the stage
-    derivatives [3][B][Lc][dmax]; `sel` [M][B] says per type which samples decode a block of that type; A is the host mirror of the sample states."""
+    derivatives [3][B][Lc][dmax], Hist (multistep rules) the history ring [3][B][Lc][dmax]; `sel` [M][B] says per type which samples decode a block of that
+    type; A is the host mirror of the sample states."""
 
     def __init__(self, smp, c, ctl, cond_times):
         self.smp, self.c, self.ctl, self.cond_times = smp, c, ctl, cond_times     # ctl: ode.ode_control; cond_times: its times + [1.] on the device
         self.rk = smp.m.ode_method != 'midpoint'                                  # the tableau rules: tfx_ode_rk_stage / tfx_ode_rk_update
-        self.Lc, self.Y, self.Ym = 0, None, None
+        self.ab = smp.m.ode_method in MULTISTEP                                   # tfx_ode_rk_stage / tfx_ode_ab_update
+        self.Lc, self.Y, self.Ym, self.Hist = 0, None, None, None
         M = smp.m.num_modalities
         self.sel = torch.zeros(M, c.B, device=smp.dev) if M > 1 else None
         self.A = np.zeros((11, c.B), np.int64)
@@ -329,9 +364,12 @@ class _Blocks:
         L, dmax = st.modality_length, max(smp.md.dim_latents)
         if L > self.Lc:
             newY, newYm = torch.zeros(B, L, dmax, device=smp.dev), torch.zeros(*((3,) if self.rk else ()), B, L, dmax, device=smp.dev)
+            newHist = torch.zeros(HIST_SLOTS, B, L, dmax, device=smp.dev) if self.ab else None
             if self.Y is not None:
                 newY[:, :self.Lc], newYm[..., :self.Lc, :] = self.Y, self.Ym
-            self.Y, self.Ym, self.Lc = newY, newYm, L
+                if self.ab:
+                    newHist[:, :, :self.Lc] = self.Hist
+            self.Y, self.Ym, self.Hist, self.Lc = newY, newYm, newHist, L
         smp._init_noise(self.Y[i], st, self.c)
         st.begin_block(self.c.use_cfg)
         if self.sel is not None:
@@ -657,9 +695,10 @@ class Sampler:
         m, md, B, H, stream = self.m, self.md, c.B, c.H, c.stream
         M, dmax, sp = m.num_modalities, max(md.dim_latents), ctypes.c_void_p(c.stream)
         lib = capi.lib()
-        ode_stage, ode_update = (lib.tfx_ode_rk_stage, lib.tfx_ode_rk_update) if blocks.rk else (lib.tfx_ode_stage, lib.tfx_ode_update)
+        ode_stage, ode_update = (lib.tfx_ode_rk_stage, lib.tfx_ode_ab_update if blocks.ab else lib.tfx_ode_rk_update) if blocks.rk else (lib.tfx_ode_stage, lib.tfx_ode_update)
         unit_blk0 = p.unit_blk0.data_ptr() if lay.units is not None else None
         Y, Ym, Lc = blocks.Y, blocks.Ym, blocks.Lc
+        hist = (blocks.Hist.data_ptr(),) if blocks.ab else ()        # the multistep rules' ring, next to the stage derivatives
         if not getattr(p, '_cont_ready', False):
             for t in range(M):
                 p.row_inst[t].zero_()
@@ -679,7 +718,7 @@ class Sampler:
         self._run(p, stream, p.fwd_cond[1], p.fwd_pred_end)
         for t in range(M):
             dl = md.dim_latents[t]
-            capi.check(ode_update(Y.data_ptr(), Ym.data_ptr(), p.ctl.data_ptr(), B, Lc, dmax, p.lat[t]['pred'].data_ptr(), H, Lq, dl,
+            capi.check(ode_update(Y.data_ptr(), Ym.data_ptr(), *hist, p.ctl.data_ptr(), B, Lc, dmax, p.lat[t]['pred'].data_ptr(), H, Lq, dl,
                                   float(c.cfg_scale), blocks.sel[t].data_ptr() if M > 1 else None, unit_blk0, sp), 'tfx_ode_update')
 
     def _upload_row_maps(self, p, lay, r, ctl):

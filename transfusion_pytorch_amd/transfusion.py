@@ -1662,10 +1662,10 @@ class Transfusion(nn.Module):
         try:
             grid = torch.linspace(0., 1., modality_steps, device=dev)
             f = lambda tt, yy: self.forward_modality(yy, times=tt.expand(batch_size), modality_type=t, encode_modality=False, return_loss=False)
-            if self.ode_method != 'midpoint':                                              # the other tableaus: one tfx_ode_rk_axpy per evaluation
-                from .sampling import _ode_rk_solve
+            if self.ode_method != 'midpoint':                                              # the other rules: one tfx_ode_rk_axpy / tfx_ode_ab_axpy per evaluation
+                from .sampling import _ode_solve
                 vel = lambda tt, yy: (f(torch.full((1,), tt, device=dev), yy).float().contiguous(), None)
-                y = _ode_rk_solve(self.ode_method, modality_steps, y, vel, 1., self._stream())
+                y = _ode_solve(self.ode_method, modality_steps, y, vel, 1., self._stream())
             else:
                 for i in range(modality_steps - 1):                                        # torchdiffeq fixed-grid 'midpoint'
                     t0, dt = grid[i], grid[i + 1] - grid[i]
