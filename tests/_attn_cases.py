@@ -9,6 +9,9 @@ and the first masked key e are aligned with those rows' queries: the three score
 distinct values.  The rows' weight splits over the visible sentinels (so dS = P (dP - delta) does not cancel), and one key more or less moves
 their output and gradients by O(1), far above the per-row tolerances below - which the CPU mutation test (tests/test_attention_layouts_cpu.py)
 proves with the same builder and the same tolerances.  The odd heads stay random.
+
+The tolerances below are MEASURED on the kernels; the derived per-element bounds are in tests/_attn_bounds.py (tests/test_attention_softcap_gpu.py): out, lse,
+do_eff, delta, dgate, dq, dk and dv of the plain and the LASER path now have both, the fused QK-norm backward's raw d q | d k and gain gradients only these.
 """
 import math
 from typing import NamedTuple
