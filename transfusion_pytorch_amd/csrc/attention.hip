@@ -10,6 +10,7 @@
 // MFMA contraction "slots" e=0..7 of lane-half hi map to rows 16*tt + 8*(e>>2) + 4*hi + (e&3) of a
 // 32-row block: both operands use the same map, so the sum is unchanged.
 #include "tfx_kernels.h"
+#include "stage_block.h"
 #include "attn_asm_clobbers.inc"
 
 namespace tfx {
@@ -214,10 +215,8 @@ TFX_DEV bf16x8 pack8(const f32x16& v, int tt) {
 // whenever heads * samples is a multiple of 8.  (Measured round 6, profiles/r06_attn_pmc_l2_by_block_order.txt: the L2 hit rate of this order is 5 % - 512 other
 // pairs run between two tiles of a pair; an XCD-local order reaches 68 % and is SLOWER in the step: the operands come from the Infinity Cache either way and the
 // heaviest-first balance matters more.  The tile-fastest grid of round 1 was removed.)
-// A wave's 32 x 64 bf16 output block (this lane: row l & 31, columns db * 32 + 8 rg + 4 hi .. + 3) leaves through a wave-private 4 KiB LDS image:
-// 16-byte stores, 8 lanes per 128-byte row = 8 cache lines per instruction.  The direct form - 8 bytes per lane in accumulator shape - puts
-// 32 rows behind every store instruction and visits each line 8 times (the address coalescer walks the lines one by one: the same effect that
-// cost the NT epilogues 7 k clocks per tile, gemm.hip staged_epilogue_bf16).  `st` must be free: the callers pass a tile buffer behind a barrier.
+// A wave's 32 x 64 bf16 output block (this lane: row l & 31, columns db * 32 + 8 rg + 4 hi .. + 3) leaves as the staged block of stage_block.h
+// (layout, read-back and the reason for staging are there).  `st` must be free: the callers pass a tile buffer behind a barrier.
 // Falls back to the direct stores when a row is not 16-byte aligned.
 TFX_DEV void wave_block_store(bf16* st, const bf16x4 (&v)[2][4], bf16* g0, int ld, int rows_valid, int lane = -1) {
   const int l = (lane >= 0 ? lane : (int)threadIdx.x) & 63, hi = l >> 5, r = l & 31, ch = l & 7;
@@ -233,16 +232,9 @@ TFX_DEV void wave_block_store(bf16* st, const bf16x4 (&v)[2][4], bf16* g0, int l
 #pragma unroll
   for (int db = 0; db < 2; db++)
 #pragma unroll
-    for (int rg = 0; rg < 4; rg++) {
-      const int col = db * 32 + 8 * rg + 4 * hi;
-      *(bf16x4*)(st + r * 64 + (((col >> 3) ^ ((r >> 1) & 7)) << 3) + (col & 7)) = v[db][rg];
-    }
+    for (int rg = 0; rg < 4; rg++) *(bf16x4*)(st + stage_off(r, db * 32 + 8 * rg + 4 * hi)) = v[db][rg];
   bf16x8 t[4];
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-    const int row = q * 8 + (l >> 3);
-    t[q] = *(const bf16x8*)(st + row * 64 + ((ch ^ ((row >> 1) & 7)) << 3));
-  }
+  stage_read4(st, l, ch, t);
 #pragma unroll
   for (int q = 0; q < 4; q++) {
     const int row = q * 8 + (l >> 3);
@@ -262,10 +254,7 @@ TFX_DEV void wave_block_store_nr(bf16* st, const bf16x4 (&v)[2][4], const tfx_at
 #pragma unroll
   for (int db = 0; db < 2; db++)
 #pragma unroll
-    for (int rg = 0; rg < 4; rg++) {
-      const int col = db * 32 + 8 * rg + 4 * hi;
-      *(bf16x4*)(st + r * 64 + (((col >> 3) ^ ((r >> 1) & 7)) << 3) + (col & 7)) = v[db][rg];
-    }
+    for (int rg = 0; rg < 4; rg++) *(bf16x4*)(st + stage_off(r, db * 32 + 8 * rg + 4 * hi)) = v[db][rg];
   if (!p.nr_gamma_q) {                                            // (kernel argument: uniform) no gains = no RMS normalisation (tfx.h): d q = q_scale rope^T(d q~),
     const int last = max(rows_valid - 1, 0);                      // d k = rope^T(d k~) - tokenwise.hip's spelling (qk_rope_bwd_chunk), no raw chunk, no gain gradients
     int pos[4];
@@ -275,7 +264,7 @@ TFX_DEV void wave_block_store_nr(bf16* st, const bf16x4 (&v)[2][4], const tfx_at
     for (int q = 0; q < 4; q++) {
       const int row = q * 8 + (l >> 3), rd = min(row, last);
       const f32x4 cs = *(const f32x4*)(p.nr_cos + (size_t)pos[q] * 32 + ch * 4), sn = *(const f32x4*)(p.nr_sin + (size_t)pos[q] * 32 + ch * 4);
-      const bf16x8 t = *(const bf16x8*)(st + rd * 64 + ((ch ^ ((rd >> 1) & 7)) << 3));
+      const bf16x8 t = *(const bf16x8*)(st + stage_chunk(rd, ch));
       const bf16x8 o = qk_rope_bwd_chunk(t, WHICH == 0 ? p.nr_q_scale : 1.f, cs, sn);
       if (row < rows_valid) *(bf16x8*)(p.nr_dqkv + (tok + row) * p.nr_ld_dqkv + colq + ch * 8) = o;
     }
@@ -297,11 +286,7 @@ TFX_DEV void wave_block_store_nr(bf16* st, const bf16x4 (&v)[2][4], const tfx_at
     cs[q] = *(const f32x4*)(p.nr_cos + (size_t)pos * 32 + ch * 4);
     sn[q] = *(const f32x4*)(p.nr_sin + (size_t)pos * 32 + ch * 4);
   }
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-    const int row = min(q * 8 + (l >> 3), last);
-    t[q] = *(const bf16x8*)(st + row * 64 + ((ch ^ ((row >> 1) & 7)) << 3));
-  }
+  stage_read4<true>(st, l, ch, t, last);
 #pragma unroll
   for (int q = 0; q < 4; q++) {
     const int row = q * 8 + (l >> 3);

@@ -10,6 +10,7 @@
 #include "tfx_common.h"
 #include "tfx_kernels.h"
 #include "nt_ring.h"
+#include "stage_block.h"
 #include <type_traits>
 #include <cmath>
 #include <cstring>
@@ -124,21 +125,8 @@ TFX_DEV void fast_epilogue(const GemmNT& p, f32x16 (&acc)[NI][2], int m_w, int n
     const int m = m_w + i * 32 + r;
     mo[i] = m < p.M ? (p.rowmap ? p.rowmap[m] : m) : -1;
   }
-  // ONE branch around all eight loads: with a branch per load hipcc waits (`s_waitcnt vmcnt(0)`) at every join - eight serial round trips to L2
-  f32x4 bias[2][4];
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int j = 0; j < 2; j++)
-#pragma unroll
-    for (int g = 0; g < 4; g++) bias[j][g] = zero4;
-  if constexpr (EPI != EPI_GEGLU_BWD) {
-    if (p.bias) {
-#pragma unroll
-      for (int j = 0; j < 2; j++)
-#pragma unroll
-        for (int g = 0; g < 4; g++) bias[j][g] = *(const f32x4*)(p.bias + min(n_w + j * 32 + 8 * g + 4 * hi, p.N - 4));
-    }
-  }
+  f32x4 bias[2][4];                                            // one branch around the eight loads (stage_bias)
+  stage_bias(bias, EPI != EPI_GEGLU_BWD ? p.bias : nullptr, n_w, hi, p.N);
   // side-data loads are unconditional (addresses clamped into range): a load under a divergent branch makes the
   // compiler fall back to vmcnt(0) at the join, which would drain the stores again
   auto load_in = [&](EpiIn<EPI>& in, int i) {
@@ -227,46 +215,23 @@ TFX_DEV void fast_epilogue(const GemmNT& p, f32x16 (&acc)[NI][2], int m_w, int n
 }
 
 // ------------------------------------------------------------------------------------------------
-// LDS-staged store of a wave's 32x64 bf16 block.  fast_epilogue's bf16x4 stores put 64 different rows (64 cache
-// lines) behind every store instruction; s_memtime stamps of the 256x256 kernel show that issuing them takes ~10k
-// cycles per tile - as long as 3.3 K-tiles of MFMA work - because the address coalescer walks the lines one by one.
-// Staging the block through a wave-private 4 KiB LDS area (128-byte rows, chunk index XOR ((row >> 1) & 7): conflict-free
-// for both the 8-byte writes and the 16-byte reads) turns them into 16-byte stores with 8 lanes per 128-byte row segment:
-// 8 lines per instruction.  No block barrier: the area is wave-private and one wave's LDS operations execute in order.
+// LDS-staged stores of a wave's 32x64 blocks: layout, read-back, flush and the reasons for staging are in stage_block.h.
 // ------------------------------------------------------------------------------------------------
-TFX_DEV void stage_put4(bf16* st, int row, int col, f32x4 v) {
-  bf16x4 o; o[0] = f2bf(v[0]); o[1] = f2bf(v[1]); o[2] = f2bf(v[2]); o[3] = f2bf(v[3]);
-  *(bf16x4*)(st + row * 64 + (((col >> 3) ^ ((row >> 1) & 7)) << 3) + (col & 7)) = o;
-}
 // C(bf16)[mo][n_w .. n_w+63] = acc + bias for the NI 32-row blocks of a wave; needs ldc % 8 == 0, N % 8 == 0, C 16-byte aligned
 // PLAIN (no row map, no bias): no load at all - and therefore no wait: hipcc puts the `s_waitcnt vmcnt(0)` of the (conditional) side loads on the common path, where it
 // drains whatever is in flight: the stores of a wave's previous 64-column half (one-wave-per-SIMD kernels: two calls per wave), the next tile's DMAs (persistent kernel)
-template <int NI, bool PLAIN = false>
+// CACHE (with PLAIN; the v columns of a decode step): the rows also go, as bf16, to the KV cache behind the k~ columns (tfx_qk_norm_rope_fwd's `cache` path)
+template <int NI, bool PLAIN = false, bool CACHE = false>
 TFX_DEV void staged_epilogue_bf16(const GemmNT& p, f32x16 (&acc)[NI][2], int m_w, int n_w, bf16* st, int lane = -1) {
   const int l = lane >= 0 ? lane : (int)(threadIdx.x & 63), hi = l >> 5, r = l & 31, ch = l & 7;
-  int mo[NI][4];                                               // output row of (block i, flush pass q): row q * 8 + (l >> 3)
-#pragma unroll
-  for (int i = 0; i < NI; i++)
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      const int m = m_w + i * 32 + q * 8 + (l >> 3);
-      if constexpr (PLAIN) mo[i][q] = m < p.M ? m : -1;
-      else mo[i][q] = m < p.M ? (p.rowmap ? p.rowmap[m] : m) : -1;
-    }
-  f32x4 bias[2][4];                                            // one branch around the eight loads (see fast_epilogue)
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int j = 0; j < 2; j++)
-#pragma unroll
-    for (int g = 0; g < 4; g++) bias[j][g] = zero4;
-  if constexpr (!PLAIN) {
-    if (p.bias) {
-#pragma unroll
-      for (int j = 0; j < 2; j++)
-#pragma unroll
-        for (int g = 0; g < 4; g++) bias[j][g] = *(const f32x4*)(p.bias + min(n_w + j * 32 + 8 * g + 4 * hi, p.N - 4));
-    }
+  int mo[NI][4], cp[CACHE ? NI : 1][4];                        // output row / cache row of (block i, flush pass q)
+  stage_rows<PLAIN ? ROWS_IDENT : ROWS_MAP_OR_IDENT>(mo, m_w, p.M, l, p.rowmap);
+  if constexpr (CACHE) {
+    stage_rows<ROWS_MAP>(cp, m_w, p.M, l, p.qk_cache_pos);
+    asm volatile("" ::: "memory");
   }
+  f32x4 bias[2][4];
+  stage_bias(bias, PLAIN ? nullptr : p.bias, n_w, hi, p.N);
   const bool col_ok = n_w + ch * 8 < p.N;
 #ifdef TFX_PP_TIMING
   unsigned long long* stamps = (unsigned long long*)p.aux + (size_t)blockIdx.x * 8;
@@ -284,15 +249,16 @@ TFX_DEV void staged_epilogue_bf16(const GemmNT& p, f32x16 (&acc)[NI][2], int m_w
         for (int e = 0; e < 4; e++) v[e] = PLAIN ? acc[i][j][4 * g + e] : acc[i][j][4 * g + e] + bias[j][g][e];
         stage_put4(s, r, j * 32 + 8 * g + 4 * hi, v);
       }
-    bf16x8 v[4];                                               // all four LDS reads ahead of the (branch-guarded) stores: one LDS latency per block, not four
+    bf16x8 v[4];
+    stage_read4(s, l, ch, v);
+    // the stores spelled out, not stage_store4: with its operands evaluated ahead of the predicate hipcc spills 37 registers in gemm_nt_ow_kernel<BF16> (2 without)
 #pragma unroll
     for (int q = 0; q < 4; q++) {
-      const int row = q * 8 + (l >> 3);
-      v[q] = *(const bf16x8*)(s + row * 64 + ((ch ^ ((row >> 1) & 7)) << 3));
-    }
-#pragma unroll
-    for (int q = 0; q < 4; q++)
       if (col_ok && mo[i][q] >= 0) *(bf16x8*)((bf16*)p.C + (size_t)mo[i][q] * p.ldc + n_w + ch * 8) = v[q];
+      if constexpr (CACHE) {
+        if (col_ok && cp[i][q] >= 0) *(bf16x8*)((bf16*)p.qk_cache + (size_t)cp[i][q] * p.qk_ld_cache + (n_w - p.qk_heads * 64) + ch * 8) = v[q];
+      }
+    }
 #ifdef TFX_PP_TIMING
     if (threadIdx.x == 0 && i < 2) stamps[6 + i] = __builtin_readcyclecounter();
 #endif
@@ -305,26 +271,13 @@ template <int NI>
 TFX_DEV void staged_epilogue_resid(const GemmNT& p, f32x16 (&acc)[NI][2], int m_w, int n_w, bf16* st) {
   const int l = threadIdx.x & 63, hi = l >> 5, r = l & 31, ch = l & 7;
   int mo[NI][4], mr[NI][4];                                    // output row / residual row of (block i, pass q): tile row q * 8 + (l >> 3)
+  stage_rows<ROWS_MAP_OR_IDENT>(mo, m_w, p.M, l, p.rowmap);
 #pragma unroll
   for (int i = 0; i < NI; i++)
 #pragma unroll
-    for (int q = 0; q < 4; q++) {
-      const int m = m_w + i * 32 + q * 8 + (l >> 3);
-      mo[i][q] = m < p.M ? (p.rowmap ? p.rowmap[m] : m) : -1;
-      mr[i][q] = p.resid_mapped ? max(mo[i][q], 0) : min(m, p.M - 1);
-    }
-  f32x4 bias[2][4];                                            // one branch around the eight loads (see fast_epilogue)
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int j = 0; j < 2; j++)
-#pragma unroll
-    for (int g = 0; g < 4; g++) bias[j][g] = zero4;
-  if (p.bias) {
-#pragma unroll
-    for (int j = 0; j < 2; j++)
-#pragma unroll
-      for (int g = 0; g < 4; g++) bias[j][g] = *(const f32x4*)(p.bias + min(n_w + j * 32 + 8 * g + 4 * hi, p.N - 4));
-  }
+    for (int q = 0; q < 4; q++) mr[i][q] = p.resid_mapped ? max(mo[i][q], 0) : min(m_w + i * 32 + q * 8 + (l >> 3), p.M - 1);
+  f32x4 bias[2][4];
+  stage_bias(bias, p.bias, n_w, hi, p.N);
   const bool col_ok = n_w + ch * 8 < p.N;
   const int ncol = min(n_w + ch * 8, p.N - 8);
   bf16* sr = st + 4096;                                        // residual block; the two output areas keep st[0, 4096)
@@ -337,10 +290,7 @@ TFX_DEV void staged_epilogue_resid(const GemmNT& p, f32x16 (&acc)[NI][2], int m_
 #pragma unroll
   for (int i = 0; i < NI; i++) {
 #pragma unroll
-    for (int q = 0; q < 4; q++) {
-      const int row = q * 8 + (l >> 3);
-      *(bf16x8*)(sr + row * 64 + ((ch ^ ((row >> 1) & 7)) << 3)) = pre[q];
-    }
+    for (int q = 0; q < 4; q++) *(bf16x8*)(sr + stage_chunk(q * 8 + (l >> 3), ch)) = pre[q];
     if (i + 1 < NI) load_r(i + 1);
     bf16* s = st + (i & 1) * 2048;
 #pragma unroll
@@ -348,27 +298,16 @@ TFX_DEV void staged_epilogue_resid(const GemmNT& p, f32x16 (&acc)[NI][2], int m_
 #pragma unroll
       for (int g = 0; g < 4; g++) {
         const int col = j * 32 + 8 * g + 4 * hi;
-        const bf16x4 rv = *(const bf16x4*)(sr + r * 64 + (((col >> 3) ^ ((r >> 1) & 7)) << 3) + (col & 7));
+        const bf16x4 rv = *(const bf16x4*)(sr + stage_off(r, col));
         f32x4 v;
 #pragma unroll
         for (int e = 0; e < 4; e++) v[e] = acc[i][j][4 * g + e] + bias[j][g][e] + bf2f(rv[e]);
         stage_put4(s, r, col, v);
       }
     bf16x8 v[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      const int row = q * 8 + (l >> 3);
-      v[q] = *(const bf16x8*)(s + row * 64 + ((ch ^ ((row >> 1) & 7)) << 3));
-    }
-#pragma unroll
-    for (int q = 0; q < 4; q++)
-      if (col_ok && mo[i][q] >= 0) *(bf16x8*)((bf16*)p.C + (size_t)mo[i][q] * p.ldc + n_w + ch * 8) = v[q];
+    stage_read4(s, l, ch, v);
+    stage_store4(v, col_ok, (bf16*)p.C + n_w, p.ldc, ch, mo[i]);
   }
-}
-// 32x32 bf16 block (64-byte rows; chunk XOR ((row >> 2) & 3)) for the GEGLU product h = a * gelu(g)
-TFX_DEV void stage_put4_32(bf16* st, int row, int col, f32x4 v) {
-  bf16x4 o; o[0] = f2bf(v[0]); o[1] = f2bf(v[1]); o[2] = f2bf(v[2]); o[3] = f2bf(v[3]);
-  *(bf16x4*)(st + row * 32 + (((col >> 3) ^ ((row >> 2) & 3)) << 3) + (col & 7)) = o;
 }
 // GEGLU forward / backward with staged stores.  Forward: per 32-row block one [a|g] block (32x64) and one h block (32x32).
 // Backward: per 32-row block two [da|dg] blocks (one per 32 dh columns).  The saved-activation loads of the backward stay
@@ -403,26 +342,16 @@ TFX_DEV GegluUVH geglu_uvh_grid(const float* gtab, float a, float g) {
 template <int EPI, int NI>
 TFX_DEV void staged_epilogue_geglu(const GemmNT& p, f32x16 (&acc)[NI][2], int m_w, int n_w, bf16* st, const float* gtab = nullptr, bool use_tab = false) {
   const int l = threadIdx.x & 63, hi = l >> 5, r = l & 31, ch = l & 7;
-  int mo[NI][4], mo2[NI][2];                                   // rows of the 8-lane-per-row / 4-lane-per-row flush passes
-#pragma unroll
-  for (int i = 0; i < NI; i++) {
-#pragma unroll
-    for (int q = 0; q < 4; q++) { const int m = m_w + i * 32 + q * 8 + (l >> 3); mo[i][q] = m < p.M ? (p.rowmap ? p.rowmap[m] : m) : -1; }
-#pragma unroll
-    for (int q = 0; q < 2; q++) { const int m = m_w + i * 32 + q * 16 + (l >> 2); mo2[i][q] = (EPI == EPI_GEGLU && m < p.M) ? (p.rowmap ? p.rowmap[m] : m) : -1; }
-  }
+  int mo[NI][4];                                               // rows of the 8-lane-per-row flush passes
+  stage_rows<ROWS_MAP_OR_IDENT>(mo, m_w, p.M, l, p.rowmap);
   auto flush64 = [&](const bf16* s, int i, int n_base, int Nout) {
     bf16x8 v[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      const int row = q * 8 + (l >> 3);
-      v[q] = *(const bf16x8*)(s + row * 64 + ((ch ^ ((row >> 1) & 7)) << 3));
-    }
-#pragma unroll
-    for (int q = 0; q < 4; q++)
-      if (n_base + ch * 8 < Nout && mo[i][q] >= 0) *(bf16x8*)((bf16*)p.C + (size_t)mo[i][q] * p.ldc + n_base + ch * 8) = v[q];
+    stage_read4(s, l, ch, v);
+    stage_store4(v, n_base + ch * 8 < Nout, (bf16*)p.C + n_base, p.ldc, ch, mo[i]);
   };
   if constexpr (EPI == EPI_GEGLU) {
+    int mo2[NI][2];                                            // rows of the 4-lane-per-row passes of the h block
+    stage_rows<ROWS_MAP_OR_IDENT>(mo2, m_w, p.M, l, p.rowmap);
     f32x4 ba[4], bg[4];                                        // one branch around the eight loads (see fast_epilogue)
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -451,10 +380,7 @@ TFX_DEV void staged_epilogue_geglu(const GemmNT& p, f32x16 (&acc)[NI][2], int m_
       flush64(s, i, n_w, p.N);
       bf16x8 hv[2];
 #pragma unroll
-      for (int q = 0; q < 2; q++) {
-        const int row = q * 16 + (l >> 2);
-        hv[q] = *(const bf16x8*)(s + 2048 + row * 32 + ((c4 ^ ((row >> 2) & 3)) << 3));
-      }
+      for (int q = 0; q < 2; q++) hv[q] = *(const bf16x8*)(s + 2048 + stage_off32(q * 16 + (l >> 2), c4 * 8));
       const int feat = (n_w >> 6) * 32 + c4 * 8;
 #pragma unroll
       for (int q = 0; q < 2; q++)
@@ -464,7 +390,7 @@ TFX_DEV void staged_epilogue_geglu(const GemmNT& p, f32x16 (&acc)[NI][2], int m_
     // The saved [a|g] of a 32-row block - for the wave's 64 dh columns 128 contiguous bf16 per row - comes in with 16-byte loads, 16 lanes per row
     // (8 cache lines per instruction), passes through a wave-private LDS image (chunk index XOR (row & 15)) and is read back in fragment shape.
     // Round 2 loaded it as 8-byte per-lane fragments: 32 rows = 32 cache lines behind every load instruction, 512 line visits per block against 64
-    // (the same address-coalescer walk that made the direct stores slow, see staged_epilogue_bf16).
+    // (the same address-coalescer walk that made the direct stores slow, see stage_block.h).
     bf16* sag = st + 2048;                                       // [32][128]; the output staging block keeps st[0, 2048)
     const int cbase = min(n_w >> 5, (p.N >> 5) - 2) * 64;
     bf16x8 pre[8];
@@ -482,15 +408,15 @@ TFX_DEV void staged_epilogue_geglu(const GemmNT& p, f32x16 (&acc)[NI][2], int m_
 #pragma unroll
       for (int k = 0; k < 8; k++) {
         const int q = l + 64 * k, row = q >> 4, cc = q & 15;
-        *(bf16x8*)(sag + row * 128 + ((cc ^ (row & 15)) << 3)) = pre[k];
+        *(bf16x8*)(sag + stage_off_ag(row, cc * 8)) = pre[k];
       }
       if (i + 1 < NI) load_aux(i + 1);
 #pragma unroll
       for (int j = 0; j < 2; j++) {
 #pragma unroll
         for (int g = 0; g < 4; g++) {
-          const bf16x4 u4 = *(const bf16x4*)(sag + r * 128 + (((j * 8 + g) ^ (r & 15)) << 3) + 4 * hi);          // saved u = gelu(g)
-          const bf16x4 v4 = *(const bf16x4*)(sag + r * 128 + (((j * 8 + 4 + g) ^ (r & 15)) << 3) + 4 * hi);      // saved v = a gelu'(g)
+          const bf16x4 u4 = *(const bf16x4*)(sag + stage_off_ag(r, j * 64 + 8 * g + 4 * hi));           // saved u = gelu(g)
+          const bf16x4 v4 = *(const bf16x4*)(sag + stage_off_ag(r, j * 64 + 32 + 8 * g + 4 * hi));      // saved v = a gelu'(g)
           f32x4 da, dg;
 #pragma unroll
           for (int e = 0; e < 4; e++) {
@@ -533,13 +459,8 @@ TFX_DEV void staged_epilogue_qknr_(const GemmNT& p, f32x16 (&acc)[NI][2], int m_
   // other side data (a load behind a store waits for the store's round trip)
   // (NI == 1 = the decode-step kernel's instantiation: the 256 x 256 kernel never appends - qknr_fusable - and has no registers to spare for the positions)
   const bool to_cache = NI == 1 && p.qk_cache != nullptr && which == 1;      // wave-uniform
-  int cpos[NI == 1 ? NS : 1][2];
-  if constexpr (NI == 1) {
-#pragma unroll
-    for (int s = 0; s < NS; s++)
-#pragma unroll
-      for (int k = 0; k < 2; k++) { const int m = row_of(s, k); cpos[s][k] = (to_cache && m < p.M) ? p.qk_cache_pos[m] : -1; }
-  }
+  int cpos[1][4];                                                  // cache row of flush pass q = 2 (s & 1) + k
+  if constexpr (NI == 1) stage_rows<ROWS_MAP>(cpos, m_w, to_cache ? p.M : 0, l, p.qk_cache_pos);      // (no rows unless this wave appends)
   auto load_cs = [&](const int (&pos)[2], f32x4 (&cs)[2], f32x4 (&sn)[2]) {
 #pragma unroll
     for (int k = 0; k < 2; k++) {
@@ -575,25 +496,12 @@ TFX_DEV void staged_epilogue_qknr_(const GemmNT& p, f32x16 (&acc)[NI][2], int m_
     }
     if (qh == 0) {                                                 // stage the 32-row block, read it back row-major, store the raw projection
       bf16* sbuf = st + (i & 1) * 2048;
+      stage_put_acc(sbuf, r, hi, acc[i]);
+      stage_read4(sbuf, l, ch, v);
+      int mq[4];
 #pragma unroll
-      for (int j = 0; j < 2; j++)
-#pragma unroll
-        for (int g = 0; g < 4; g++) {
-          f32x4 a4;
-#pragma unroll
-          for (int e = 0; e < 4; e++) a4[e] = acc[i][j][4 * g + e];
-          stage_put4(sbuf, r, j * 32 + 8 * g + 4 * hi, a4);
-        }
-#pragma unroll
-      for (int q = 0; q < 4; q++) {
-        const int row = q * 8 + (l >> 3);
-        v[q] = *(const bf16x8*)(sbuf + row * 64 + ((ch ^ ((row >> 1) & 7)) << 3));
-      }
-#pragma unroll
-      for (int q = 0; q < 4; q++) {
-        const int m = m_w + i * 32 + q * 8 + (l >> 3);
-        if (!GUARD || (col_ok && m < p.M)) *(bf16x8*)((bf16*)p.C + (size_t)m * p.ldc + n_w + ch * 8) = v[q];
-      }
+      for (int q = 0; q < 4; q++) { const int m = m_w + i * 32 + q * 8 + (l >> 3); mq[q] = (!GUARD || m < p.M) ? m : -1; }
+      stage_store4<GUARD>(v, col_ok, (bf16*)p.C + n_w, p.ldc, ch, mq);
     }
     {
 #pragma unroll
@@ -606,47 +514,9 @@ TFX_DEV void staged_epilogue_qknr_(const GemmNT& p, f32x16 (&acc)[NI][2], int m_
         const int m = row_of(s, k);
         if (!GUARD || m < p.M) *(bf16x8*)((bf16*)p.C2 + (size_t)m * p.ldc2 + n_w + ch * 8) = o;
         if constexpr (NI == 1) {
-          if (to_cache && cpos[s][k] >= 0) *(bf16x8*)((bf16*)p.qk_cache + (size_t)cpos[s][k] * p.qk_ld_cache + (n_w - hd) + ch * 8) = o;
+          if (to_cache && cpos[0][2 * qh + k] >= 0) *(bf16x8*)((bf16*)p.qk_cache + (size_t)cpos[0][2 * qh + k] * p.qk_ld_cache + (n_w - hd) + ch * 8) = o;
         }
       }
-    }
-  }
-}
-// v columns of a decode step: the raw projection goes to C and, as bf16 rows, to the KV cache behind the k~ columns (tfx_qk_norm_rope_fwd's `cache` path)
-template <int NI>
-TFX_DEV void staged_epilogue_vcache(const GemmNT& p, f32x16 (&acc)[NI][2], int m_w, int n_w, bf16* st) {
-  const int l = threadIdx.x & 63, hi = l >> 5, r = l & 31, ch = l & 7;
-  const int hd = p.qk_heads * 64;
-  const bool col_ok = n_w + ch * 8 < p.N;
-  int cp[NI][4];
-#pragma unroll
-  for (int i = 0; i < NI; i++)
-#pragma unroll
-    for (int q = 0; q < 4; q++) { const int m = m_w + i * 32 + q * 8 + (l >> 3); cp[i][q] = m < p.M ? p.qk_cache_pos[m] : -1; }
-  asm volatile("" ::: "memory");
-#pragma unroll
-  for (int i = 0; i < NI; i++) {
-    bf16* sbuf = st + (i & 1) * 2048;
-#pragma unroll
-    for (int j = 0; j < 2; j++)
-#pragma unroll
-      for (int g = 0; g < 4; g++) {
-        f32x4 a4;
-#pragma unroll
-        for (int e = 0; e < 4; e++) a4[e] = acc[i][j][4 * g + e];
-        stage_put4(sbuf, r, j * 32 + 8 * g + 4 * hi, a4);
-      }
-    bf16x8 v[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      const int row = q * 8 + (l >> 3);
-      v[q] = *(const bf16x8*)(sbuf + row * 64 + ((ch ^ ((row >> 1) & 7)) << 3));
-    }
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      const int m = m_w + i * 32 + q * 8 + (l >> 3);
-      if (col_ok && m < p.M) *(bf16x8*)((bf16*)p.C + (size_t)m * p.ldc + n_w + ch * 8) = v[q];
-      if (col_ok && cp[i][q] >= 0) *(bf16x8*)((bf16*)p.qk_cache + (size_t)cp[i][q] * p.qk_ld_cache + (n_w - hd) + ch * 8) = v[q];
     }
   }
 }
@@ -654,7 +524,7 @@ template <int NI>
 TFX_DEV void staged_epilogue_qknr(const GemmNT& p, f32x16 (&acc)[NI][2], int m_w, int n_w, bf16* st) {
   const int hd_ = p.qk_heads * 64;
   if constexpr (NI == 1) {
-    if (p.qk_cache && n_w >= 2 * hd_ && n_w + 64 <= 3 * hd_) { staged_epilogue_vcache<NI>(p, acc, m_w, n_w, st); return; }      // v columns of a decode step (wave-uniform)
+    if (p.qk_cache && n_w >= 2 * hd_ && n_w + 64 <= 3 * hd_) { staged_epilogue_bf16<NI, true, true>(p, acc, m_w, n_w, st); return; }      // v columns of a decode step (wave-uniform): raw rows to C and to the KV cache
   }
   if (n_w + 64 > 2 * p.qk_heads * 64) { staged_epilogue_bf16<NI>(p, acc, m_w, n_w, st); return; }      // v / gate columns: the plain staged store (wave-uniform)
   if (m_w + 32 * NI <= p.M) staged_epilogue_qknr_<NI, false>(p, acc, m_w, n_w, st);
@@ -670,25 +540,9 @@ TFX_DEV void staged_epilogue_f32(const GemmNT& p, f32x16 (&acc)[NI][2], int m_w,
   float* st = (float*)st_;                                       // 8704 of the wave's 16384 bytes
   const int l = threadIdx.x & 63, hi = l >> 5, r = l & 31, c16 = l & 15;
   int mo[NI][8];                                               // output row of (block i, flush pass q): row q * 4 + (l >> 4)
-#pragma unroll
-  for (int i = 0; i < NI; i++)
-#pragma unroll
-    for (int q = 0; q < 8; q++) {
-      const int m = m_w + i * 32 + q * 4 + (l >> 4);
-      mo[i][q] = m < p.M ? (p.rowmap ? p.rowmap[m] : m) : -1;
-    }
+  stage_rows<ROWS_MAP_OR_IDENT>(mo, m_w, p.M, l, p.rowmap);
   f32x4 bias[2][4];
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int j = 0; j < 2; j++)
-#pragma unroll
-    for (int g = 0; g < 4; g++) bias[j][g] = zero4;
-  if (p.bias) {
-#pragma unroll
-    for (int j = 0; j < 2; j++)
-#pragma unroll
-      for (int g = 0; g < 4; g++) bias[j][g] = *(const f32x4*)(p.bias + min(n_w + j * 32 + 8 * g + 4 * hi, p.N - 4));
-  }
+  stage_bias(bias, p.bias, n_w, hi, p.N);
   asm volatile("" ::: "memory");                               // side loads stay ahead of the first store (one in-order counter)
   const bool col_ok = n_w + c16 * 4 < p.N;
 #pragma unroll
@@ -700,18 +554,18 @@ TFX_DEV void staged_epilogue_f32(const GemmNT& p, f32x16 (&acc)[NI][2], int m_w,
         f32x4 v;
 #pragma unroll
         for (int e = 0; e < 4; e++) v[e] = acc[i][j][4 * g + e] + bias[j][g][e];
-        *(f32x4*)(st + r * 68 + j * 32 + 8 * g + 4 * hi) = v;
+        *(f32x4*)(st + stage_off_f32(r, j * 32 + 8 * g + 4 * hi)) = v;
       }
     f32x4 v[8];
 #pragma unroll
-    for (int q = 0; q < 8; q++) v[q] = *(const f32x4*)(st + (q * 4 + (l >> 4)) * 68 + c16 * 4);
+    for (int q = 0; q < 8; q++) v[q] = *(const f32x4*)(st + stage_off_f32(q * 4 + (l >> 4), c16 * 4));
 #pragma unroll
     for (int q = 0; q < 8; q++)
       if (col_ok && mo[i][q] >= 0) *(f32x4*)((float*)p.C + (size_t)mo[i][q] * p.ldc + n_w + c16 * 4) = v[q];
   }
 }
 template <int EPI> TFX_DEV bool can_stage(const GemmNT& p) {
-  bool ok = ((p.ldc | p.N) & 7) == 0 && (((uintptr_t)p.C) & 15) == 0;
+  bool ok = ((p.ldc | p.N) & (EPI == EPI_F32 ? 3 : 7)) == 0 && (((uintptr_t)p.C) & 15) == 0;      // rows of 16-byte chunks
   if constexpr (EPI == EPI_GEGLU) ok = ok && (p.ldc2 & 7) == 0 && (((uintptr_t)p.C2) & 15) == 0;
   if constexpr (EPI == EPI_GEGLU_BWD) ok = ok && (p.ldaux & 7) == 0 && (((uintptr_t)p.aux) & 15) == 0 && p.N >= 64;
   if constexpr (EPI == EPI_RESID) ok = ok && (p.ldr & 7) == 0 && (((uintptr_t)p.R) & 15) == 0 && p.N >= 8;
@@ -728,7 +582,7 @@ TFX_DEV void nt_epilogue(const GemmNT& p, f32x16 (&acc)[NI][2], int m_w, int n_w
       return;
     }
   } else if constexpr (EPI == EPI_F32) {
-    if (((p.ldc | p.N) & 3) == 0 && (((uintptr_t)p.C) & 15) == 0) { staged_epilogue_f32<NI>(p, acc, m_w, n_w, st); return; }
+    if (can_stage<EPI>(p)) { staged_epilogue_f32<NI>(p, acc, m_w, n_w, st); return; }
   } else if constexpr (EPI == EPI_GEGLU || EPI == EPI_GEGLU_BWD) {
     if (can_stage<EPI>(p)) { staged_epilogue_geglu<EPI, NI>(p, acc, m_w, n_w, st, gtab, use_tab); return; }
   } else if constexpr (EPI == EPI_RESID) {
