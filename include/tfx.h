@@ -456,6 +456,43 @@ typedef struct {
 int tfx_ce_fwd(const tfx_ce_chunk_args* a, void* stream);
 int tfx_ce_bwd(const tfx_ce_chunk_args* a, void* stream);
 
+/* the cross entropy with its two REGULARISERS: a z-loss on the softmax normaliser (PaLM, Chameleon) and label smoothing.  For a valid row (label y >= 0) with
+ * the launch's V valid columns, logits l_c, lse = log sum_c exp l_c, p_c = exp(l_c - lse), weights z = z_weight >= 0 and e = smoothing in [0, 1):
+ *   row term     r = (1 - e) (lse - l_y) + e (lse - (1/V) sum_c l_c) + z lse^2
+ *   d r / d l_c    = p_c (1 + 2 z lse) - (1 - e) [c == y] - e / V
+ * With e > 0 and z = 0 this is torch.nn.functional.cross_entropy(..., ignore_index = -1, label_smoothing = e).  Ignored rows contribute nothing and get
+ * exact zeros, pad columns V .. ld_d - 1 are exact zeros.  V is the launch's V: whoever narrows it (forward_text: the text tokens) narrows what is smoothed over.
+ * The regularised row sums go where the plain ones go - acc[0] += sum_t r_t, acc[1] += #valid - so every normalisation of the plain loss holds.  `aux`
+ * (two floats, required) receives what the plain loss would have been and the drift monitor: aux[0] += sum_t (lse - l_y), aux[1] += sum_t lse^2.
+ * Entry points, kernel shapes, grid caps, argument rules and return codes are those of tfx_ce_fwd_bwd / tfx_ce_fwd / tfx_ce_bwd; a block issues its (now
+ * four) atomics only when one of its rows is valid.  sum_c l_c is formed only when smoothing > 0.  The backward needs nothing of the forward but lse (and no
+ * `acc` / `aux`).  z_weight < 0, smoothing outside [0, 1) or a non-finite weight: -1 before any launch.  z_weight = smoothing = 0 gives the plain kernels'
+ * d logits to the bit. */
+typedef struct {
+  int32_t T, V; const float* logits; int32_t ld;
+  const int32_t* labels;                      /* -1 = ignore */
+  float grad_scale;
+  tfx_bf16* dlogits; int32_t ld_d;            /* bf16 [T, ld_d], pad columns zeroed */
+  float* acc;                                 /* acc[0] += sum of the regularised row terms, acc[1] += #valid */
+  float z_weight, smoothing;
+  float* aux;                                 /* aux[0] += sum (lse - l_y), aux[1] += sum lse^2 */
+} tfx_ce_reg_args;
+int tfx_ce_reg_fwd_bwd(const tfx_ce_reg_args* a, void* stream);
+
+typedef struct {
+  int32_t T, V; const float* logits; int32_t ld;      /* a chunk: T rows */
+  const int32_t* labels;                              /* -1 = ignore */
+  float* lse;                                         /* [T]; ignored rows get 0 */
+  float* acc;                                         /* as tfx_ce_reg_args (forward) */
+  /* backward */
+  float grad_scale; const float* scale_dev;           /* g *= grad_scale * (scale_dev ? *scale_dev : 1) */
+  tfx_bf16* dlogits; int32_t ld_d;                    /* pad columns V..ld_d-1 and ignored rows zeroed */
+  float z_weight, smoothing;
+  float* aux;                                         /* as tfx_ce_reg_args (forward) */
+} tfx_ce_reg_chunk_args;
+int tfx_ce_reg_fwd(const tfx_ce_reg_chunk_args* a, void* stream);
+int tfx_ce_reg_bwd(const tfx_ce_reg_chunk_args* a, void* stream);
+
 /* fused MSE forward + backward: pred/flow fp32 [R, dl]   T:3359-3362 */
 typedef struct {
   int32_t R, dl; const float* pred; int32_t ld_pred; const float* flow;
@@ -853,6 +890,8 @@ enum { TFX_OP_GEMM_NT = 0, TFX_OP_GEMM_TN = 1, TFX_OP_ATTN_FWD = 2, TFX_OP_ATTN_
        TFX_OP_SILU_BWD = 37, TFX_OP_COLSUM_BF16 = 38, TFX_OP_COLSUM_F32 = 39, TFX_OP_ADD_BF16 = 40, TFX_OP_SCALE_BF16_DEV = 41, TFX_OP_CAST_BLOCK_BF16 = 42, TFX_OP_SCALE_BF16_COPY = 43, TFX_OP_ADALN_POST_PRE_FWD = 44, TFX_OP_LAYER_END_FWD = 45,
        TFX_OP_ATTNRES_PREP = 46, TFX_OP_ATTNRES_PULL_BWD = 47, TFX_OP_ATTNRES_FINISH = 52, TFX_OP_ADALN_PRE_POST_BWD = 53,
        TFX_OP_CE_BWD = 54,                      /* (args = tfx_ce_chunk_args, as TFX_OP_CE_FWD: the struct codes below 32 are used up) */
+       TFX_OP_CE_REG_FWD_BWD = 55,              /* (args = tfx_ce_reg_args) */
+       TFX_OP_CE_REG_FWD = 56, TFX_OP_CE_REG_BWD = 57,      /* (args = tfx_ce_reg_chunk_args) */
        /* stream control (args = any non-NULL pointer; `stream` = event slot 0..63):
           FORK: the library's side stream waits for everything enqueued so far on the caller's stream;
           JOIN_RECORD: mark "everything enqueued so far on the side stream";  JOIN_WAIT: the caller's stream waits for that mark;

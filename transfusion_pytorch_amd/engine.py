@@ -235,7 +235,7 @@ class _BwdBuild:
 
 class Plan:
     def __init__(self, ps: ParamStore, b: int, n: int, I: int, R: dict, training: bool = True, cache=None, dp_groups: int = 0, tile_attn: bool = False, units=None, ctl_rows: int = 2, tn_defer=None, ckpt: bool = False,
-                 chunk_rows=None):
+                 chunk_rows=None, text_terms=None):
         """cache: None, or a KV cache tensor [depth, b, maxlen, 2*heads*64] (k~ | v per token).  With a cache the plan is a
         DECODE step: each layer appends this step's k~ / v rows at `cache_pos` (flat row b*maxlen + position, -1 = skip) and
         attention reads keys / values from the cache (per-token visible length in `kv_end`).
@@ -247,13 +247,17 @@ class Plan:
         chunk_rows: CHUNKED TEXT HEAD (training plans; Transfusion.set_text_head_chunking_): the logits and their gradient exist for `chunk_rows` token rows
         at a time - `logits_c`, `dlogits_c` - instead of for all T (`logits`, `dlogits`: not allocated).  The forward runs the logits product and tfx_ce_fwd
         chunk by chunk and keeps one float per row (`ce_lse`); the backward runs the same product again, tfx_ce_bwd and the head's two gradient products per
-        chunk (_bwd_text_chunks).  The upstream gradient of the loss reaches tfx_ce_bwd through the device scalar `go_dev`."""
+        chunk (_bwd_text_chunks).  The upstream gradient of the loss reaches tfx_ce_bwd through the device scalar `go_dev`.
+        text_terms: (z-loss weight, label smoothing) of the TEXT LOSS TERMS (training plans; Transfusion.set_text_loss_terms_).  With a non-zero weight every
+        cross-entropy launch of the plan is its `_reg` form (tfx.h tfx_ce_reg_args) and the plan owns `aux`, two floats behind `acc` - the plain CE sum and
+        the sum of lse^2 - zeroed with it (zero_acc).  (0, 0) and None build the plain plan, launch for launch."""
         md = ps.md
         self.training = training
         self.ckpt = bool(ckpt) and training
         self.chunk = min(int(chunk_rows), max(b * n, 1)) if (chunk_rows and training) else None      # rows per chunk of the text head (None: the whole head at once)
         # the side stream's weight-gradient GEMMs read a layer's saved activations one layer behind the data-gradient chain: two slots by layer parity
         # there, one on a single stream
+        self.reg = (float(text_terms[0]), float(text_terms[1])) if (training and text_terms and (text_terms[0] or text_terms[1])) else None
         self.n_slots = (2 if self._side_stream(md) else 1) if self.ckpt else None
         self.units = units
         assert not units or (cache is not None and tile_attn), 'compacted plans are decode plans on the tiled attention kernel (the row ranges are its arguments)'
@@ -371,7 +375,10 @@ class Plan:
                                flow=e(r, dl, dtype=torch.float32), pred=e(r, dl, dtype=torch.float32), dpred=z(r, dlp))
         for t in self.ext_add:
             self.lat[t]['add'] = z(R[t], d)      # additive token rows: the axial positional embedding (T:1384-1403, T:3173-3176), bf16
-        self.acc = z(max(8, 2 + 3 * len(md.dim_latents)), dtype=torch.float32)      # [ce sum, ce count, flow sse per type..., velocity sse per type..., weighted recon sse per type...]
+        self.acc = z(max(8, 2 + 3 * len(md.dim_latents)) + (2 if self.reg else 0), dtype=torch.float32)      # [ce sum, ce count, flow sse per type..., velocity sse per type..., weighted recon sse per type...]
+        self._acc_all, self.aux = self.acc, None
+        if self.reg:                          # text loss terms: [plain ce sum, sum of lse^2] ride behind the accumulators - one buffer, one memset
+            self.acc, self.aux = self._acc_all[:-2], self._acc_all[-2:]
         # per layer: the soft-cap plan tfx_qk_norm_rope_fwd derives from the layer's QK-RMSNorm gains (tfx.h) and its attention kernels - forward
         # and, later, backward - read: polynomial degree and coefficients from the BOUND on the scores, no look at the data.
         # Without QK-RMSNorm (md.qk_norm False) nothing bounds the scores: no plan, the attention kernels take their data-dependent form
@@ -628,7 +635,7 @@ class Plan:
         if self.chunk:
             for r0, m in self._chunks():                  # per chunk: its logits, then their cross entropy - nothing of the chunk outlives it but `ce_lse`
                 self._chunk_logits(L, r0, m)
-                L.append(('tfx_ce_fwd', self._ce_chunk_args(L, r0, m)))
+                L.append((self._ce_fn('tfx_ce_fwd'), self._ce_chunk_args(L, r0, m)))
                 self._hbm(L, extra_bytes=m * (md.vp * 4 + 4))              # fp32 logits in, lse out
         else:
             self._nt(L, A=self.embed, lda=d, B=S['logits'], ldb=d, M=T, N=md.vp, K=d, algo_n=md.vocab, epi=E['TFX_EPI_F32'], C=self.logits, ldc=md.vp)   # zero pad rows: N % 4 == 0 keeps the LDS-DMA kernel
@@ -646,9 +653,9 @@ class Plan:
             self._chain_weight_prefetch(L)
             return
         if not self.chunk:
-            self._ce_args = capi.make_args('tfx_ce_args', T=T, V=md.vocab, logits=self.logits, ld=md.vp, labels=self.labels, grad_scale=0.0,
-                                           dlogits=self.dlogits, ld_d=md.vp, acc=self.acc)
-            L.append(('tfx_ce_fwd_bwd', self._ce_args))
+            self._ce_args = capi.make_args(self._ce_fn('tfx_ce_args'), T=T, V=md.vocab, logits=self.logits, ld=md.vp, labels=self.labels, grad_scale=0.0,
+                                           dlogits=self.dlogits, ld_d=md.vp, acc=self.acc, **self._ce_terms())
+            L.append((self._ce_fn('tfx_ce_fwd_bwd'), self._ce_args))
             self._hbm(L, extra_bytes=T * md.vp * (4 + 2))                        # fp32 logits in, bf16 d logits out
         nm = len(md.dim_latents)
         for t, r in native.items():
@@ -673,11 +680,23 @@ class Plan:
         md, d = self.md, self.md.dim
         self._nt(lst, A=self.embed[r0:], lda=d, B=self.ps.shadows['logits'], ldb=d, M=m, N=md.vp, K=d, algo_n=md.vocab, epi=E['TFX_EPI_F32'], C=self.logits_c, ldc=md.vp)
 
+    def _ce_fn(self, name):
+        """a cross-entropy entry point or args struct by its plain name: with text loss terms (`reg`) its `_reg` form, tfx_ce_fwd -> tfx_ce_reg_fwd"""
+        return name.replace('tfx_ce_', 'tfx_ce_reg_') if self.reg else name
+
+    def _ce_terms(self):
+        """the fields a `_reg` args struct has beyond the plain one ({} without text loss terms)"""
+        return dict(z_weight=self.reg[0], smoothing=self.reg[1], aux=self.aux) if self.reg else {}
+
+    def zero_acc(self):
+        """zero the step's accumulators (`acc`, and `aux` behind it)"""
+        self._acc_all.zero_()
+
     def _ce_chunk_args(self, lst, r0, m):
         """tfx_ce_chunk_args of rows r0 .. r0 + m, owned by `lst` and registered with it for the per-step setters (set_ce_vocab, set_loss_scales)"""
         md = self.md
-        a = capi.make_args('tfx_ce_chunk_args', T=m, V=md.vocab, logits=self.logits_c, ld=md.vp, labels=self.labels[r0:], lse=self.ce_lse[r0:], acc=self.acc,
-                           grad_scale=0.0, scale_dev=self.go_dev, dlogits=self.dlogits_c, ld_d=md.vp)
+        a = capi.make_args(self._ce_fn('tfx_ce_chunk_args'), T=m, V=md.vocab, logits=self.logits_c, ld=md.vp, labels=self.labels[r0:], lse=self.ce_lse[r0:], acc=self.acc,
+                           grad_scale=0.0, scale_dev=self.go_dev, dlogits=self.dlogits_c, ld_d=md.vp, **self._ce_terms())
         lst.patched('ce', a)
         return a
 
@@ -1017,7 +1036,7 @@ class Plan:
         md, d, S, L = self.md, self.md.dim, self.ps.shadows, self.bwd
         for r0, m in self._chunks():
             self._chunk_logits(L, r0, m)
-            L.append(('tfx_ce_bwd', self._ce_chunk_args(L, r0, m)))
+            L.append((self._ce_fn('tfx_ce_bwd'), self._ce_chunk_args(L, r0, m)))
             self._hbm(L, extra_bytes=m * (md.vp * (4 + 2) + 4))                # fp32 logits and lse in, bf16 d logits out
             if c.tr('to_text_logits.weight'):
                 self._tn(L, m, md.vocab, d, A=self.dlogits_c, lda=md.vp, a_cols=md.vp, B=self.embed[r0:], ldb=d, b_cols=d, C=self.ps.grad_ptr('to_text_logits.weight'), ldc=d)

@@ -9,7 +9,9 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import math
 import os
+import weakref
 from typing import NamedTuple
 
 import numpy as np
@@ -23,6 +25,12 @@ from .ode import check_odeint_kwargs
 from .packing import fast_signature, is_int_tensor, scan_batch, scan_signature, token_maps, token_segments
 from .axial import ContinuousAxialPositionalEmbedding
 from .params import ModelDims, ParamStore
+
+
+class TextLossTerms(NamedTuple):            # Transfusion.text_loss_terms()
+    text: torch.Tensor
+    ce: torch.Tensor
+    lse_sq: torch.Tensor
 
 
 class LossBreakdown(NamedTuple):            # T:105-110
@@ -414,6 +422,8 @@ class Transfusion(nn.Module):
         self._plans = {}
         self._ckpt = False                   # activation checkpointing (set_activation_checkpointing_): part of the plan key
         self._chunk = None                   # rows per chunk of the text head (set_text_head_chunking_; None = off): part of the plan key
+        self._text_terms = (0.0, 0.0)        # (z-loss weight, label smoothing) of the text loss (set_text_loss_terms_): part of the plan key
+        self._text_terms_plan = None         # the plan of the last training step that ran with the terms on (text_loss_terms)
         self._struct_cache = {}
         self._decode_plans = {}              # decode plans of the cached forward calls and of the sampler (sampling.Sampler._decode_plan)
         self._flat_pred_flows = False        # set by `_teacher_pass` around a teacher's forward
@@ -490,7 +500,7 @@ class Transfusion(nn.Module):
             new = new.to(self.device)
         new.load_state_dict(self.state_dict())
         new.train(self.training)
-        new._ckpt, new._chunk = self._ckpt, self._chunk
+        new._ckpt, new._chunk, new._text_terms = self._ckpt, self._chunk, self._text_terms
         memo[id(self)] = new
         return new
 
@@ -691,6 +701,52 @@ class Transfusion(nn.Module):
         self._chunk = rows
         return self
 
+    @property
+    def text_z_loss_weight(self) -> float:
+        return self._text_terms[0]
+
+    @property
+    def text_label_smoothing(self) -> float:
+        return self._text_terms[1]
+
+    def set_text_loss_terms_(self, z_loss=0., label_smoothing=0.):
+        """the two standard regularisers of the text head's cross entropy, formed inside the native loss kernels (include/tfx.h tfx_ce_reg_args): per
+        valid text row, with lse = log sum_c exp(logit_c) over the V columns the loss runs over,
+            (1 - label_smoothing) (lse - logit_label) + label_smoothing (lse - mean_c logit_c) + z_loss lse^2
+        `z_loss` >= 0 is the z-loss of PaLM (1e-4) and Chameleon (1e-5): it holds the softmax normaliser near 1, which keeps the logits of an early-fusion model
+        from drifting.  0 <= `label_smoothing` < 1 is torch.nn.functional.cross_entropy's `label_smoothing`.  V is the whole vocabulary in `forward(...,
+        return_loss=True)` and the text tokens in `forward_text(return_loss=True)`; rows are normalised as the plain loss is, so `loss`, `LossBreakdown.text`
+        and forward_text's mean carry the terms.  Takes effect at the next training forward of those two calls; the pair is part of the plan key, and (0, 0) -
+        the default - runs the plain kernels, launch for launch.  Inference, decode, sampling and `forward_modality` never look at it.  The setting is copied
+        by create_ema() / copy.deepcopy and is not saved in `state_dict`.  Returns self."""
+        vals = []
+        for name, v in (('z_loss', z_loss), ('label_smoothing', label_smoothing)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)):
+                raise TypeError(f'set_text_loss_terms_: {name} takes a number, got {type(v).__name__}')
+            v = float(v)
+            if not math.isfinite(v):
+                raise ValueError(f'set_text_loss_terms_: {name} must be finite, got {v}')
+            vals.append(v)
+        z, e = vals
+        if z < 0.:
+            raise ValueError(f'set_text_loss_terms_: z_loss must be >= 0, got {z}')
+        if not 0. <= e < 1.:
+            raise ValueError(f'set_text_loss_terms_: label_smoothing must lie in [0, 1), got {e}')
+        self._text_terms = (z, e)
+        if not any(self._text_terms):
+            self._text_terms_plan = None
+        return self
+
+    def text_loss_terms(self):
+        """the text loss of the last training step (`forward(..., return_loss=True)` or `forward_text(return_loss=True)`) by its parts, device scalars:
+        `text` - the regularised mean, `LossBreakdown.text`; `ce` - the plain mean cross entropy (what perplexity is computed from); `lse_sq` - the mean of
+        lse^2, the quantity the z-loss penalises (a drift monitor).  None when the terms are off (set_text_loss_terms_)."""
+        plan = self._text_terms_plan() if self._text_terms_plan is not None else None
+        if plan is None or not any(self._text_terms):
+            return None
+        cnt = plan.acc[1].clamp(min=1.)
+        return TextLossTerms(plan.acc[0] / cnt, plan.aux[0] / cnt, plan.aux[1] / cnt)
+
     def _require_gpu(self):
         if self.device.type != 'cuda':
             raise capi.TfxError('the Transfusion hot path only runs on an MI355X (model.cuda()); there is no CPU fallback')
@@ -711,18 +767,21 @@ class Transfusion(nn.Module):
         dp_groups = getattr(self, '_dp_groups', 0) if training else 0
         ckpt = training and self._ckpt                              # inference, decode, sampling and hiddens-only plans never look at the switch
         chunk = self._chunk if (training and text_loss) else None   # ... nor at this one; forward_modality's training plans neither (no text loss)
-        key = (b, n, I, tuple(sorted(R.items())), training, dp_groups, ckpt, chunk)
+        terms = self._text_terms if (training and text_loss and any(self._text_terms)) else None      # ... nor at the text loss terms
+        key = (b, n, I, tuple(sorted(R.items())), training, dp_groups, ckpt, chunk, terms)
         plan = self._plans.pop(key, None)
         if plan is None:
             while len(self._plans) >= 8:                             # least recently used plan goes first (dict order = use order)
                 self._plans.pop(next(iter(self._plans)))
-            plan = Plan(self.store, b, n, I, R, training=training, dp_groups=dp_groups, ckpt=ckpt, **({'chunk_rows': chunk} if chunk else {}))
+            plan = Plan(self.store, b, n, I, R, training=training, dp_groups=dp_groups, ckpt=ckpt, **({'chunk_rows': chunk} if chunk else {}), **({'text_terms': terms} if terms else {}))
             # a plan owns every activation of its step (tens of GB for a training plan at dim 1024 / depth 24): besides the count, the cache is
             # bounded by bytes - TFX_PLAN_BUDGET_GB, default 40 % of the device memory - oldest first, the new plan always stays
             budget = float(os.environ.get('TFX_PLAN_BUDGET_GB', 0)) * 2 ** 30 or 0.4 * torch.cuda.get_device_properties(self.device).total_memory
             while self._plans and sum(p.nbytes for p in self._plans.values()) + plan.nbytes > budget:
                 self._plans.pop(next(iter(self._plans)))
         self._plans[key] = plan                                      # (re-)insert at the most recent position
+        if training and text_loss:
+            self._text_terms_plan = weakref.ref(plan) if terms else None      # (weak: the plan cache alone decides how long a plan lives)
         if training:
             # `p.requires_grad_(False)` on native parameters: the backward list of the current frozen set (built on first use, a few kept per plan)
             # (and the LoRA adapters that train: their gradient launches stand in that list)
@@ -1096,7 +1155,7 @@ class Transfusion(nn.Module):
         plan.set_loss_scales(self.text_loss_weight / total, {t: 2.0 * self.flow_loss_weight * w[t] / den[t] for t in native})
         plan.set_ce_vocab(md.vocab)
         self._bwd_scale = None
-        plan.acc.zero_()
+        plan.zero_acc()
         Plan.run(plan.fwd, stream, graph='auto')
 
         text_loss = acc[0] / acc[1].clamp(min=1.)
@@ -1432,7 +1491,7 @@ class Transfusion(nn.Module):
         plan.labels.copy_(torch.where(lab == self.ignore_index, torch.full_like(lab, -1), lab))
         plan.set_loss_scales(1.0, {})                        # mean over the valid labels: the count lives on the device (see _bwd_scale)
         plan.set_ce_vocab(self.num_text_tokens)              # text_only_logits_mask (T:2653)
-        plan.acc.zero_()
+        plan.zero_acc()
         Plan.run(plan.fwd, stream)
         cnt = plan.acc[1].clamp(min=1.)
         loss = plan.acc[0] / cnt                             # T:2655-2659
@@ -1551,7 +1610,7 @@ class Transfusion(nn.Module):
         plan.set_loss_scales(0.0, {} if ext else {t: 2.0 / (rows * dl)})
         plan.set_ce_vocab(md.vocab)
         self._bwd_scale = None
-        plan.acc.zero_()
+        plan.zero_acc()
         Plan.run(plan.fwd, stream, graph='auto')
         flow_loss = torch.zeros((), device=dev) if ext else plan.acc[2 + t] / (rows * dl)   # T:2817
         loss = flow_loss
@@ -1904,6 +1963,7 @@ class Transfusion(nn.Module):
         m = Transfusion(**kw)
         m._ckpt = self._ckpt                 # (create_ema / EMA: harmless there - a teacher's passes run without gradient, on inference plans)
         m._chunk = self._chunk
+        m._text_terms = self._text_terms
         return m.to(self.device) if self.device.type == 'cuda' else m
 
     def create_dataloader(self, *args, **kwargs):                   # T:1676-1679
