@@ -493,6 +493,42 @@ typedef struct {
 int tfx_ce_reg_fwd(const tfx_ce_reg_chunk_args* a, void* stream);
 int tfx_ce_reg_bwd(const tfx_ce_reg_chunk_args* a, void* stream);
 
+/* the regularised cross entropy with one LOSS WEIGHT PER ROW (per-token loss weights: which tokens of a packed sample are trained on, and how strongly).
+ * The structs are the `_reg` ones plus `row_w`, [T] floats >= 0 (required; the host refuses negative and non-finite weights).  With w = row_w[t]:
+ *   a row with label < 0 or w == 0 is ignored: its logits are not read, its d logits are exact zeros, the chunk forward writes lse = 0;
+ *   any other row adds  acc[0] += w r,  acc[1] += w,  aux[0] += w (lse - l_y),  aux[1] += w lse^2   (r: the row term of tfx_ce_reg_args),
+ *   and gets  d logits = (d r / d l_c) s  with  s = grad_scale w [* *scale_dev]  formed once per row, in that order.
+ * So acc[0] / acc[1] is the weighted mean torch.nn.functional.cross_entropy(weight = ...) normalises to, w = 1.0f gives tfx_ce_reg_*'s d logits and lse to
+ * the bit, and weights in {0, 1} give what those kernels give with the zero-weight labels set to -1.  Entry points, kernel shapes, width classes, grid caps,
+ * argument rules and return codes are those of tfx_ce_reg_*; z_weight = smoothing = 0 is allowed (the plain weighted cross entropy); a block issues its
+ * atomics only when one of its rows counts.  NULL row_w: -1 before any launch. */
+typedef struct {
+  int32_t T, V; const float* logits; int32_t ld;
+  const int32_t* labels;                      /* -1 = ignore */
+  float grad_scale;
+  tfx_bf16* dlogits; int32_t ld_d;            /* bf16 [T, ld_d], pad columns zeroed */
+  float* acc;                                 /* acc[0] += sum w r, acc[1] += sum w */
+  float z_weight, smoothing;
+  float* aux;                                 /* aux[0] += sum w (lse - l_y), aux[1] += sum w lse^2 */
+  const float* row_w;                         /* [T] */
+} tfx_ce_w_args;
+int tfx_ce_w_fwd_bwd(const tfx_ce_w_args* a, void* stream);
+
+typedef struct {
+  int32_t T, V; const float* logits; int32_t ld;      /* a chunk: T rows */
+  const int32_t* labels;                              /* -1 = ignore */
+  float* lse;                                         /* [T]; ignored rows get 0 */
+  float* acc;                                         /* as tfx_ce_w_args (forward) */
+  /* backward */
+  float grad_scale; const float* scale_dev;           /* g *= grad_scale * row_w[t] * (scale_dev ? *scale_dev : 1) */
+  tfx_bf16* dlogits; int32_t ld_d;                    /* pad columns V..ld_d-1 and ignored rows zeroed */
+  float z_weight, smoothing;
+  float* aux;                                         /* as tfx_ce_w_args (forward) */
+  const float* row_w;                                 /* [T], both directions */
+} tfx_ce_w_chunk_args;
+int tfx_ce_w_fwd(const tfx_ce_w_chunk_args* a, void* stream);
+int tfx_ce_w_bwd(const tfx_ce_w_chunk_args* a, void* stream);
+
 /* fused MSE forward + backward: pred/flow fp32 [R, dl]   T:3359-3362 */
 typedef struct {
   int32_t R, dl; const float* pred; int32_t ld_pred; const float* flow;
@@ -513,6 +549,19 @@ typedef struct {
   const float* recon_w; const int32_t* recon_inst; const float* recon_time; int32_t recon_mode;
 } tfx_mse_args;
 int tfx_mse_fwd_bwd(const tfx_mse_args* a, void* stream);
+/* the same squared error with one LOSS WEIGHT PER ROW (row_w, [R] floats >= 0, required: NULL returns -1 before any launch) and without the
+ * reconstruction form:  acc[0] += sum_r w_r sum_c err^2,  dpred (+)= grad_scale w_r err (clean factor).  A row with w_r == 0 is not read and writes exact
+ * zeros (with `accumulate` it adds nothing); w_r = 1.0f gives tfx_mse_fwd_bwd's dpred to the bit.  The other fields are tfx_mse_args'. */
+typedef struct {
+  int32_t R, dl; const float* pred; int32_t ld_pred; const float* flow;
+  float grad_scale;
+  tfx_bf16* dpred; int32_t ld_d;
+  float* acc;
+  int32_t accumulate;
+  const int32_t* row_inst; const float* inst_time; float clean_eps;
+  const float* row_w;                         /* [R] */
+} tfx_mse_w_args;
+int tfx_mse_w_fwd_bwd(const tfx_mse_w_args* a, void* stream);
 /* fused cosine loss forward + backward over bf16 rows (the Self-Flow representation loss, default_rep_loss_fn: 1 - cosine_similarity(pred, target, -1).mean()):
  *   c_t = <x_t, y_t> / (max(|x_t|, 1e-8) max(|y_t|, 1e-8)),   acc[0] += sum of c_t over the rows that count (the host forms 1 - acc / N),
  *   dpred_t = -grad_scale (y_t / (|x_t| |y_t|) - c_t x_t / |x_t|^2)   in bf16, zero for the rows that do not count.
@@ -892,6 +941,9 @@ enum { TFX_OP_GEMM_NT = 0, TFX_OP_GEMM_TN = 1, TFX_OP_ATTN_FWD = 2, TFX_OP_ATTN_
        TFX_OP_CE_BWD = 54,                      /* (args = tfx_ce_chunk_args, as TFX_OP_CE_FWD: the struct codes below 32 are used up) */
        TFX_OP_CE_REG_FWD_BWD = 55,              /* (args = tfx_ce_reg_args) */
        TFX_OP_CE_REG_FWD = 56, TFX_OP_CE_REG_BWD = 57,      /* (args = tfx_ce_reg_chunk_args) */
+       TFX_OP_CE_W_FWD_BWD = 58,                /* (args = tfx_ce_w_args) */
+       TFX_OP_CE_W_FWD = 59, TFX_OP_CE_W_BWD = 60,          /* (args = tfx_ce_w_chunk_args) */
+       TFX_OP_MSE_W_FWD_BWD = 61,               /* (args = tfx_mse_w_args) */
        /* stream control (args = any non-NULL pointer; `stream` = event slot 0..63):
           FORK: the library's side stream waits for everything enqueued so far on the caller's stream;
           JOIN_RECORD: mark "everything enqueued so far on the side stream";  JOIN_WAIT: the caller's stream waits for that mark;

@@ -1946,6 +1946,181 @@ __global__ __launch_bounds__(256) void ce_reg_chunk_bwd_k(tfx_ce_reg_chunk_args 
   }
 }
 
+// ---- the regularised cross entropy with a loss weight per row (tfx.h tfx_ce_w_args / tfx_ce_w_chunk_args): the three `_reg` kernels with one more 4-byte
+// load per row.  A row whose weight is 0 is an ignored row (label -1 from there on); a row that counts adds w times what ce_reg_row adds, and its gradient
+// scale is s = grad_scale w [* *scale_dev], formed once per row - with w = 1.0f every product below has the `_reg` kernels' bits.
+
+TFX_DEV void ce_w_row(float w, float lse, float ly, float sl, float z, float e, float inv_v, float (&sum)[4]) {
+  const float ce = lse - ly, sq = lse * lse;
+  float r = ce;
+  if (e > 0.f) r = (1.f - e) * ce + e * (lse - sl * inv_v);
+  sum[0] += w * (r + z * sq); sum[1] += w; sum[2] += w * ce; sum[3] += w * sq;
+}
+
+__global__ __launch_bounds__(256) void ce_w_k(tfx_ce_w_args p) {
+  __shared__ float sacc[4][WAVES];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const float z = p.z_weight, sm = p.smoothing, inv_v = 1.f / (float)p.V, oh = 1.f - sm, ev = sm * inv_v;
+  float sum[4] = {0.f, 0.f, 0.f, 0.f};
+  const bool fast = p.ld <= 512 && p.ld_d <= 512 && (p.ld & 3) == 0 && (p.ld_d & 3) == 0 && (((uintptr_t)p.logits) & 15) == 0 && (((uintptr_t)p.dlogits) & 7) == 0;
+  if (fast) {
+    for (int t = blockIdx.x * WAVES + w; t < p.T; t += gridDim.x * WAVES) {
+      const float rw = p.row_w[t];
+      const int lab = rw == 0.f ? -1 : p.labels[t];
+      const float gs = p.grad_scale * rw;
+      const float* lg = p.logits + (size_t)t * p.ld;
+      bf16* dl = p.dlogits + (size_t)t * p.ld_d;
+      f32x4 v[2];
+      float mx = -INFINITY;
+#pragma unroll
+      for (int k = 0; k < 2; k++) {
+        const int c = k * 256 + lane * 4;
+        const f32x4 ninf = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+        v[k] = ninf;
+        if (lab >= 0 && c < p.ld) v[k] = *(const f32x4*)(lg + c);
+#pragma unroll
+        for (int e = 0; e < 4; e++) { if (c + e >= p.V) v[k][e] = -INFINITY; mx = fmaxf(mx, v[k][e]); }
+      }
+      float lse = 0.f, kf = 1.f;
+      if (lab >= 0) {
+        mx = wave_max(mx);
+        float se = 0.f, sl = 0.f;
+#pragma unroll
+        for (int k = 0; k < 2; k++)
+#pragma unroll
+          for (int e = 0; e < 4; e++) se += __expf(v[k][e] - mx);
+        se = wave_sum(se);
+        if (sm > 0.f) {
+#pragma unroll
+          for (int k = 0; k < 2; k++)
+#pragma unroll
+            for (int e = 0; e < 4; e++) sl += k * 256 + lane * 4 + e < p.V ? v[k][e] : 0.f;
+          sl = wave_sum(sl);
+        }
+        lse = mx + __logf(se);
+        kf = 1.f + 2.f * z * lse;
+        ce_w_row(rw, lse, lg[lab], sl, z, sm, inv_v, sum);
+      }
+#pragma unroll
+      for (int k = 0; k < 2; k++) {
+        const int c = k * 256 + lane * 4;
+        if (c < p.ld_d) {
+          bf16x4 o;
+#pragma unroll
+          for (int e = 0; e < 4; e++) {
+            float g = 0.f;
+            if (lab >= 0 && c + e < p.V) g = (__expf(v[k][e] - lse) * kf - (c + e == lab ? oh : 0.f) - ev) * gs;
+            o[e] = f2bf(g);
+          }
+          *(bf16x4*)(dl + c) = o;
+        }
+      }
+    }
+  } else
+  for (int t = blockIdx.x * WAVES + w; t < p.T; t += gridDim.x * WAVES) {
+    const float rw = p.row_w[t];
+    const int lab = rw == 0.f ? -1 : p.labels[t];
+    const float gs = p.grad_scale * rw;
+    const float* lg = p.logits + (size_t)t * p.ld;
+    bf16* dl = p.dlogits + (size_t)t * p.ld_d;
+    if (lab < 0) {
+      for (int c = lane; c < p.ld_d; c += 64) dl[c] = f2bf(0.f);
+      continue;
+    }
+    float mx = -INFINITY, sl = 0.f;
+    if (sm > 0.f) { for (int c = lane; c < p.V; c += 64) { const float x = lg[c]; mx = fmaxf(mx, x); sl += x; } sl = wave_sum(sl); }
+    else for (int c = lane; c < p.V; c += 64) mx = fmaxf(mx, lg[c]);
+    mx = wave_max(mx);
+    float se = 0.f;
+    for (int c = lane; c < p.V; c += 64) se += __expf(lg[c] - mx);
+    se = wave_sum(se);
+    const float lse = mx + __logf(se), kf = 1.f + 2.f * z * lse;
+    for (int c = lane; c < p.ld_d; c += 64) {
+      float g = 0.f;
+      if (c < p.V) g = (__expf(lg[c] - lse) * kf - (c == lab ? oh : 0.f) - ev) * gs;
+      dl[c] = f2bf(g);
+    }
+    ce_w_row(rw, lse, lg[lab], sl, z, sm, inv_v, sum);
+  }
+  ce_reg_flush(sum, sacc, p.acc, p.aux);          // (sum[1] = the block's weight: positive exactly when one of its rows counts)
+}
+
+template <bool WIDE>
+__global__ __launch_bounds__(256) void ce_w_chunk_fwd_k(tfx_ce_w_chunk_args p) {
+  __shared__ float sacc[4][WAVES];
+  __shared__ float spair[2][3][WAVES];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int q0 = WIDE ? threadIdx.x : lane, qs = WIDE ? 256 : 64;
+  const int nq = (p.V + 3) >> 2;
+  const float z = p.z_weight, sm = p.smoothing, inv_v = 1.f / (float)p.V;
+  float sum[4] = {0.f, 0.f, 0.f, 0.f};
+  int par = 0;
+  for (int t = WIDE ? blockIdx.x : blockIdx.x * WAVES + w; t < p.T; t += WIDE ? gridDim.x : gridDim.x * WAVES) {
+    const float rw = p.row_w[t];                                // (like the label uniform over the row's waves: an ignored row skips the barrier as a block)
+    const int lab = rw == 0.f ? -1 : p.labels[t];
+    if (lab < 0) { if (q0 == 0) p.lse[t] = 0.f; continue; }
+    const float* lg = p.logits + (size_t)t * p.ld;
+    float m = -INFINITY, s = 0.f, sl = 0.f;
+    if (sm > 0.f) {
+#pragma unroll 4
+      for (int q = q0; q < nq; q += qs) ce_online4_sum(*(const f32x4*)(lg + 4 * q), 4 * q, p.V, m, s, sl);
+      sl = wave_sum(sl);
+    } else {
+#pragma unroll 4
+      for (int q = q0; q < nq; q += qs) ce_online4(*(const f32x4*)(lg + 4 * q), 4 * q, p.V, m, s);
+    }
+    float M = wave_max(m);
+    float S = wave_sum(m == -INFINITY ? 0.f : s * __expf(m - M));
+    if (WIDE) {
+      if (lane == 0) { spair[par][0][w] = M; spair[par][1][w] = S; spair[par][2][w] = sl; }
+      __syncthreads();
+      float mm = spair[par][0][0];
+#pragma unroll
+      for (int i = 1; i < WAVES; i++) mm = fmaxf(mm, spair[par][0][i]);
+      float ss = 0.f, tl = 0.f;
+#pragma unroll
+      for (int i = 0; i < WAVES; i++) { ss += spair[par][1][i] * __expf(spair[par][0][i] - mm); tl += spair[par][2][i]; }
+      M = mm; S = ss; sl = tl; par ^= 1;
+    }
+    if (q0 == 0) {
+      const float lse = M + __logf(S);
+      p.lse[t] = lse;
+      ce_w_row(rw, lse, lg[lab], sl, z, sm, inv_v, sum);
+    }
+  }
+  ce_reg_flush(sum, sacc, p.acc, p.aux);
+}
+
+template <bool WIDE>
+__global__ __launch_bounds__(256) void ce_w_chunk_bwd_k(tfx_ce_w_chunk_args p) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int c0 = (WIDE ? threadIdx.x : lane) * 8, cs = WIDE ? 2048 : 512;
+  const float sd = p.scale_dev ? *p.scale_dev : 1.f;
+  const float oh = 1.f - p.smoothing, ev = p.smoothing * (1.f / (float)p.V), z2 = 2.f * p.z_weight;
+  for (int t = WIDE ? blockIdx.x : blockIdx.x * WAVES + w; t < p.T; t += WIDE ? gridDim.x : gridDim.x * WAVES) {
+    const float rw = p.row_w[t];
+    const int lab = rw == 0.f ? -1 : p.labels[t];
+    const float sc = p.grad_scale * rw * sd;
+    const float lse = p.lse[t], kf = 1.f + z2 * lse;
+    const float* lg = p.logits + (size_t)t * p.ld;
+    bf16* dl = p.dlogits + (size_t)t * p.ld_d;
+    for (int c = c0; c < p.ld_d; c += cs) {
+      bf16x8 o;
+#pragma unroll
+      for (int e = 0; e < 8; e++) o[e] = f2bf(0.f);
+      if (lab >= 0 && c < p.V) {
+        const f32x4 a = *(const f32x4*)(lg + c), b = *(const f32x4*)(lg + c + 4);
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+          const float x = e < 4 ? a[e & 3] : b[e & 3];
+          if (c + e < p.V) o[e] = f2bf((__expf(x - lse) * kf - (c + e == lab ? oh : 0.f) - ev) * sc);
+        }
+      }
+      *(bf16x8*)(dl + c) = o;
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void mse_k(tfx_mse_args p) {
   __shared__ float sacc[WAVES];
   const long long n = (long long)p.R * p.ld_d;
@@ -1977,6 +2152,28 @@ __global__ __launch_bounds__(256) void mse_k(tfx_mse_args p) {
   if ((threadIdx.x & 63) == 0) sacc[threadIdx.x >> 6] = s;
   __syncthreads();
   if (threadIdx.x == 0) { float a = 0.f; for (int i = 0; i < WAVES; i++) a += sacc[i]; atomicAdd(p.acc, a); }
+}
+
+// mse_k's plain branch with a loss weight per row (tfx.h tfx_mse_w_args): a row of weight 0 is not read; w = 1.0f leaves df * (grad_scale * 1) = mse_k's bits
+__global__ __launch_bounds__(256) void mse_w_k(tfx_mse_w_args p) {
+  __shared__ float sacc[WAVES];
+  const long long n = (long long)p.R * p.ld_d;
+  float s = 0.f;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    const int r = (int)(i / p.ld_d), c = (int)(i % p.ld_d);
+    const float w = p.row_w[r];
+    float g = 0.f;
+    if (c < p.dl && w != 0.f) {
+      const float df = p.pred[(size_t)r * p.ld_pred + c] - p.flow[(size_t)r * p.dl + c];
+      s += w * (df * df); g = df * (p.grad_scale * w);
+      if (p.row_inst) g *= 1.f / fmaxf(1.f - p.inst_time[p.row_inst[r]], p.clean_eps);
+    }
+    p.dpred[i] = f2bf(p.accumulate ? g + bf2f(p.dpred[i]) : g);
+  }
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) sacc[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) { float a = 0.f; for (int i = 0; i < WAVES; i++) a += sacc[i]; if (a != 0.f) atomicAdd(p.acc, a); }
 }
 
 // fused cosine loss, forward + backward (Self-Flow representation loss): one wave per row, both operands read once, d pred written once.
@@ -2774,10 +2971,44 @@ int tfx_ce_reg_bwd(const tfx_ce_reg_chunk_args* a, void* s) {
   else hipLaunchKernelGGL(ce_reg_chunk_bwd_k<false>, dim3(ce_chunk_grid(&b, false)), dim3(256), 0, ST(s), *a);
   RET();
 }
+int tfx_ce_w_fwd_bwd(const tfx_ce_w_args* a, void* s) {
+  if (!a || a->T < 0 || !a->row_w || !ce_reg_weights_ok(a->z_weight, a->smoothing)) return -1;
+  if (a->T == 0) return 0;
+  if (a->V < 1 || a->V > a->ld || a->V > a->ld_d || !a->logits || !a->labels || !a->dlogits || !a->acc || !a->aux) return -1;
+  int g = grid_tokens(a->T); if (g > 1024) g = 1024;
+  hipLaunchKernelGGL(ce_w_k, dim3(g), dim3(256), 0, ST(s), *a); RET();
+}
+static inline tfx_ce_chunk_args ce_w_plain(const tfx_ce_w_chunk_args* a) {
+  tfx_ce_chunk_args b = {a->T, a->V, a->logits, a->ld, a->labels, a->lse, a->acc, a->grad_scale, a->scale_dev, a->dlogits, a->ld_d};
+  return b;
+}
+int tfx_ce_w_fwd(const tfx_ce_w_chunk_args* a, void* s) {
+  if (!a || !a->row_w || !ce_reg_weights_ok(a->z_weight, a->smoothing)) return -1;
+  const tfx_ce_chunk_args b = ce_w_plain(a);
+  const int rc = ce_chunk_check(&b, false); if (rc) return rc < 0 ? rc : 0;
+  if (!a->aux) return -1;
+  if (a->ld > CE_WIDE_LD) hipLaunchKernelGGL(ce_w_chunk_fwd_k<true>, dim3(ce_chunk_grid(&b, true)), dim3(256), 0, ST(s), *a);
+  else hipLaunchKernelGGL(ce_w_chunk_fwd_k<false>, dim3(ce_chunk_grid(&b, false)), dim3(256), 0, ST(s), *a);
+  RET();
+}
+int tfx_ce_w_bwd(const tfx_ce_w_chunk_args* a, void* s) {
+  if (!a || !a->row_w || !ce_reg_weights_ok(a->z_weight, a->smoothing)) return -1;
+  const tfx_ce_chunk_args b = ce_w_plain(a);
+  const int rc = ce_chunk_check(&b, true); if (rc) return rc < 0 ? rc : 0;
+  if (a->ld_d > CE_WIDE_LD) hipLaunchKernelGGL(ce_w_chunk_bwd_k<true>, dim3(ce_chunk_grid(&b, true)), dim3(256), 0, ST(s), *a);
+  else hipLaunchKernelGGL(ce_w_chunk_bwd_k<false>, dim3(ce_chunk_grid(&b, false)), dim3(256), 0, ST(s), *a);
+  RET();
+}
 int tfx_mse_fwd_bwd(const tfx_mse_args* a, void* s) {
   long long n = (long long)a->R * a->ld_d; if (n == 0) return 0;
   long long g = (n + 255) / 256; if (g > 2048) g = 2048;
   hipLaunchKernelGGL(mse_k, dim3((unsigned)g), dim3(256), 0, ST(s), *a); RET();
+}
+int tfx_mse_w_fwd_bwd(const tfx_mse_w_args* a, void* s) {
+  if (!a || !a->row_w) return -1;
+  long long n = (long long)a->R * a->ld_d; if (n == 0) return 0;
+  long long g = (n + 255) / 256; if (g > 2048) g = 2048;
+  hipLaunchKernelGGL(mse_w_k, dim3((unsigned)g), dim3(256), 0, ST(s), *a); RET();
 }
 int tfx_cosine_fwd_bwd(const tfx_cosine_args* a, void* s) {
   if (!a || a->T < 0 || a->d <= 0 || a->d > 2048 || (a->d % 64) || (a->ld_pred % 8) || (a->ld_target % 8) || (a->ld_d % 8) || a->ld_pred < a->d || a->ld_target < a->d || a->ld_d < a->d) return -1;
@@ -2913,6 +3144,6 @@ int tfx_laser_v_bwd(const tfx_laser_v_args* a, void* s) {
   if (nch >= (1ll << 31)) return -4;
   hipLaunchKernelGGL(laser_v_bwd_k, dim3((unsigned)((nch + 255) / 256)), dim3(256), 0, ST(s), *a, (unsigned)nch); RET();
 }
-const char* tfx_version(void) { return "tfx-hip gfx950 r5-laser-muon-selfflow-adamgroups-oderk-tntable-atan2-ablate-lora-topkp-odeab-textreg-frozen"; }
+const char* tfx_version(void) { return "tfx-hip gfx950 r5-laser-muon-selfflow-adamgroups-oderk-tntable-atan2-ablate-lora-topkp-odeab-lossw-textreg-frozen"; }
 
 }  // extern "C"

@@ -235,7 +235,7 @@ class _BwdBuild:
 
 class Plan:
     def __init__(self, ps: ParamStore, b: int, n: int, I: int, R: dict, training: bool = True, cache=None, dp_groups: int = 0, tile_attn: bool = False, units=None, ctl_rows: int = 2, tn_defer=None, ckpt: bool = False,
-                 chunk_rows=None, text_terms=None):
+                 chunk_rows=None, text_terms=None, weighted=False):
         """cache: None, or a KV cache tensor [depth, b, maxlen, 2*heads*64] (k~ | v per token).  With a cache the plan is a
         DECODE step: each layer appends this step's k~ / v rows at `cache_pos` (flat row b*maxlen + position, -1 = skip) and
         attention reads keys / values from the cache (per-token visible length in `kv_end`).
@@ -250,7 +250,11 @@ class Plan:
         chunk (_bwd_text_chunks).  The upstream gradient of the loss reaches tfx_ce_bwd through the device scalar `go_dev`.
         text_terms: (z-loss weight, label smoothing) of the TEXT LOSS TERMS (training plans; Transfusion.set_text_loss_terms_).  With a non-zero weight every
         cross-entropy launch of the plan is its `_reg` form (tfx.h tfx_ce_reg_args) and the plan owns `aux`, two floats behind `acc` - the plain CE sum and
-        the sum of lse^2 - zeroed with it (zero_acc).  (0, 0) and None build the plain plan, launch for launch."""
+        the sum of lse^2 - zeroed with it (zero_acc).  (0, 0) and None build the plain plan, launch for launch.
+        weighted: PER-TOKEN LOSS WEIGHTS (training plans; Transfusion.forward(loss_weights=...)).  The plan owns `w_text` [T] - the weight of every row's
+        label - and per native type `w_inst` [I] and `w_row` [R] (fp32, filled per step by the caller); every cross-entropy launch is its `_w` form
+        (tfx.h tfx_ce_w_args, text terms included, so the plan owns `aux` too) and the flow and velocity targets are tfx_mse_w_fwd_bwd on `w_row`, which a
+        tfx_gather_f32 ahead of the flow target expands from `w_inst` through `row_inst`.  Nothing else differs, and False builds what it always built."""
         md = ps.md
         self.training = training
         self.ckpt = bool(ckpt) and training
@@ -258,6 +262,7 @@ class Plan:
         # the side stream's weight-gradient GEMMs read a layer's saved activations one layer behind the data-gradient chain: two slots by layer parity
         # there, one on a single stream
         self.reg = (float(text_terms[0]), float(text_terms[1])) if (training and text_terms and (text_terms[0] or text_terms[1])) else None
+        self.weighted = bool(weighted) and training
         self.n_slots = (2 if self._side_stream(md) else 1) if self.ckpt else None
         self.units = units
         assert not units or (cache is not None and tile_attn), 'compacted plans are decode plans on the tiled attention kernel (the row ranges are its arguments)'
@@ -375,10 +380,16 @@ class Plan:
                                flow=e(r, dl, dtype=torch.float32), pred=e(r, dl, dtype=torch.float32), dpred=z(r, dlp))
         for t in self.ext_add:
             self.lat[t]['add'] = z(R[t], d)      # additive token rows: the axial positional embedding (T:1384-1403, T:3173-3176), bf16
-        self.acc = z(max(8, 2 + 3 * len(md.dim_latents)) + (2 if self.reg else 0), dtype=torch.float32)      # [ce sum, ce count, flow sse per type..., velocity sse per type..., weighted recon sse per type...]
+        self.acc = z(max(8, 2 + 3 * len(md.dim_latents)) + (2 if (self.reg or self.weighted) else 0), dtype=torch.float32)      # [ce sum, ce count, flow sse per type..., velocity sse per type..., weighted recon sse per type...]
         self._acc_all, self.aux = self.acc, None
-        if self.reg:                          # text loss terms: [plain ce sum, sum of lse^2] ride behind the accumulators - one buffer, one memset
+        if self.reg or self.weighted:         # text loss terms: [plain ce sum, sum of lse^2] ride behind the accumulators - one buffer, one memset
             self.acc, self.aux = self._acc_all[:-2], self._acc_all[-2:]
+        if self.weighted:                     # loss weights: per label row, per instance, per latent row (padding rows and instances: 0)
+            self.w_text = z(max(T, 1), dtype=torch.float32)
+            self.w_inst = z(I1, dtype=torch.float32)
+            for t, r in R.items():
+                if t not in self.ext:
+                    self.lat[t]['w_row'] = z(r, dtype=torch.float32)
         # per layer: the soft-cap plan tfx_qk_norm_rope_fwd derives from the layer's QK-RMSNorm gains (tfx.h) and its attention kernels - forward
         # and, later, backward - read: polynomial degree and coefficients from the BOUND on the scores, no look at the data.
         # Without QK-RMSNorm (md.qk_norm False) nothing bounds the scores: no plan, the attention kernels take their data-dependent form
@@ -662,6 +673,10 @@ class Plan:
             lt = self.lat[t]
             lt['vel'] = torch.zeros(r, md.dim_latents[t], device=self.ps.device, dtype=torch.float32)
             lt['recw'] = torch.zeros(r, device=self.ps.device, dtype=torch.float32)
+            if self.weighted:                 # w_row = w_inst[row_inst], over the real rows (set_rows)
+                gat = [self.w_inst.data_ptr(), self.row_inst[t].data_ptr(), lt['w_row'].data_ptr(), r]      # (mutable: the row count follows the step)
+                L.append((capi.lib().tfx_gather_f32, gat))
+                L.patched(('rows', t), (gat, 3))
             self._mse_args[t] = self._loss_target(L, t, 2 + t, lt['flow'])
             # second target on the same prediction; dpred accumulates.  Run only when a teacher is given
             self._vel_args[t] = self._loss_target(self.vel, t, 2 + nm + t, lt['vel'], accumulate=1)
@@ -681,11 +696,15 @@ class Plan:
         self._nt(lst, A=self.embed[r0:], lda=d, B=self.ps.shadows['logits'], ldb=d, M=m, N=md.vp, K=d, algo_n=md.vocab, epi=E['TFX_EPI_F32'], C=self.logits_c, ldc=md.vp)
 
     def _ce_fn(self, name):
-        """a cross-entropy entry point or args struct by its plain name: with text loss terms (`reg`) its `_reg` form, tfx_ce_fwd -> tfx_ce_reg_fwd"""
-        return name.replace('tfx_ce_', 'tfx_ce_reg_') if self.reg else name
+        """a cross-entropy entry point or args struct by its plain name: with text loss terms (`reg`) its `_reg` form, tfx_ce_fwd -> tfx_ce_reg_fwd; with
+        loss weights (`weighted`) its `_w` form, which carries the terms too"""
+        return name.replace('tfx_ce_', 'tfx_ce_w_') if self.weighted else name.replace('tfx_ce_', 'tfx_ce_reg_') if self.reg else name
 
-    def _ce_terms(self):
-        """the fields a `_reg` args struct has beyond the plain one ({} without text loss terms)"""
+    def _ce_terms(self, r0=0):
+        """the fields a `_reg` / `_w` args struct has beyond the plain one ({} without text loss terms and loss weights); `r0`: the launch's first row"""
+        if self.weighted:
+            z, e = self.reg or (0., 0.)
+            return dict(z_weight=z, smoothing=e, aux=self.aux, row_w=self.w_text[r0:])
         return dict(z_weight=self.reg[0], smoothing=self.reg[1], aux=self.aux) if self.reg else {}
 
     def zero_acc(self):
@@ -696,7 +715,7 @@ class Plan:
         """tfx_ce_chunk_args of rows r0 .. r0 + m, owned by `lst` and registered with it for the per-step setters (set_ce_vocab, set_loss_scales)"""
         md = self.md
         a = capi.make_args(self._ce_fn('tfx_ce_chunk_args'), T=m, V=md.vocab, logits=self.logits_c, ld=md.vp, labels=self.labels[r0:], lse=self.ce_lse[r0:], acc=self.acc,
-                           grad_scale=0.0, scale_dev=self.go_dev, dlogits=self.dlogits_c, ld_d=md.vp, **self._ce_terms())
+                           grad_scale=0.0, scale_dev=self.go_dev, dlogits=self.dlogits_c, ld_d=md.vp, **self._ce_terms(r0))
         lst.patched('ce', a)
         return a
 
@@ -710,9 +729,10 @@ class Plan:
         md, lt = self.md, self.lat[t]
         dl = md.dim_latents[t]
         clean = dict(row_inst=self.row_inst[t], inst_time=self.inst_time, clean_eps=float(md.clean_eps)) if md.model_output_clean else {}
-        a = capi.make_args('tfx_mse_args', R=self.R[t], dl=dl, pred=lt['pred'], ld_pred=dl, flow=target, grad_scale=0.0, dpred=lt['dpred'], ld_d=pad_to(dl, 64),
-                           acc=self.acc.data_ptr() + 4 * slot, **clean, **extra)
-        lst.append(('tfx_mse_fwd_bwd', a))
+        wt = self.weighted and 'recon_w' not in extra          # (the reconstruction target takes no loss weights: it keeps the plain kernel)
+        a = capi.make_args('tfx_mse_w_args' if wt else 'tfx_mse_args', R=self.R[t], dl=dl, pred=lt['pred'], ld_pred=dl, flow=target, grad_scale=0.0, dpred=lt['dpred'],
+                           ld_d=pad_to(dl, 64), acc=self.acc.data_ptr() + 4 * slot, **clean, **extra, **({'row_w': lt['w_row']} if wt else {}))
+        lst.append(('tfx_mse_w_fwd_bwd' if wt else 'tfx_mse_fwd_bwd', a))
         lst.patched(('rows', t), (a, 'R'))
         return a
 
@@ -924,6 +944,8 @@ class Plan:
                 lt['xt'][r:].zero_()
                 if 'dpred' in lt:
                     lt['dpred'][r:].zero_()
+                if 'w_row' in lt:
+                    lt['w_row'][r:].zero_()
             if self.row_gat is not self.row_tok:
                 torch.clamp(self.row_tok[t], min=0, out=self.row_gat[t])
 

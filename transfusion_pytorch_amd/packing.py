@@ -9,6 +9,7 @@ rows are right-padded with -1; `total_tokens` = sum of packed lengths; positions
 from __future__ import annotations
 
 import math
+import weakref
 from dataclasses import dataclass
 
 import numpy as np
@@ -39,6 +40,13 @@ class PackedBatch:
     row_pos: dict                     # type -> (R,) int32 flat position b*n_full + offset + i  (in the FULL layout)
     lens: np.ndarray                  # packed length per sample
     total_tokens: int = 0
+    # the layout of per-part LOSS WEIGHTS (lay_loss_weights): per part in scan order its sample, the flat range of the tokens it put on the (b, n_full) grid
+    # - a text part's tokens; a modality part's [meta] shape [som] slots [eom] - and its instance (-1: text); per sample the flat position of [eos] (-1: none)
+    part_b: np.ndarray = None
+    part_start: np.ndarray = None
+    part_len: np.ndarray = None
+    part_inst: np.ndarray = None
+    eos_dest: np.ndarray = None
 
 
 def _ranges(starts: np.ndarray, lens: np.ndarray) -> np.ndarray:
@@ -61,6 +69,8 @@ def scan_batch(modalities, *, num_modalities, dim_latents, sos_id, eos_id, meta_
     inst_b, inst_m, inst_type, inst_off, inst_len, inst_shape = [], [], [], [], [], []
     latents = {t: [] for t in range(num_modalities)}
     run_b, run_o, run_l, run_fill, run_drop = [], [], [], [], []      # constant runs: (sample, offset, length, id value, droppable)
+    part_b, part_o, part_l, part_inst = [], [], [], []               # every part: (sample, offset, tokens it puts on the row, instance | -1)
+    eos_o = np.full(b, -1, dtype=np.int64)
     lit_b, lit_o, lit_ids = [], [], []                                # literal runs: the [meta] shape string [som] tokens (never droppable)
     meta_cache = {}
     lens = np.zeros(b, dtype=np.int64)
@@ -82,6 +92,7 @@ def scan_batch(modalities, *, num_modalities, dim_latents, sos_id, eos_id, meta_
                 user_text.append(part if part.ndim == 1 else part.reshape(-1))
                 dest_b.append(bi); dest_o.append(cur); dest_l.append(L)
                 run_b.append(bi); run_o.append(cur); run_l.append(L); run_fill.append(-1); run_drop.append(True)
+                part_b.append(bi); part_o.append(cur); part_l.append(L); part_inst.append(-1)
                 cur += L
                 continue
             ty, x = part[0], part[1]
@@ -89,6 +100,7 @@ def scan_batch(modalities, *, num_modalities, dim_latents, sos_id, eos_id, meta_
             assert x.shape[-1] == dim_latents[ty], f'mismatch for modality latent dimension - expected {dim_latents[ty]} but received {x.shape[-1]}'
             axial = tuple(x.shape[:-1])
             L = math.prod(axial)
+            part_b.append(bi); part_o.append(cur); part_inst.append(len(inst_b))
             if add_meta:
                 key = (axial, ty)
                 lit = meta_cache.get(key)
@@ -102,12 +114,14 @@ def scan_batch(modalities, *, num_modalities, dim_latents, sos_id, eos_id, meta_
             if add_meta:
                 run_b.append(bi); run_o.append(cur); run_l.append(1); run_fill.append(eom_ids[ty]); run_drop.append(False)
                 cur += 1
+            part_l.append(cur - part_o[-1])
             inst_b.append(bi); inst_m.append(m); inst_type.append(ty); inst_off.append(off); inst_len.append(L); inst_shape.append(axial)
             pos.append((ty, off, L))
             latents[ty].append(x if x.ndim == 2 else x.reshape(L, -1))
             m += 1
         if add_sos_eos:
             run_b.append(bi); run_o.append(cur); run_l.append(1); run_fill.append(eos_id); run_drop.append(True)
+            eos_o[bi] = cur
             cur += 1
         lens[bi] = cur
         positions.append(pos)
@@ -135,7 +149,9 @@ def scan_batch(modalities, *, num_modalities, dim_latents, sos_id, eos_id, meta_
     return PackedBatch(
         b=b, n_full=n_full, text_host=text_host.reshape(b, n_full), user_text=user_text, text_dest=text_dest, cfg_droppable=cfg_drop.reshape(b, n_full),
         positions=positions, inst_b=ib, inst_m=np.array(inst_m, np.int64), inst_type=it, inst_off=io, inst_len=il,
-        inst_shape=inst_shape, latents=latents, row_inst=row_inst, row_pos=row_pos, lens=lens, total_tokens=int(lens.sum()))
+        inst_shape=inst_shape, latents=latents, row_inst=row_inst, row_pos=row_pos, lens=lens, total_tokens=int(lens.sum()),
+        part_b=np.asarray(part_b, np.int64), part_start=np.asarray(part_b, np.int64) * n_full + np.asarray(part_o, np.int64), part_len=np.asarray(part_l, np.int64),
+        part_inst=np.asarray(part_inst, np.int64), eos_dest=np.where(eos_o >= 0, np.arange(b, dtype=np.int64) * n_full + eos_o, -1))
 
 
 def scan_signature(sig, user_text, latents, *, num_modalities, dim_latents, sos_id, eos_id, meta_id, som_ids, eom_ids,
@@ -210,10 +226,12 @@ def scan_signature(sig, user_text, latents, *, num_modalities, dim_latents, sos_
             row_pos[t] = _ranges(m_b[sel] * n_full + inst_off[sel], inst_len[sel]).astype(np.int32)
             row_inst[t] = np.repeat(sel.astype(np.int32), inst_len[sel])
             lat[t] = latents[t]
+    part_inst = np.full(N, -1, dtype=np.int64); part_inst[is_mod] = np.arange(M, dtype=np.int64)
     return PackedBatch(
         b=b, n_full=n_full, text_host=text_host.reshape(b, n_full), user_text=user_text, text_dest=text_dest, cfg_droppable=cfg_drop.reshape(b, n_full),
         positions=positions, inst_b=m_b, inst_m=inst_m, inst_type=inst_type, inst_off=inst_off.astype(np.int32), inst_len=inst_len.astype(np.int32),
-        inst_shape=[tuple(a) for a in inst_shape], latents=lat, row_inst=row_inst, row_pos=row_pos, lens=lens, total_tokens=int(lens.sum()))
+        inst_shape=[tuple(a) for a in inst_shape], latents=lat, row_inst=row_inst, row_pos=row_pos, lens=lens, total_tokens=int(lens.sum()),
+        part_b=part_b, part_start=part_b * n_full + off, part_len=cnt, part_inst=part_inst, eos_dest=row0 + lens - 1 if add_sos_eos else np.full(b, -1, np.int64))
 
 
 @dataclass
@@ -249,6 +267,100 @@ def token_maps(P: PackedBatch, n: int, num_modalities: int, rot_offset: int = 0)
     rot = ar[None, :] - np.cumsum(extra.reshape(b, n), axis=1, dtype=np.int32) + rot_offset
     return TokenMaps(n=n, tok_inst=tok_inst.reshape(b, n), kv_end=kv_end.reshape(b, n).astype(np.int32), q_start=q_start.reshape(b, n).astype(np.int32),
                      rot_pos=rot.astype(np.int32), is_type=counts)
+
+
+def loss_weight_maps(P: PackedBatch):
+    """the structure side of the loss-weight layout (nothing of the weights themselves): `tok_part` (b * n_full,) - for every token of the grid the slot
+    of the weight table `lay_loss_weights` reads it from: the part that put it there, N (weight 0) for [sos] and padding, and for [eos] the sample's last
+    part, or N + 1 (weight 1) in a sample without parts - and `inst_part` (I,), the part of every modality instance"""
+    N = len(P.part_b)
+    tok_part = np.full(P.b * P.n_full, N, dtype=np.int64)
+    tok_part[_ranges(P.part_start, P.part_len)] = np.repeat(np.arange(N, dtype=np.int64), P.part_len)
+    last = np.full(P.b, N + 1, dtype=np.int64)
+    last[P.part_b] = np.arange(N, dtype=np.int64)                     # (scan order: a sample's last part writes last)
+    has_eos = P.eos_dest >= 0
+    tok_part[P.eos_dest[has_eos]] = last[has_eos]
+    inst_part = np.flatnonzero(P.part_inst >= 0)
+    return tok_part, inst_part
+
+
+def check_weight_tensors(src, on_device, seen=None):
+    """refuse negative / non-finite loss weights given as tensors: ONE flag read back from the device for all of them (the values stay there).  `seen`: a
+    dict the caller keeps - a tensor that passed is remembered by identity and version counter ({id: (weak reference, version)}), so a weight set that is
+    reused step after step (a dataset's cached masks) is read back once and the later steps do not synchronise; new or modified tensors are checked again."""
+    fresh = [(s, d) for s, d in zip(src, on_device) if seen is None or not ((e := seen.get(id(s))) is not None and e[0]() is s and e[1] == s._version)]
+    if not fresh:
+        return
+    for group in ([s for s, _ in fresh if s.device.type == 'cpu'], [d for s, d in fresh if s.device.type != 'cpu']):      # (host tensors: read where they are)
+        if group:
+            flat = torch.cat([g.reshape(-1).float() for g in group])
+            if bool((~torch.isfinite(flat) | (flat < 0)).any()):
+                raise ValueError('loss_weights must be finite and >= 0')
+    if seen is not None:
+        if len(seen) > 65536:
+            seen.clear()
+        for s, _ in fresh:
+            seen[id(s)] = (weakref.ref(s), s._version)
+
+
+def lay_loss_weights(P: PackedBatch, loss_weights, device, maps=None, seen=None):
+    """per-part loss weights onto the token grid: `loss_weights` holds one entry per sample - None (all ones) or a list with one entry per part: None,
+    a Python number or a 0-d tensor for the whole part, or, for a text part, a 1-D float tensor with one weight per token.  Returns (grid, w_inst):
+    `grid` (b, n_full) fp32 on `device`, aligned with the packed tokens - element [i, j] weights the PREDICTION of token j of row i; a modality part's weight
+    stands on the tokens the packer inserted for it ([meta], the shape characters, [som], [eom]; its latent slots are never labels), [sos] and padding carry
+    0 and [eos] the last weight of the sample's last part - and `w_inst` (I,) fp32, the weight of every modality instance's flow rows.  Weight tensors stay
+    on their device: the host reads shapes, and one flag for the refusal of negative / non-finite values (check_weight_tensors; `seen`: its memory of the
+    tensors that passed).  `maps`: `loss_weight_maps(P)` as tensors on `device`, when the caller keeps them."""
+    N = len(P.part_b)
+    if not isinstance(loss_weights, (list, tuple)) or len(loss_weights) != P.b:
+        raise ValueError(f'loss_weights takes one entry per sample ({P.b}), got {len(loss_weights) if isinstance(loss_weights, (list, tuple)) else type(loss_weights).__name__}')
+    nparts = np.bincount(P.part_b, minlength=P.b) if N else np.zeros(P.b, np.int64)
+    first = np.cumsum(nparts) - nparts
+    table = np.ones(N + 2, dtype=np.float32); table[N] = 0.
+    scalars, vectors = [], []                                              # (slot, 0-d tensor), (part, 1-D tensor)
+    for bi, sw in enumerate(loss_weights):
+        if sw is None:
+            continue
+        if not isinstance(sw, (list, tuple)) or len(sw) != nparts[bi]:
+            raise ValueError(f'loss_weights[{bi}] takes None or one entry per part of the sample ({int(nparts[bi])})')
+        for j, w in enumerate(sw):
+            k = int(first[bi]) + j
+            if w is None:
+                continue
+            if torch.is_tensor(w):
+                if not w.is_floating_point():
+                    raise ValueError(f'loss_weights[{bi}][{j}]: a weight tensor is a float tensor, got {w.dtype}')
+                if w.ndim == 0:
+                    scalars.append((k, w))
+                elif w.ndim == 1 and P.part_inst[k] < 0 and w.numel() == P.part_len[k]:
+                    vectors.append((k, w))
+                else:
+                    want = f'a 0-d tensor or one weight per token, ({int(P.part_len[k])},)' if P.part_inst[k] < 0 else 'a number or a 0-d tensor (a modality part takes one weight)'
+                    raise ValueError(f'loss_weights[{bi}][{j}]: shape {tuple(w.shape)} does not match the part - {want}')
+            elif isinstance(w, (int, float)) and not isinstance(w, bool):
+                if not math.isfinite(w) or w < 0:
+                    raise ValueError(f'loss_weights[{bi}][{j}] must be finite and >= 0, got {w}')
+                table[k] = w
+            else:
+                raise ValueError(f'loss_weights[{bi}][{j}]: None, a number or a float tensor, got {type(w).__name__}')
+    if maps is None:
+        maps = tuple(torch.from_numpy(a).to(device) for a in loss_weight_maps(P))
+    tok_part, inst_part = maps
+    tab = torch.from_numpy(table).to(device)
+    given = [w.to(device, torch.float32) for _, w in scalars] + [w.to(device, torch.float32) for _, w in vectors]
+    check_weight_tensors([w for _, w in scalars] + [w for _, w in vectors], given, seen)      # the one value the host reads: a flag
+    if scalars:
+        tab[torch.tensor([k for k, _ in scalars], device=device)] = torch.stack(given[:len(scalars)])
+    grid = tab[tok_part]
+    if vectors:
+        last = {int(first[bi] + nparts[bi] - 1): bi for bi in range(P.b) if nparts[bi]}
+        starts, lens, vals = [], [], []
+        for (k, _), w in zip(vectors, given[len(scalars):]):
+            starts.append(int(P.part_start[k])); lens.append(int(P.part_len[k])); vals.append(w)
+            if k in last and P.eos_dest[last[k]] >= 0 and w.numel():     # [eos] behind the sample's last part: that part's last weight
+                starts.append(int(P.eos_dest[last[k]])); lens.append(1); vals.append(w[-1:])
+        grid.index_copy_(0, torch.from_numpy(_ranges(np.asarray(starts), np.asarray(lens))).to(device), torch.cat(vals))
+    return grid.view(P.b, P.n_full), tab[inst_part]
 
 
 def fast_signature(modalities):

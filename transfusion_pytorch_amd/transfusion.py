@@ -22,7 +22,7 @@ from . import capi
 from . import engine as _engine            # (pull_form_ok is looked up there at call time)
 from .engine import Plan
 from .ode import check_odeint_kwargs
-from .packing import fast_signature, is_int_tensor, scan_batch, scan_signature, token_maps, token_segments
+from .packing import check_weight_tensors, fast_signature, is_int_tensor, lay_loss_weights, loss_weight_maps, scan_batch, scan_signature, token_maps, token_segments
 from .axial import ContinuousAxialPositionalEmbedding
 from .params import ModelDims, ParamStore
 
@@ -149,6 +149,11 @@ def _check_text_filters(top_k, top_p):
             raise ValueError(f'top_p must be None or a number in (0, 1], got {top_p!r}')
         top_p = float(top_p)
     return top_k, top_p
+
+
+def _positive(x):
+    """a sum of loss weights as a divisor: itself where positive, 1 where nothing counted (the numerator is 0 there)"""
+    return torch.where(x > 0, x, torch.ones_like(x))
 
 
 def _num_modalities(sample):
@@ -424,6 +429,7 @@ class Transfusion(nn.Module):
         self._chunk = None                   # rows per chunk of the text head (set_text_head_chunking_; None = off): part of the plan key
         self._text_terms = (0.0, 0.0)        # (z-loss weight, label smoothing) of the text loss (set_text_loss_terms_): part of the plan key
         self._text_terms_plan = None         # the plan of the last training step that ran with the terms on (text_loss_terms)
+        self._lw_seen = {}                   # loss-weight tensors that passed the finite / non-negative check (packing.check_weight_tensors)
         self._struct_cache = {}
         self._decode_plans = {}              # decode plans of the cached forward calls and of the sampler (sampling.Sampler._decode_plan)
         self._flat_pred_flows = False        # set by `_teacher_pass` around a teacher's forward
@@ -633,9 +639,22 @@ class Transfusion(nn.Module):
             lo += L
         return preds
 
-    def _ext_flow_loss(self, t, preds, ctx):
+    @staticmethod
+    def _ext_weighted_mse(preds, targets, wi):
+        """the packed mse of an `ext` type under per-instance loss weights `wi` (I_t,): (what stands in the loss where the unweighted mean stood -
+        sum_i w_i sse_i / (all elements), so that times the type's token share it is sum w err^2 / (elements per row) / total_tokens -, the weighted
+        mean sum_i w_i sse_i / sum_i w_i n_i that the breakdown reports: the native types' sum w err^2 / (dl sum_rows w); 0 when every weight is 0)"""
+        sse = torch.stack([(p.reshape(-1) - f.reshape(-1)).square().sum() for p, f in zip(preds, targets)])
+        n = torch.tensor([p.numel() for p in preds], device=sse.device, dtype=sse.dtype)
+        num = (wi.to(sse.dtype) * sse).sum()
+        return num / n.sum(), (num / _positive((wi.to(sse.dtype) * n).sum())).detach()
+
+    def _ext_flow_loss(self, t, preds, ctx, wi=None):
         """flow loss of an `ext` type: ONE mse over all instances of the type packed together (T:3356-3364); with a reconstruction loss also the
-        mean over the instances of mse(noised, noise + pred (1 - t)) (MP:177-200, T:3422-3426).  Returns (flow loss, reconstruction loss | None)."""
+        mean over the instances of mse(noised, noise + pred (1 - t)) (MP:177-200, T:3422-3426).  Returns (flow loss, reconstruction loss | None).
+        `wi`: per-instance loss weights - the flow loss is then the pair of `_ext_weighted_mse` (no reconstruction loss: refused with weights)."""
+        if wi is not None:
+            return self._ext_weighted_mse(preds, ctx['flow'], wi), None
         fl = torch.nn.functional.mse_loss(torch.cat([p.reshape(-1) for p in preds]), torch.cat([f.reshape(-1) for f in ctx['flow']]))
         rec = None
         if self.has_recon_loss:
@@ -744,7 +763,7 @@ class Transfusion(nn.Module):
         plan = self._text_terms_plan() if self._text_terms_plan is not None else None
         if plan is None or not any(self._text_terms):
             return None
-        cnt = plan.acc[1].clamp(min=1.)
+        cnt = _positive(plan.acc[1]) if plan.weighted else plan.acc[1].clamp(min=1.)      # (loss weights: the sum of the weights, the means are weighted)
         return TextLossTerms(plan.acc[0] / cnt, plan.aux[0] / cnt, plan.aux[1] / cnt)
 
     def _require_gpu(self):
@@ -762,18 +781,21 @@ class Transfusion(nn.Module):
             self._rope = (cos.to(self.device).contiguous(), sin.to(self.device).contiguous())
         return self._rope
 
-    def _plan(self, b, n, I, R, training, text_loss=False):
-        """`text_loss`: the call returns the text loss (forward, forward_text with return_loss) - the training plans set_text_head_chunking_ applies to"""
+    def _plan(self, b, n, I, R, training, text_loss=False, weighted=False):
+        """`text_loss`: the call returns the text loss (forward, forward_text with return_loss) - the training plans set_text_head_chunking_ applies to;
+        `weighted`: the call carries loss weights (their presence is part of the key, their values never are)"""
         dp_groups = getattr(self, '_dp_groups', 0) if training else 0
         ckpt = training and self._ckpt                              # inference, decode, sampling and hiddens-only plans never look at the switch
         chunk = self._chunk if (training and text_loss) else None   # ... nor at this one; forward_modality's training plans neither (no text loss)
         terms = self._text_terms if (training and text_loss and any(self._text_terms)) else None      # ... nor at the text loss terms
-        key = (b, n, I, tuple(sorted(R.items())), training, dp_groups, ckpt, chunk, terms)
+        weighted = bool(weighted) and training
+        key = (b, n, I, tuple(sorted(R.items())), training, dp_groups, ckpt, chunk, terms, weighted)
         plan = self._plans.pop(key, None)
         if plan is None:
             while len(self._plans) >= 8:                             # least recently used plan goes first (dict order = use order)
                 self._plans.pop(next(iter(self._plans)))
-            plan = Plan(self.store, b, n, I, R, training=training, dp_groups=dp_groups, ckpt=ckpt, **({'chunk_rows': chunk} if chunk else {}), **({'text_terms': terms} if terms else {}))
+            plan = Plan(self.store, b, n, I, R, training=training, dp_groups=dp_groups, ckpt=ckpt, **({'chunk_rows': chunk} if chunk else {}), **({'text_terms': terms} if terms else {}),
+                        **({'weighted': True} if weighted else {}))
             # a plan owns every activation of its step (tens of GB for a training plan at dim 1024 / depth 24): besides the count, the cache is
             # bounded by bytes - TFX_PLAN_BUDGET_GB, default 40 % of the device memory - oldest first, the new plan always stays
             budget = float(os.environ.get('TFX_PLAN_BUDGET_GB', 0)) * 2 ** 30 or 0.4 * torch.cuda.get_device_properties(self.device).total_memory
@@ -822,6 +844,8 @@ class Transfusion(nn.Module):
             th = np.full((b, n_new), -1, dtype=np.int32); th[:, :old] = P.text_host; P.text_host = th
             cd = np.zeros((b, n_new), dtype=bool); cd[:, :old] = P.cfg_droppable; P.cfg_droppable = cd
             P.text_dest = (P.text_dest // old) * n_new + (P.text_dest % old)
+            P.part_start = (P.part_start // old) * n_new + (P.part_start % old)
+            P.eos_dest = np.where(P.eos_dest >= 0, (P.eos_dest // old) * n_new + (P.eos_dest % old), -1)
             for t in P.row_pos:
                 rp = P.row_pos[t].astype(np.int64)
                 P.row_pos[t] = ((rp // old) * n_new + (rp % old)).astype(np.int32)
@@ -941,11 +965,26 @@ class Transfusion(nn.Module):
     def forward(self, modalities, times=None, num_modalities_to_times_fn=None, modality_type=None, cache=None, decode_length=None,
                 decoding_text_or_modality=None, velocity_consistency_ema_model=None, velocity_consistency_delta_time=1e-3,
                 return_only_pred_flows=False, return_loss=True, return_breakdown=False, return_embed=False, return_hiddens=False,
-                return_kv_cache=False, return_times=False, prob_uncond=None, _hidden_request=None):
+                return_kv_cache=False, return_times=False, prob_uncond=None, _hidden_request=None, *, loss_weights=None):
         """`_hidden_request` (internal, SelfMaskedRepTraining): {'raw': hiddens as bf16 views of the plan's buffers, 'hiddens_only': under no_grad run the
-        training layout on a plan that keeps the hiddens alone and stops at the final norm (loss = None)}; the return value then ends with (plan, n_true)"""
+        training layout on a plan that keeps the hiddens alone and stops at the final norm (loss = None)}; the return value then ends with (plan, n_true)
+        `loss_weights`: PER-TOKEN LOSS WEIGHTS of a training step (which tokens of a packed sample are trained on, and how strongly): None, or a list with
+        one entry per sample, each None (all ones) or a list with one entry per part - None, a number or a 0-d tensor for the whole part, or for a text part a
+        1-D float tensor with one weight per token (element j weights the prediction of the part's token j).  A modality part's weight applies to its flow
+        rows and to the tokens the packer inserts for it ([meta], shape characters, [som], [eom]); [sos] is never a label; [eos] takes the last weight of the
+        sample's last part.  Every valid token adds (its weight) x (its own loss) / total_tokens to the loss - no new normaliser; `LossBreakdown.text` is the
+        weighted mean sum w r / sum w, each flow / velocity entry sum w err^2 / (dim_latent sum_rows w) (0 where sum w is 0).  The weights run inside the
+        native loss kernels (include/tfx.h tfx_ce_w_args, tfx_mse_w_args) and never visit the host."""
         # ---- dispatch and argument checks
         self._require_gpu()
+        if loss_weights is not None:
+            if torch.is_tensor(modalities):
+                raise NotImplementedError('loss_weights with a tensor batch: call forward_text(text, loss_weights=W) / forward_modality(x, loss_weights=w)')
+            if self.has_recon_loss:
+                raise NotImplementedError('loss_weights with reconstruction_loss_weight > 0: that term averages per-instance means, no weighting is defined for it')
+            if (not return_loss or return_embed or return_only_pred_flows or return_kv_cache or cache is not None or decoding_text_or_modality is not None
+                    or (_hidden_request or {}).get('hiddens_only')):
+                raise ValueError('loss_weights weight the loss of a training step: they need return_loss = True (and no cache / decode / embed / pred-flow call)')
         # the reference looks its packer up in the registry on every call (get_processing_strategy, MP:1252-1256, called at T:3104-3107).  The fused
         # step packs with the native packer only (every name the reference ships maps to it): an entry someone replaced or added must not be
         # ignored silently
@@ -1018,14 +1057,19 @@ class Transfusion(nn.Module):
 
         # ---- plan
         self.store.refresh_shadows(stream)
-        plan = self._step_plan(S, return_loss, hid_only, no_teacher=ema is None and not return_only_pred_flows)
+        weights = None
+        if loss_weights is not None:                          # refusals first: a bad weight list leaves every plan as it was
+            if 'w_maps' not in S:                             # (structure only: shared by every weight list on this structure)
+                S['w_maps'] = tuple(torch.from_numpy(a).to(dev) for a in loss_weight_maps(P))
+            weights = lay_loss_weights(P, loss_weights, dev, S['w_maps'], self._lw_seen)
+        plan = self._step_plan(S, return_loss, hid_only, no_teacher=ema is None and not return_only_pred_flows, weighted=weights is not None)
         if train_hiddens and not hid_only and torch.is_grad_enabled() and not (_engine.pull_form_ok(self.md) and plan.pull):
             raise NotImplementedError(f'return_hiddens next to the loss (hidden taps) needs the pull-form AttentionResidual backward: {_engine.PULL_LIMITS} '
                                       '(under torch.no_grad() the hiddens come back without a tap)')
 
         # ---- inputs onto the plan: token ids (values never visit the host), CFG drop, labels, instance times, latent rows, noise
         prob_uncond = self.prob_uncond if prob_uncond is None else prob_uncond
-        self._load_text(plan, S, user_text, prob_uncond if self.training else 0., labels=return_loss)
+        self._load_text(plan, S, user_text, prob_uncond if self.training else 0., labels=return_loss, weights=weights)
         if I > 0:
             plan.inst_time[:I].copy_(times[S['inst_b'], S['inst_m']])
         rows_in = self._load_latents(plan, S, latents, ext_ctx, return_loss)
@@ -1054,8 +1098,9 @@ class Transfusion(nn.Module):
         return _pack_outputs(loss, (return_breakdown, breakdown), (train_hiddens, self._hiddens_list(hid, hid_out)), (return_times, times),
                              (_hidden_request is not None, (plan, S['n_true'])))
 
-    def _step_plan(self, S, return_loss, hid_only, no_teacher):
-        """the plan of an interleaved `forward` step with the structure S loaded.  `no_teacher`: no EMA teacher and not a teacher's own `return_only_pred_flows` call."""
+    def _step_plan(self, S, return_loss, hid_only, no_teacher, weighted=False):
+        """the plan of an interleaved `forward` step with the structure S loaded.  `no_teacher`: no EMA teacher and not a teacher's own `return_only_pred_flows` call.
+        `weighted`: the step carries loss weights."""
         md, I, R = self.md, S['I'], S['R']
         # Ragged corpora change the number of modality instances and of latent rows with every batch.  A training plan owns every activation of the
         # step and its launch lists (building one costs far more than a step), so in the plain training case the plan is built for both counts ROUNDED
@@ -1066,7 +1111,7 @@ class Transfusion(nn.Module):
                   and not md.model_output_clean and os.environ.get('TFX_PLAN_BUCKETS', '1') != '0')
         Ip = _bucket(I, 64) if (bucket and I > 0) else I
         Rp = {t: _bucket(r, 256) for t, r in R.items()} if bucket else R
-        plan = self._plan(S['b'], S['n'], Ip, Rp, training=return_loss and not hid_only, text_loss=True)
+        plan = self._plan(S['b'], S['n'], Ip, Rp, training=return_loss and not hid_only, text_loss=True, weighted=weighted)
         if return_loss and not hid_only:
             plan.clear_taps()                               # a tap lives for the step that set it
         if md.model_output_clean:
@@ -1077,9 +1122,10 @@ class Transfusion(nn.Module):
                                 segments=(S['seg_start'], S['seg_len']), rows={t: (S['row_tok'][t], S['row_inst'][t]) for t in R}, set_rows=return_loss)
         return plan
 
-    def _load_text(self, plan, S, user_text, prob_uncond=0., labels=False):
+    def _load_text(self, plan, S, user_text, prob_uncond=0., labels=False, weights=None):
         """token ids of a scanned batch onto its plan, on the device: the structure's own tokens with the caller's text scattered in, the CFG text
-        drop (`prob_uncond` > 0), and with `labels` the next-token labels"""
+        drop (`prob_uncond` > 0), and with `labels` the next-token labels; `weights` = (token grid, instance weights) of `lay_loss_weights`: shifted by
+        one with the labels onto the plan's `w_text`, and `w_inst` (padding instances: 0)"""
         dev, n = self.device, S['n']
         text_full = S['text_host'].clone()
         if user_text:
@@ -1092,6 +1138,11 @@ class Transfusion(nn.Module):
             lab = text_full[:, 1:]                                                          # T:3144
             lab = torch.where(S['is_mod'] | (lab == self.null_text_id), S['minus1'], lab)    # T:3320-3323
             plan.labels.copy_(lab.reshape(-1))
+        if weights is not None:
+            grid, w_inst = weights
+            plan.w_text.copy_(grid[:, 1:n + 1].reshape(-1))
+            I = w_inst.numel()
+            plan.w_inst[:I].copy_(w_inst); plan.w_inst[I:].zero_()
 
     def _load_latents(self, plan, S, latents, ext_ctx, return_loss):
         """latent rows and their noise onto the plan.  Returns the rows PyTorch hands to the engine: (kind, type, tensor with autograd history)"""
@@ -1158,12 +1209,17 @@ class Transfusion(nn.Module):
         plan.zero_acc()
         Plan.run(plan.fwd, stream, graph='auto')
 
-        text_loss = acc[0] / acc[1].clamp(min=1.)
+        # loss weights (plan.weighted): acc holds the weighted sums, so the loss keeps its form - a token adds (its weight) x (its loss) / total - and only
+        # the reported means change their divisors: sum w for the text, dim_latent x (sum of the row weights) for a type's flow and velocity entries
+        wden = {t: md.dim_latents[t] * _positive(plan.lat[t]['w_row'][:R[t]].sum()) for t in native} if plan.weighted else None
+        text_loss = acc[0] / (_positive(acc[1]) if plan.weighted else acc[1].clamp(min=1.))
         loss = self.text_loss_weight * acc[0] / total
         flow_losses = {}
         for t in native:
             flow_losses[t] = acc[2 + t] / den[t]
             loss = loss + self.flow_loss_weight * flow_losses[t] * w[t]
+            if plan.weighted:
+                flow_losses[t] = acc[2 + t] / wden[t]
 
         velocity_losses = None
         if teacher_flows is not None:                                                      # T:3383-3418
@@ -1178,6 +1234,8 @@ class Transfusion(nn.Module):
             for t in native:
                 velocity_losses[t] = acc[2 + M + t] / den[t]
                 loss = loss + self.velocity_consistency_loss_weight * velocity_losses[t] * w[t]
+                if plan.weighted:
+                    velocity_losses[t] = acc[2 + M + t] / wden[t]
 
         recon_losses = {}
         if self.has_recon_loss:                                                            # T:3420-3431
@@ -1194,15 +1252,23 @@ class Transfusion(nn.Module):
         loss, outs = self._close_step(plan, loss, rows_in, ext_out, hid, S['n_true'])
         for t, rows in zip(ext_out, outs):                                                  # the user's decoders and their flow losses, in PyTorch
             preds = self._ext_decode(t, rows, ext_ctx[t])
-            fl, rec = self._ext_flow_loss(t, preds, ext_ctx[t])
-            flow_losses[t] = fl
+            wi = None
+            if plan.weighted:                              # the weights of the type's instances, in scan order (the order of `preds`)
+                wi = plan.w_inst[torch.from_numpy(np.flatnonzero(P.inst_type == t)).to(plan.w_inst.device)]
+            fl, rec = self._ext_flow_loss(t, preds, ext_ctx[t], wi)
+            if wi is not None:
+                fl, flow_losses[t] = fl
+            else:
+                flow_losses[t] = fl
             loss = loss + self.flow_loss_weight * fl * w[t]
             if rec is not None:
                 recon_losses[t] = rec
                 loss = loss + self.reconstruction_loss_weight * rec * w[t]
             if teacher_flows is not None:                                                   # T:3397-3411: mse(student flows, teacher flows), all instances of the type packed
-                vl = torch.nn.functional.mse_loss(torch.cat([p.reshape(-1) for p in preds]), torch.cat([p.reshape(-1) for p in teacher[t]]))
-                velocity_losses[t] = vl
+                if wi is not None:
+                    vl, velocity_losses[t] = self._ext_weighted_mse(preds, teacher[t], wi)
+                else:
+                    vl = velocity_losses[t] = torch.nn.functional.mse_loss(torch.cat([p.reshape(-1) for p in preds]), torch.cat([p.reshape(-1) for p in teacher[t]]))
                 loss = loss + self.velocity_consistency_loss_weight * vl * w[t]
         by_type = lambda d: [d[t] for t in sorted(d)]
         breakdown = LossBreakdown(loss, text_loss, by_type(flow_losses), by_type(velocity_losses) if velocity_losses is not None else None,
@@ -1455,15 +1521,24 @@ class Transfusion(nn.Module):
         plan.inst_time.copy_(times.to(dev, torch.float32).reshape(b, -1)[:, -1])
 
     # ------------------------------------------------------------------ pure-text LM path (T:2586-2664)
-    def forward_text(self, text, return_loss=True, return_embed=False, cache=None, return_hiddens=False, return_kv_cache=False):
+    def forward_text(self, text, return_loss=True, return_embed=False, cache=None, return_hiddens=False, return_kv_cache=False, *, loss_weights=None):
         """`Transfusion.forward_text`: the hot path with zero modalities - causal mask, no conditioning, cross entropy over the
         text-only part of the vocabulary (`text_only_logits_mask`, T:1509, T:2653).  Inference calls also take / return the kv cache
-        `(tensor, tokens_seen)` and the hiddens (T:2612-2645): with a cache, `text` holds the NEW tokens only (rotary positions from tokens_seen)."""
+        `(tensor, tokens_seen)` and the hiddens (T:2612-2645): with a cache, `text` holds the NEW tokens only (rotary positions from tokens_seen).
+        `loss_weights`: a float tensor (b, n) aligned with `text` - column j weights the prediction of text[:, j], column 0 is unused; the loss is the weighted
+        mean sum w r / sum w (torch.nn.functional.cross_entropy's `weight` normalisation; with weights in {0, 1}: the loss with those labels ignored)."""
         self._require_gpu()
         if (cache is not None or return_hiddens or return_kv_cache) and return_loss:
             raise NotImplementedError('forward_text: kv cache / hiddens are returned by the inference call only (return_loss = False)')
         dev, stream = self.device, self._stream()
         text = text.to(dev)
+        if loss_weights is not None:
+            if not return_loss or cache is not None:
+                raise ValueError('loss_weights weight the loss of a training step: they need return_loss = True')
+            if not torch.is_tensor(loss_weights) or not loss_weights.is_floating_point() or tuple(loss_weights.shape) != tuple(text.shape):
+                raise ValueError(f'forward_text: loss_weights is a float tensor of the shape of `text`, {tuple(text.shape)}')
+            src, loss_weights = loss_weights, loss_weights.to(dev, torch.float32)
+            check_weight_tensors([src], [loss_weights], self._lw_seen)
         if cache is not None:
             return self._forward_text_cached(text, cache, return_embed, return_kv_cache, return_hiddens)
         inp, labels = (text[:, :-1], text[:, 1:]) if return_loss else (text, None)          # T:2603-2604
@@ -1478,7 +1553,7 @@ class Transfusion(nn.Module):
                         seg_start=D(seg_start), seg_len=D(seg_len))
         S = self._structure(('text', b, n), build)
         self.store.refresh_shadows(stream)
-        plan = self._plan(b, n, 0, {}, training=return_loss, text_loss=True)
+        plan = self._plan(b, n, 0, {}, training=return_loss, text_loss=True, weighted=loss_weights is not None)
         if plan.loaded_structure is not S:
             plan.load_structure(S, self._rope_tables(n), S['tok_inst'], S['kv_end'], S['q_start'], S['rot_pos'], segments=(S['seg_start'], S['seg_len']))
         plan.text_ids.copy_(inp.masked_fill(inp == -1, 0).reshape(-1))                      # T:2608
@@ -1491,9 +1566,11 @@ class Transfusion(nn.Module):
         plan.labels.copy_(torch.where(lab == self.ignore_index, torch.full_like(lab, -1), lab))
         plan.set_loss_scales(1.0, {})                        # mean over the valid labels: the count lives on the device (see _bwd_scale)
         plan.set_ce_vocab(self.num_text_tokens)              # text_only_logits_mask (T:2653)
+        if plan.weighted:
+            plan.w_text.copy_(loss_weights[:, 1:].reshape(-1))
         plan.zero_acc()
         Plan.run(plan.fwd, stream)
-        cnt = plan.acc[1].clamp(min=1.)
+        cnt = _positive(plan.acc[1]) if plan.weighted else plan.acc[1].clamp(min=1.)      # (loss weights: the sum of the weights)
         loss = plan.acc[0] / cnt                             # T:2655-2659
         self._bwd_scale = (1. / cnt).detach()
         return self._close_step(plan, loss)[0]
@@ -1524,12 +1601,24 @@ class Transfusion(nn.Module):
 
     # ------------------------------------------------------------------ pure flow path (T:2710-2869)
     def forward_modality(self, modalities, times=None, modality_type=None, encode_modality=True, velocity_consistency_ema_model=None,
-                         velocity_consistency_delta_time=1e-5, return_loss=True, return_loss_breakdown=False):
+                         velocity_consistency_delta_time=1e-5, return_loss=True, return_loss_breakdown=False, *, loss_weights=None):
         """`Transfusion.forward_modality`: every token is a latent of ONE instance per sample (`modality_only=True`): conditioned on
         the sample's time, no attention mask, no rotary embedding; loss = MSE(pred flow, x - noise).  Encoders / EMA velocity
-        consistency / reconstruction loss are outside the native path."""
+        consistency / reconstruction loss are outside the native path.
+        `loss_weights`: one weight per batch entry (a float tensor (b,) or a list of numbers): the flow and velocity terms become
+        sum w err^2 / (dim_latent sum_rows w) - a zero-weight entry trains as if it were not in the batch."""
         # ---- argument checks, frozen encoder, times
         self._require_gpu()
+        if loss_weights is not None:
+            if not return_loss:
+                raise ValueError('loss_weights weight the loss of a training step: they need return_loss = True')
+            if self.has_recon_loss:
+                raise NotImplementedError('loss_weights with reconstruction_loss_weight > 0: that term averages per-instance means, no weighting is defined for it')
+            src = loss_weights if torch.is_tensor(loss_weights) else torch.as_tensor(loss_weights, dtype=torch.float32)      # (a list of numbers: checked on the host)
+            loss_weights = src.to(self.device, torch.float32)
+            if loss_weights.ndim != 1 or loss_weights.numel() != modalities.shape[0]:
+                raise ValueError(f'forward_modality: loss_weights takes one weight per batch entry ({modalities.shape[0]},), got shape {tuple(loss_weights.shape)}')
+            check_weight_tensors([src], [loss_weights], self._lw_seen)
         ema = self._resolve_ema(velocity_consistency_ema_model)
         if self.num_modalities > 1 and modality_type is None:
             raise AssertionError('`modality_type` must be explicitly passed in on forward when training on greater than 1 modality')
@@ -1573,7 +1662,8 @@ class Transfusion(nn.Module):
         rows = b * L
 
         # ---- structure, plan and its inputs
-        plan = self._modality_plan(b, L, t, return_loss)
+        # (a type whose maps are user modules forms its loss in PyTorch: its weights are applied there, on the unweighted plan)
+        plan = self._modality_plan(b, L, t, return_loss, weighted=loss_weights is not None and not ext)
         plan.inst_time.copy_(times)
         lt = plan.lat[t]
         rows_in = []
@@ -1607,16 +1697,23 @@ class Transfusion(nn.Module):
             self._fill_noise(lt['eps'], t, reshape=True)                                    # T:2753
             plan.set_noise(t, lt['eps'].data_ptr())
         plan.labels.fill_(-1)
-        plan.set_loss_scales(0.0, {} if ext else {t: 2.0 / (rows * dl)})
+        plan.set_loss_scales(0.0, {} if ext else {t: 2.0 / (dl if plan.weighted else rows * dl)})
         plan.set_ce_vocab(md.vocab)
         self._bwd_scale = None
+        if plan.weighted:                                    # weighted mean: the divisor dl x (sum of the row weights) lives on the device (as forward_text's count)
+            plan.w_inst.copy_(loss_weights)
+            wsum = _positive(loss_weights.sum() * L)
+            self._bwd_scale = 1. / wsum
         plan.zero_acc()
         Plan.run(plan.fwd, stream, graph='auto')
-        flow_loss = torch.zeros((), device=dev) if ext else plan.acc[2 + t] / (rows * dl)   # T:2817
+        flow_loss = torch.zeros((), device=dev) if ext else plan.acc[2 + t] / (dl * wsum if plan.weighted else rows * dl)   # T:2817
         loss = flow_loss
         velocity_loss = recon_loss = None
         if ema is not None:
-            velocity_loss = self._modality_velocity_loss(plan, t, ema, teacher_in, orig_times + velocity_consistency_delta_time, flow_ext if ext else None)
+            velocity_loss = self._modality_velocity_loss(plan, t, ema, teacher_in, orig_times + velocity_consistency_delta_time, flow_ext if ext else None,
+                                                         loss_weights if ext else None)
+            if plan.weighted:
+                velocity_loss = velocity_loss * (rows / wsum)                                # (the kernel's sum carries the weights: its divisor is dl x sum_rows w)
             loss = loss + self.velocity_consistency_loss_weight * velocity_loss              # T:2858-2862
         dec = self.modality_decoder[t]
         if self.has_recon_loss:                                                            # T:2840-2853
@@ -1630,7 +1727,7 @@ class Transfusion(nn.Module):
             pred = self.model_to_latent_projs[t](emb.view(b, *axial, d))
             if md.model_output_clean:                                                   # T:2770-2771, T:2810
                 pred = (pred - noised) / (1. - tt).clamp_min(md.clean_eps)
-            flow_loss = torch.nn.functional.mse_loss(pred, flow_ext)
+            flow_loss = torch.nn.functional.mse_loss(pred, flow_ext) if loss_weights is None else self._entry_weighted_mse(pred, flow_ext, loss_weights)
             loss = loss + flow_loss
             if self.has_recon_loss:
                 rec = eps + pred * (1. - tt)
@@ -1645,7 +1742,7 @@ class Transfusion(nn.Module):
         zero = torch.zeros((), device=dev)
         return loss, (flow_loss.detach(), velocity_loss.detach() if velocity_loss is not None else zero, recon_loss.detach() if recon_loss is not None else zero)
 
-    def _modality_plan(self, b, L, t, return_loss):
+    def _modality_plan(self, b, L, t, return_loss, weighted=False):
         """the plan of a `forward_modality` call - b instances of type t, L tokens each, one per row - with its structure loaded"""
         dev, rows = self.device, b * L
 
@@ -1655,7 +1752,7 @@ class Transfusion(nn.Module):
                         row_tok=torch.arange(rows, dtype=torch.int32, device=dev), empty=torch.zeros(0, dtype=torch.int32, device=dev))
         S = self._structure(('modality', b, L, t), build)
         self.store.refresh_shadows(self._stream())
-        plan = self._plan(b, L, b, {t: rows}, training=return_loss)
+        plan = self._plan(b, L, b, {t: rows}, training=return_loss, weighted=weighted)
         if self.md.model_output_clean:
             plan.set_clean_mode('latent')                   # pure flow path: the latent-space conversion (T:2772-2810)
         if plan.loaded_structure is not S:
@@ -1665,14 +1762,20 @@ class Transfusion(nn.Module):
             plan.text_ids.zero_()
         return plan
 
-    def _modality_velocity_loss(self, plan, t, ema, teacher_in, teacher_times, flow_ext=None):
+    @staticmethod
+    def _entry_weighted_mse(a, b, w):
+        """sum_i w_i sum (a_i - b_i)^2 / (elements per entry x sum_i w_i) over the batch entries i: the weighted mean of forward_modality (0 when sum w is 0)"""
+        sse = (a - b).square().reshape(a.shape[0], -1)
+        return (w * sse.sum(dim=1)).sum() / (sse.shape[1] * _positive(w.sum()))
+
+    def _modality_velocity_loss(self, plan, t, ema, teacher_in, teacher_times, flow_ext=None, ext_weights=None):
         """velocity consistency of `forward_modality` (T:2823-2836): mse(FLOW TARGET, teacher flow at t + delta on the clean input) - no gradient reaches
         the student through it.  `flow_ext`: the flow target of a type whose maps are user modules - the teacher's flow comes back in the raw layout,
         the mse is PyTorch's"""
         with _teacher_pass(ema):
             teacher = ema.forward_modality(teacher_in, times=teacher_times, modality_type=t, encode_modality=False, return_loss=False)
             if flow_ext is not None:
-                return torch.nn.functional.mse_loss(flow_ext, teacher)
+                return torch.nn.functional.mse_loss(flow_ext, teacher) if ext_weights is None else self._entry_weighted_mse(flow_ext, teacher, ext_weights)
             if self.channel_first_latent[t]:
                 teacher = teacher.movedim(1, -1)
         lt = plan.lat[t]
