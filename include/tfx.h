@@ -529,6 +529,23 @@ typedef struct {
 int tfx_ce_w_fwd(const tfx_ce_w_chunk_args* a, void* stream);
 int tfx_ce_w_bwd(const tfx_ce_w_chunk_args* a, void* stream);
 
+/* tfx_ce_w_fwd with the ROW TERMS as an output (per-token losses: Transfusion.set_token_losses_()): the forward fields of
+ * tfx_ce_w_chunk_args plus `row_loss`, [T] floats (required).  lse, acc and aux are what tfx_ce_w_fwd writes, sum for sum - the same kernel, width classes,
+ * 16-byte loads and grid caps - and a row that counts also stores  row_loss[t] = w r  (the very number it adds to acc[0]); an ignored row (label < 0 or
+ * w == 0) is not read and stores row_loss[t] = 0.  There is no backward of its own: tfx_ce_w_bwd forms d logits from lse under whatever row weights the
+ * caller hands it - for a function f of the row terms, row_w[t] (d f / d row_loss[t]).  NULL row_w or row_loss: -1 before any launch. */
+typedef struct {
+  int32_t T, V; const float* logits; int32_t ld;      /* a chunk: T rows */
+  const int32_t* labels;                              /* -1 = ignore */
+  float* lse;                                         /* [T]; ignored rows get 0 */
+  float* acc;                                         /* as tfx_ce_w_args */
+  float z_weight, smoothing;
+  float* aux;                                         /* as tfx_ce_w_args */
+  const float* row_w;                                 /* [T] */
+  float* row_loss;                                    /* [T]: w r; ignored rows get 0 */
+} tfx_ce_rows_args;
+int tfx_ce_rows_fwd(const tfx_ce_rows_args* a, void* stream);
+
 /* fused MSE forward + backward: pred/flow fp32 [R, dl]   T:3359-3362 */
 typedef struct {
   int32_t R, dl; const float* pred; int32_t ld_pred; const float* flow;
@@ -562,6 +579,19 @@ typedef struct {
   const float* row_w;                         /* [R] */
 } tfx_mse_w_args;
 int tfx_mse_w_fwd_bwd(const tfx_mse_w_args* a, void* stream);
+/* the forward half of tfx_mse_w_fwd_bwd with the ROW SUMS as an output (per-token losses):  acc[0] += sum_r w_r sum_c err^2  exactly as that kernel forms it
+ * (the same element order: `ld_d` is the row pitch of the d pred its backward will write, a multiple of 64 here, so that a wave's 64 elements lie in one row),
+ * and  row_sse[r] += w_r sum_c err^2  (row_sse: [R] floats the caller zeroes, as it zeroes acc; ld_d / 64 atomics per row that counts).  A row with w_r == 0
+ * is not read and adds nothing.  No gradient is written - the `model_output_clean` factor scales only the gradient, so the forward carries none of its
+ * fields; the backward is tfx_mse_w_fwd_bwd under the caller's row weights, its `acc` pointing at scratch.  NULL row_w or row_sse, ld_d % 64: -1. */
+typedef struct {
+  int32_t R, dl; const float* pred; int32_t ld_pred; const float* flow;
+  int32_t ld_d;
+  float* acc;
+  const float* row_w;                         /* [R] */
+  float* row_sse;                             /* [R], += */
+} tfx_mse_rows_args;
+int tfx_mse_rows_fwd(const tfx_mse_rows_args* a, void* stream);
 /* fused cosine loss forward + backward over bf16 rows (the Self-Flow representation loss, default_rep_loss_fn: 1 - cosine_similarity(pred, target, -1).mean()):
  *   c_t = <x_t, y_t> / (max(|x_t|, 1e-8) max(|y_t|, 1e-8)),   acc[0] += sum of c_t over the rows that count (the host forms 1 - acc / N),
  *   dpred_t = -grad_scale (y_t / (|x_t| |y_t|) - c_t x_t / |x_t|^2)   in bf16, zero for the rows that do not count.
@@ -944,6 +974,8 @@ enum { TFX_OP_GEMM_NT = 0, TFX_OP_GEMM_TN = 1, TFX_OP_ATTN_FWD = 2, TFX_OP_ATTN_
        TFX_OP_CE_W_FWD_BWD = 58,                /* (args = tfx_ce_w_args) */
        TFX_OP_CE_W_FWD = 59, TFX_OP_CE_W_BWD = 60,          /* (args = tfx_ce_w_chunk_args) */
        TFX_OP_MSE_W_FWD_BWD = 61,               /* (args = tfx_mse_w_args) */
+       TFX_OP_CE_ROWS_FWD = 62,                 /* (args = tfx_ce_rows_args) */
+       TFX_OP_MSE_ROWS_FWD = 63,                /* (args = tfx_mse_rows_args) */
        /* stream control (args = any non-NULL pointer; `stream` = event slot 0..63):
           FORK: the library's side stream waits for everything enqueued so far on the caller's stream;
           JOIN_RECORD: mark "everything enqueued so far on the side stream";  JOIN_WAIT: the caller's stream waits for that mark;

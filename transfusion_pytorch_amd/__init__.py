@@ -5,6 +5,7 @@ from .transfusion import (
     Transfusion,
     Transformer,
     LossBreakdown,
+    TokenLosses,
     print_modality_sample,
     create_dataloader,
     exists,
@@ -20,5 +21,5 @@ from .self_flow import SelfMaskedRepTraining, default_rep_loss_fn
 from .optim import FusedAdamAtan2, FusedMuonAdamAtan2, AdamAtan2
 from .lora import add_lora_, lora_parameters, merge_lora_, remove_lora_
 
-__all__ = ['Transfusion', 'Transformer', 'LossBreakdown', 'print_modality_sample', 'create_dataloader', 'EMA', 'SelfMaskedRepTraining', 'default_rep_loss_fn',
+__all__ = ['Transfusion', 'Transformer', 'LossBreakdown', 'TokenLosses', 'print_modality_sample', 'create_dataloader', 'EMA', 'SelfMaskedRepTraining', 'default_rep_loss_fn',
            'FusedAdamAtan2', 'FusedMuonAdamAtan2', 'AdamAtan2', 'add_lora_', 'lora_parameters', 'merge_lora_', 'remove_lora_']

@@ -40,8 +40,10 @@ inline int run_one(const tfx_launch& l, void* s) {
     case TFX_OP_CE_W_FWD_BWD:     return tfx_ce_w_fwd_bwd(static_cast<const tfx_ce_w_args*>(a), s);
     case TFX_OP_CE_W_FWD:         return tfx_ce_w_fwd(static_cast<const tfx_ce_w_chunk_args*>(a), s);
     case TFX_OP_CE_W_BWD:         return tfx_ce_w_bwd(static_cast<const tfx_ce_w_chunk_args*>(a), s);
+    case TFX_OP_CE_ROWS_FWD:      return tfx_ce_rows_fwd(static_cast<const tfx_ce_rows_args*>(a), s);
     case TFX_OP_MSE_FWD_BWD:      return tfx_mse_fwd_bwd(static_cast<const tfx_mse_args*>(a), s);
     case TFX_OP_MSE_W_FWD_BWD:    return tfx_mse_w_fwd_bwd(static_cast<const tfx_mse_w_args*>(a), s);
+    case TFX_OP_MSE_ROWS_FWD:     return tfx_mse_rows_fwd(static_cast<const tfx_mse_rows_args*>(a), s);
     case TFX_OP_CAST_ROWS:        return tfx_cast_rows(static_cast<const tfx_cast_args*>(a), s);
     case TFX_OP_CAST_ROWS_T:      return tfx_cast_rows_t(static_cast<const tfx_cast_args*>(a), s);
     case TFX_OP_ADAM_STEP:        return tfx_adam_step(static_cast<const tfx_adam_args*>(a), s);
@@ -235,8 +237,10 @@ inline size_t struct_bytes(int op) {
     case TFX_OP_CE_REG_FWD: case TFX_OP_CE_REG_BWD: return sizeof(tfx_ce_reg_chunk_args);
     case TFX_OP_CE_W_FWD_BWD: return sizeof(tfx_ce_w_args);
     case TFX_OP_CE_W_FWD: case TFX_OP_CE_W_BWD: return sizeof(tfx_ce_w_chunk_args);
+    case TFX_OP_CE_ROWS_FWD: return sizeof(tfx_ce_rows_args);
     case TFX_OP_MSE_FWD_BWD: return sizeof(tfx_mse_args);
     case TFX_OP_MSE_W_FWD_BWD: return sizeof(tfx_mse_w_args);
+    case TFX_OP_MSE_ROWS_FWD: return sizeof(tfx_mse_rows_args);
     case TFX_OP_CAST_ROWS: case TFX_OP_CAST_ROWS_T: return sizeof(tfx_cast_args);
     case TFX_OP_ADAM_STEP: return sizeof(tfx_adam_args);
     case TFX_OP_ADAM_ATAN2_STEP: return sizeof(tfx_adam_atan2_args);

@@ -4,6 +4,7 @@
 #include <map>
 #include <mutex>
 #include <utility>
+#include <type_traits>
 #include <cstdlib>
 
 namespace tfx {
@@ -1950,11 +1951,14 @@ __global__ __launch_bounds__(256) void ce_reg_chunk_bwd_k(tfx_ce_reg_chunk_args 
 // load per row.  A row whose weight is 0 is an ignored row (label -1 from there on); a row that counts adds w times what ce_reg_row adds, and its gradient
 // scale is s = grad_scale w [* *scale_dev], formed once per row - with w = 1.0f every product below has the `_reg` kernels' bits.
 
-TFX_DEV void ce_w_row(float w, float lse, float ly, float sl, float z, float e, float inv_v, float (&sum)[4]) {
+// (returns w r, the number the row adds to sum[0]: tfx_ce_rows_fwd's row_loss)
+TFX_DEV float ce_w_row(float w, float lse, float ly, float sl, float z, float e, float inv_v, float (&sum)[4]) {
   const float ce = lse - ly, sq = lse * lse;
   float r = ce;
   if (e > 0.f) r = (1.f - e) * ce + e * (lse - sl * inv_v);
-  sum[0] += w * (r + z * sq); sum[1] += w; sum[2] += w * ce; sum[3] += w * sq;
+  const float wr = w * (r + z * sq);
+  sum[0] += wr; sum[1] += w; sum[2] += w * ce; sum[3] += w * sq;
+  return wr;
 }
 
 __global__ __launch_bounds__(256) void ce_w_k(tfx_ce_w_args p) {
@@ -2045,8 +2049,10 @@ __global__ __launch_bounds__(256) void ce_w_k(tfx_ce_w_args p) {
   ce_reg_flush(sum, sacc, p.acc, p.aux);          // (sum[1] = the block's weight: positive exactly when one of its rows counts)
 }
 
-template <bool WIDE>
-__global__ __launch_bounds__(256) void ce_w_chunk_fwd_k(tfx_ce_w_chunk_args p) {
+// A = tfx_ce_w_chunk_args, or tfx_ce_rows_args (tfx_ce_rows_fwd): the same sums, and one more 4-byte store per row - its term w r, 0 for an ignored row
+template <bool WIDE, class A>
+__global__ __launch_bounds__(256) void ce_w_chunk_fwd_k(A p) {
+  constexpr bool ROWS = std::is_same<A, tfx_ce_rows_args>::value;
   __shared__ float sacc[4][WAVES];
   __shared__ float spair[2][3][WAVES];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -2058,7 +2064,10 @@ __global__ __launch_bounds__(256) void ce_w_chunk_fwd_k(tfx_ce_w_chunk_args p) {
   for (int t = WIDE ? blockIdx.x : blockIdx.x * WAVES + w; t < p.T; t += WIDE ? gridDim.x : gridDim.x * WAVES) {
     const float rw = p.row_w[t];                                // (like the label uniform over the row's waves: an ignored row skips the barrier as a block)
     const int lab = rw == 0.f ? -1 : p.labels[t];
-    if (lab < 0) { if (q0 == 0) p.lse[t] = 0.f; continue; }
+    if (lab < 0) {
+      if (q0 == 0) { p.lse[t] = 0.f; if constexpr (ROWS) p.row_loss[t] = 0.f; }
+      continue;
+    }
     const float* lg = p.logits + (size_t)t * p.ld;
     float m = -INFINITY, s = 0.f, sl = 0.f;
     if (sm > 0.f) {
@@ -2085,7 +2094,8 @@ __global__ __launch_bounds__(256) void ce_w_chunk_fwd_k(tfx_ce_w_chunk_args p) {
     if (q0 == 0) {
       const float lse = M + __logf(S);
       p.lse[t] = lse;
-      ce_w_row(rw, lse, lg[lab], sl, z, sm, inv_v, sum);
+      const float wr = ce_w_row(rw, lse, lg[lab], sl, z, sm, inv_v, sum);
+      if constexpr (ROWS) p.row_loss[t] = wr;
     }
   }
   ce_reg_flush(sum, sacc, p.acc, p.aux);
@@ -2169,6 +2179,33 @@ __global__ __launch_bounds__(256) void mse_w_k(tfx_mse_w_args p) {
       if (p.row_inst) g *= 1.f / fmaxf(1.f - p.inst_time[p.row_inst[r]], p.clean_eps);
     }
     p.dpred[i] = f2bf(p.accumulate ? g + bf2f(p.dpred[i]) : g);
+  }
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) sacc[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) { float a = 0.f; for (int i = 0; i < WAVES; i++) a += sacc[i]; if (a != 0.f) atomicAdd(p.acc, a); }
+}
+
+// mse_w_k's sum without its gradient, plus the row sums (tfx.h tfx_mse_rows_args): the element order over [R, ld_d] is mse_w_k's, so `acc` receives the same
+// per-block sums; ld_d % 64 == 0 puts the 64 elements of a wave's trip into one row, whose share goes to row_sse[r] in one atomic (lane 0)
+__global__ __launch_bounds__(256) void mse_rows_k(tfx_mse_rows_args p) {
+  __shared__ float sacc[WAVES];
+  const long long n = (long long)p.R * p.ld_d, step = (long long)gridDim.x * blockDim.x;
+  float s = 0.f;
+  // (every lane of a wave runs the same number of trips: n, the block's first element and the stride are multiples of 64)
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) {
+    const int r = (int)(i / p.ld_d), c = (int)(i % p.ld_d);
+    const float w = p.row_w[r];
+    float v = 0.f;
+    if (c < p.dl && w != 0.f) {
+      const float df = p.pred[(size_t)r * p.ld_pred + c] - p.flow[(size_t)r * p.dl + c];
+      v = w * (df * df);
+    }
+    s += v;
+    if (w != 0.f) {                               // (uniform over the wave: one row)
+      const float rs = wave_sum(v);
+      if ((threadIdx.x & 63) == 0) atomicAdd(p.row_sse + r, rs);
+    }
   }
   s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) sacc[threadIdx.x >> 6] = s;
@@ -2987,8 +3024,17 @@ int tfx_ce_w_fwd(const tfx_ce_w_chunk_args* a, void* s) {
   const tfx_ce_chunk_args b = ce_w_plain(a);
   const int rc = ce_chunk_check(&b, false); if (rc) return rc < 0 ? rc : 0;
   if (!a->aux) return -1;
-  if (a->ld > CE_WIDE_LD) hipLaunchKernelGGL(ce_w_chunk_fwd_k<true>, dim3(ce_chunk_grid(&b, true)), dim3(256), 0, ST(s), *a);
-  else hipLaunchKernelGGL(ce_w_chunk_fwd_k<false>, dim3(ce_chunk_grid(&b, false)), dim3(256), 0, ST(s), *a);
+  if (a->ld > CE_WIDE_LD) hipLaunchKernelGGL((ce_w_chunk_fwd_k<true, tfx_ce_w_chunk_args>), dim3(ce_chunk_grid(&b, true)), dim3(256), 0, ST(s), *a);
+  else hipLaunchKernelGGL((ce_w_chunk_fwd_k<false, tfx_ce_w_chunk_args>), dim3(ce_chunk_grid(&b, false)), dim3(256), 0, ST(s), *a);
+  RET();
+}
+int tfx_ce_rows_fwd(const tfx_ce_rows_args* a, void* s) {
+  if (!a || !a->row_w || !a->row_loss || !ce_reg_weights_ok(a->z_weight, a->smoothing)) return -1;
+  const tfx_ce_chunk_args b = {a->T, a->V, a->logits, a->ld, a->labels, a->lse, a->acc, 0.f, nullptr, nullptr, 0};
+  const int rc = ce_chunk_check(&b, false); if (rc) return rc < 0 ? rc : 0;
+  if (!a->aux) return -1;
+  if (a->ld > CE_WIDE_LD) hipLaunchKernelGGL((ce_w_chunk_fwd_k<true, tfx_ce_rows_args>), dim3(ce_chunk_grid(&b, true)), dim3(256), 0, ST(s), *a);
+  else hipLaunchKernelGGL((ce_w_chunk_fwd_k<false, tfx_ce_rows_args>), dim3(ce_chunk_grid(&b, false)), dim3(256), 0, ST(s), *a);
   RET();
 }
 int tfx_ce_w_bwd(const tfx_ce_w_chunk_args* a, void* s) {
@@ -3009,6 +3055,13 @@ int tfx_mse_w_fwd_bwd(const tfx_mse_w_args* a, void* s) {
   long long n = (long long)a->R * a->ld_d; if (n == 0) return 0;
   long long g = (n + 255) / 256; if (g > 2048) g = 2048;
   hipLaunchKernelGGL(mse_w_k, dim3((unsigned)g), dim3(256), 0, ST(s), *a); RET();
+}
+int tfx_mse_rows_fwd(const tfx_mse_rows_args* a, void* s) {
+  if (!a || !a->row_w || !a->row_sse || a->R < 0 || a->ld_d <= 0 || (a->ld_d & 63) || a->dl < 0 || a->dl > a->ld_d || a->dl > a->ld_pred) return -1;
+  long long n = (long long)a->R * a->ld_d; if (n == 0) return 0;
+  if (!a->pred || !a->flow || !a->acc) return -1;
+  long long g = (n + 255) / 256; if (g > 2048) g = 2048;
+  hipLaunchKernelGGL(mse_rows_k, dim3((unsigned)g), dim3(256), 0, ST(s), *a); RET();
 }
 int tfx_cosine_fwd_bwd(const tfx_cosine_args* a, void* s) {
   if (!a || a->T < 0 || a->d <= 0 || a->d > 2048 || (a->d % 64) || (a->ld_pred % 8) || (a->ld_target % 8) || (a->ld_d % 8) || a->ld_pred < a->d || a->ld_target < a->d || a->ld_d < a->d) return -1;
@@ -3144,6 +3197,6 @@ int tfx_laser_v_bwd(const tfx_laser_v_args* a, void* s) {
   if (nch >= (1ll << 31)) return -4;
   hipLaunchKernelGGL(laser_v_bwd_k, dim3((unsigned)((nch + 255) / 256)), dim3(256), 0, ST(s), *a, (unsigned)nch); RET();
 }
-const char* tfx_version(void) { return "tfx-hip gfx950 r5-laser-muon-selfflow-adamgroups-oderk-tntable-atan2-ablate-lora-topkp-odeab-lossw-textreg-frozen"; }
+const char* tfx_version(void) { return "tfx-hip gfx950 r5-laser-muon-selfflow-adamgroups-oderk-tntable-atan2-ablate-lora-topkp-odeab-lossw-tokloss-textreg-frozen"; }
 
 }  // extern "C"

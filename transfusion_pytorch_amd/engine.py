@@ -235,7 +235,7 @@ class _BwdBuild:
 
 class Plan:
     def __init__(self, ps: ParamStore, b: int, n: int, I: int, R: dict, training: bool = True, cache=None, dp_groups: int = 0, tile_attn: bool = False, units=None, ctl_rows: int = 2, tn_defer=None, ckpt: bool = False,
-                 chunk_rows=None, text_terms=None, weighted=False):
+                 chunk_rows=None, text_terms=None, weighted=False, token_losses=False):
         """cache: None, or a KV cache tensor [depth, b, maxlen, 2*heads*64] (k~ | v per token).  With a cache the plan is a
         DECODE step: each layer appends this step's k~ / v rows at `cache_pos` (flat row b*maxlen + position, -1 = skip) and
         attention reads keys / values from the cache (per-token visible length in `kv_end`).
@@ -254,7 +254,13 @@ class Plan:
         weighted: PER-TOKEN LOSS WEIGHTS (training plans; Transfusion.forward(loss_weights=...)).  The plan owns `w_text` [T] - the weight of every row's
         label - and per native type `w_inst` [I] and `w_row` [R] (fp32, filled per step by the caller); every cross-entropy launch is its `_w` form
         (tfx.h tfx_ce_w_args, text terms included, so the plan owns `aux` too) and the flow and velocity targets are tfx_mse_w_fwd_bwd on `w_row`, which a
-        tfx_gather_f32 ahead of the flow target expands from `w_inst` through `row_inst`.  Nothing else differs, and False builds what it always built."""
+        tfx_gather_f32 ahead of the flow target expands from `w_inst` through `row_inst`.  Nothing else differs, and False builds what it always built.
+        token_losses: PER-TOKEN LOSSES (training plans; Transfusion.set_token_losses_()).  The plan is a `weighted` one (all-ones weights when
+        the caller gives none) whose loss launches are SPLIT: the forward runs tfx_ce_rows_fwd (chunked or not: without chunking the whole `logits` buffer
+        is the one chunk) and tfx_mse_rows_fwd, which leave `row_loss` [T] and per native type `row_sse` [R] next to `acc`; nothing of a gradient exists
+        until the backward, which forms EFFECTIVE ROW WEIGHTS on the device - w_r (d total / d loss x the row's share of the loss + d total / d row value;
+        set_token_loss_seeds) - and runs tfx_ce_w_bwd / tfx_mse_w_fwd_bwd on them: the `seed` list in front of the backward list, the chunked head's
+        launches inside it.  False builds what it always built."""
         md = ps.md
         self.training = training
         self.ckpt = bool(ckpt) and training
@@ -262,7 +268,8 @@ class Plan:
         # the side stream's weight-gradient GEMMs read a layer's saved activations one layer behind the data-gradient chain: two slots by layer parity
         # there, one on a single stream
         self.reg = (float(text_terms[0]), float(text_terms[1])) if (training and text_terms and (text_terms[0] or text_terms[1])) else None
-        self.weighted = bool(weighted) and training
+        self.token_losses = bool(token_losses) and training
+        self.weighted = (bool(weighted) or self.token_losses) and training
         self.n_slots = (2 if self._side_stream(md) else 1) if self.ckpt else None
         self.units = units
         assert not units or (cache is not None and tile_attn), 'compacted plans are decode plans on the tiled attention kernel (the row ranges are its arguments)'
@@ -285,6 +292,7 @@ class Plan:
         self.fwd, self.bwd = LaunchList(), LaunchList()
         self.vel = LaunchList()                         # optional launches: velocity-consistency MSE against an EMA teacher's flows (T:3394-3418)
         self.rec = LaunchList()                         # optional launches: reconstruction loss on the same predictions (MP:177-200, T:2840-2853)
+        self.seed = LaunchList()                        # token-loss plans: the loss gradients from the effective row weights, run in front of the backward list
         self.tap0, self.taps, self._tap_buf = None, {}, {}   # hidden taps (set_taps): the launches of a tap at x_0, this step's taps, their buffers
         self.noise_args, self._mse_args, self._vel_args, self._rec_args = {}, {}, {}, {}      # per native type: the args of its noising launch and of its loss targets
         self._clean_launch, self.clean_mode = {}, ('model' if cache is not None else 'latent')
@@ -365,6 +373,8 @@ class Plan:
             self.go_dev = torch.ones(1, device=self.ps.device, dtype=torch.float32); self.nbytes += 4      # d total / d loss of the step's backward (tfx_ce_chunk_args.scale_dev)
         else:
             self.logits = e(T, md.vp, dtype=torch.float32); self.dlogits = e(T, md.vp)
+            if self.token_losses:                             # (the split cross entropy over the whole buffer: lse is what its backward needs)
+                self.ce_lse = e(T, dtype=torch.float32)
         self.fe = z(I1, md.kf); self.cond = e(I1, 4 * d); self.pre = e(I1, 4 * d)
         self.tables = z(I1, nt3, dtype=torch.float32)
         self.lat = {}
@@ -380,10 +390,19 @@ class Plan:
                                flow=e(r, dl, dtype=torch.float32), pred=e(r, dl, dtype=torch.float32), dpred=z(r, dlp))
         for t in self.ext_add:
             self.lat[t]['add'] = z(R[t], d)      # additive token rows: the axial positional embedding (T:1384-1403, T:3173-3176), bf16
-        self.acc = z(max(8, 2 + 3 * len(md.dim_latents)) + (2 if (self.reg or self.weighted) else 0), dtype=torch.float32)      # [ce sum, ce count, flow sse per type..., velocity sse per type..., weighted recon sse per type...]
-        self._acc_all, self.aux = self.acc, None
-        if self.reg or self.weighted:         # text loss terms: [plain ce sum, sum of lse^2] ride behind the accumulators - one buffer, one memset
-            self.acc, self.aux = self._acc_all[:-2], self._acc_all[-2:]
+        n_acc = max(8, 2 + 3 * len(md.dim_latents))           # [ce sum, ce count, flow sse per type..., velocity sse per type..., weighted recon sse per type...]
+        n_aux = 2 if (self.reg or self.weighted) else 0       # text loss terms: [plain ce sum, sum of lse^2] ride behind the accumulators - one buffer, one memset
+        sse_rows = {t: r for t, r in R.items() if t not in self.ext} if self.token_losses else {}      # token losses: ... and behind them every native type's row sums
+        self._acc_all = z(n_acc + n_aux + sum(sse_rows.values()), dtype=torch.float32)
+        self.acc, self.aux = self._acc_all[:n_acc], (self._acc_all[n_acc:n_acc + 2] if n_aux else None)
+        if self.token_losses:                 # per label row / latent row: the row value, and the effective weight its gradient is formed under
+            self.row_loss, self.weff_text = z(max(T, 1), dtype=torch.float32), z(max(T, 1), dtype=torch.float32)
+            self.seed_acc = z(1, dtype=torch.float32)         # (where the backward's tfx_mse_w_fwd_bwd puts its sum: nobody reads it)
+            self.ce_seed, self.mse_seed = 0.0, {}             # d loss / d (acc[0]), {type: d loss / d (its flow sum)}: set_loss_scales
+            o = n_acc + n_aux
+            for t, r in sse_rows.items():
+                self.lat[t].update(row_sse=self._acc_all[o:o + r], weff_row=z(r, dtype=torch.float32))
+                o += r
         if self.weighted:                     # loss weights: per label row, per instance, per latent row (padding rows and instances: 0)
             self.w_text = z(max(T, 1), dtype=torch.float32)
             self.w_inst = z(I1, dtype=torch.float32)
@@ -646,7 +665,7 @@ class Plan:
         if self.chunk:
             for r0, m in self._chunks():                  # per chunk: its logits, then their cross entropy - nothing of the chunk outlives it but `ce_lse`
                 self._chunk_logits(L, r0, m)
-                L.append((self._ce_fn('tfx_ce_fwd'), self._ce_chunk_args(L, r0, m)))
+                L.append(('tfx_ce_rows_fwd', self._ce_rows_args(L, r0, m)) if self.token_losses else (self._ce_fn('tfx_ce_fwd'), self._ce_chunk_args(L, r0, m)))
                 self._hbm(L, extra_bytes=m * (md.vp * 4 + 4))              # fp32 logits in, lse out
         else:
             self._nt(L, A=self.embed, lda=d, B=S['logits'], ldb=d, M=T, N=md.vp, K=d, algo_n=md.vocab, epi=E['TFX_EPI_F32'], C=self.logits, ldc=md.vp)   # zero pad rows: N % 4 == 0 keeps the LDS-DMA kernel
@@ -663,7 +682,12 @@ class Plan:
         if self.cache is not None:           # decode plans: no losses
             self._chain_weight_prefetch(L)
             return
-        if not self.chunk:
+        if self.token_losses and not self.chunk:           # the split cross entropy on the whole buffer: the forward here, tfx_ce_w_bwd in `seed`
+            L.append(('tfx_ce_rows_fwd', self._ce_rows_args(L, 0, T)))
+            self._hbm(L, extra_bytes=T * (md.vp * 4 + 8))
+            self.seed.append(('tfx_ce_w_bwd', self._ce_chunk_args(self.seed, 0, T)))
+            self._hbm(self.seed, extra_bytes=T * (md.vp * (4 + 2) + 4))
+        elif not self.chunk:
             self._ce_args = capi.make_args(self._ce_fn('tfx_ce_args'), T=T, V=md.vocab, logits=self.logits, ld=md.vp, labels=self.labels, grad_scale=0.0,
                                            dlogits=self.dlogits, ld_d=md.vp, acc=self.acc, **self._ce_terms())
             L.append((self._ce_fn('tfx_ce_fwd_bwd'), self._ce_args))
@@ -677,6 +701,9 @@ class Plan:
                 gat = [self.w_inst.data_ptr(), self.row_inst[t].data_ptr(), lt['w_row'].data_ptr(), r]      # (mutable: the row count follows the step)
                 L.append((capi.lib().tfx_gather_f32, gat))
                 L.patched(('rows', t), (gat, 3))
+            if self.token_losses:             # the split squared error: sums and row sums here, the gradient in `seed` (no velocity / reconstruction target)
+                self._mse_args[t] = self._mse_rows(L, t, 2 + t)
+                continue
             self._mse_args[t] = self._loss_target(L, t, 2 + t, lt['flow'])
             # second target on the same prediction; dpred accumulates.  Run only when a teacher is given
             self._vel_args[t] = self._loss_target(self.vel, t, 2 + nm + t, lt['vel'], accumulate=1)
@@ -714,14 +741,47 @@ class Plan:
     def _ce_chunk_args(self, lst, r0, m):
         """tfx_ce_chunk_args of rows r0 .. r0 + m, owned by `lst` and registered with it for the per-step setters (set_ce_vocab, set_loss_scales)"""
         md = self.md
+        if self.token_losses:                 # the backward half of the split cross entropy: effective row weights, no other scale
+            z, e = self.reg or (0., 0.)
+            whole = not self.chunk
+            a = capi.make_args('tfx_ce_w_chunk_args', T=m, V=md.vocab, logits=self.logits if whole else self.logits_c, ld=md.vp, labels=self.labels[r0:], lse=self.ce_lse[r0:],
+                               acc=self.acc, grad_scale=1.0, scale_dev=None, dlogits=self.dlogits if whole else self.dlogits_c, ld_d=md.vp, z_weight=z, smoothing=e, aux=self.aux,
+                               row_w=self.weff_text[r0:])
+            lst.patched('ce', a)
+            return a
         a = capi.make_args(self._ce_fn('tfx_ce_chunk_args'), T=m, V=md.vocab, logits=self.logits_c, ld=md.vp, labels=self.labels[r0:], lse=self.ce_lse[r0:], acc=self.acc,
                            grad_scale=0.0, scale_dev=self.go_dev, dlogits=self.dlogits_c, ld_d=md.vp, **self._ce_terms(r0))
         lst.patched('ce', a)
         return a
 
+    def _ce_rows_args(self, lst, r0, m):
+        """tfx_ce_rows_args of rows r0 .. r0 + m (token-loss plans): the chunk's logits, or the whole `logits` buffer as the one chunk"""
+        md = self.md
+        z, e = self.reg or (0., 0.)
+        a = capi.make_args('tfx_ce_rows_args', T=m, V=md.vocab, logits=self.logits_c if self.chunk else self.logits, ld=md.vp, labels=self.labels[r0:], lse=self.ce_lse[r0:],
+                           acc=self.acc, z_weight=z, smoothing=e, aux=self.aux, row_w=self.w_text[r0:], row_loss=self.row_loss[r0:])
+        lst.patched('ce', a)
+        return a
+
     def _ce_structs(self):
         """the cross-entropy args the per-step setters write: the fused launch's, or every chunk's in every list that may still replay"""
-        return [a for L in self._lists() for a in L.patch.get('ce', ())] if self.chunk else [self._ce_args]
+        return [a for L in self._lists() for a in L.patch.get('ce', ())] if (self.chunk or self.token_losses) else [self._ce_args]
+
+    def _mse_rows(self, lst, t, slot):
+        """type t's split flow target (token-loss plans): tfx_mse_rows_fwd into `lst`, and in `seed` the tfx_mse_w_fwd_bwd that writes `dpred` from the
+        effective row weights - grad_scale 2: d (w err^2) / d pred = 2 w err.  Returns the forward's args."""
+        md, lt = self.md, self.lat[t]
+        dl = md.dim_latents[t]
+        a = capi.make_args('tfx_mse_rows_args', R=self.R[t], dl=dl, pred=lt['pred'], ld_pred=dl, flow=lt['flow'], ld_d=pad_to(dl, 64), acc=self.acc.data_ptr() + 4 * slot,
+                           row_w=lt['w_row'], row_sse=lt['row_sse'])
+        lst.append(('tfx_mse_rows_fwd', a))
+        lst.patched(('rows', t), (a, 'R'))
+        clean = dict(row_inst=self.row_inst[t], inst_time=self.inst_time, clean_eps=float(md.clean_eps)) if md.model_output_clean else {}
+        g = capi.make_args('tfx_mse_w_args', R=self.R[t], dl=dl, pred=lt['pred'], ld_pred=dl, flow=lt['flow'], grad_scale=2.0, dpred=lt['dpred'], ld_d=pad_to(dl, 64),
+                           acc=self.seed_acc, **clean, row_w=lt['weff_row'])
+        self.seed.append(('tfx_mse_w_fwd_bwd', g))
+        self.seed.patched(('rows', t), (g, 'R'))
+        return a
 
     def _loss_target(self, lst, t, slot, target, **extra):
         """one squared-error target on type t's flow prediction, appended to `lst`: the sum into accumulator `slot`, the gradient into (or, with
@@ -911,7 +971,7 @@ class Plan:
         kept frozen sets.  The setters below patch what these lists registered (LaunchList.patch) - a list dropped by select_frozen takes its
         args structs with it."""
         states = [{k: getattr(self, k, None) for k in self._BWD_LISTS}] + [st for st in self._bwd_sets.values() if st['bwd'] is not self.bwd]
-        return [self.fwd, self.vel, self.rec] + [st[k] for st in states for k in self._BWD_LISTS if st[k] is not None]
+        return [self.fwd, self.vel, self.rec, self.seed] + [st[k] for st in states for k in self._BWD_LISTS if st[k] is not None]
 
     def _patch_structure(self, lists, rope=True, seg=True):
         """write the loaded batch structure's rotary tables (the QK-norm / RoPE launches, the projections and the attention backward that carry them in
@@ -982,10 +1042,30 @@ class Plan:
             a.V = V
 
     def set_loss_scales(self, ce_scale: float, mse_scales: dict):
+        """the loss seeds' scales: d loss / d (a row's cross entropy), and per native type 2 d loss / d (a squared error).  A token-loss plan forms its
+        gradients at backward time: it remembers d loss / d (row value) for set_token_loss_seeds"""
+        if self.token_losses:
+            self.ce_seed, self.mse_seed = float(ce_scale), {t: 0.5 * float(s) for t, s in mse_scales.items()}
+            return
         for a in self._ce_structs():
             a.grad_scale = ce_scale
         for t, s in mse_scales.items():
             self._mse_args[t].grad_scale = s
+
+    def set_token_loss_seeds(self, go, g_text=None, g_rows=None):
+        """token-loss plans, at backward time: the effective row weights  w_r (go x d loss / d row value + g_r)  - `go` = d total / d loss (a device
+        scalar), `g_text` [T] and `g_rows` {type: [real rows]} = d total / d (the row values handed out), None where nobody used them - into `weff_text`
+        / `weff_row`, on the device"""
+        torch.mul(self.w_text, go * self.ce_seed if g_text is None else go * self.ce_seed + g_text, out=self.weff_text)
+        for t, lt in self.lat.items():
+            if 'weff_row' in lt:
+                g = (g_rows or {}).get(t)
+                s = go * self.mse_seed.get(t, 0.0)
+                if g is None:
+                    torch.mul(lt['w_row'], s, out=lt['weff_row'])
+                else:                                         # (rows past the real ones: weight 0)
+                    k = g.numel()
+                    torch.mul(lt['w_row'][:k], s + g, out=lt['weff_row'][:k]); lt['weff_row'][k:].zero_()
 
     # ------------------------------------------------------------------------------------ backward
     def _build_backward(self):
@@ -1058,7 +1138,7 @@ class Plan:
         md, d, S, L = self.md, self.md.dim, self.ps.shadows, self.bwd
         for r0, m in self._chunks():
             self._chunk_logits(L, r0, m)
-            L.append((self._ce_fn('tfx_ce_bwd'), self._ce_chunk_args(L, r0, m)))
+            L.append(('tfx_ce_w_bwd' if self.token_losses else self._ce_fn('tfx_ce_bwd'), self._ce_chunk_args(L, r0, m)))
             self._hbm(L, extra_bytes=m * (md.vp * (4 + 2) + 4))                # fp32 logits and lse in, bf16 d logits out
             if c.tr('to_text_logits.weight'):
                 self._tn(L, m, md.vocab, d, A=self.dlogits_c, lda=md.vp, a_cols=md.vp, B=self.embed[r0:], ldb=d, b_cols=d, C=self.ps.grad_ptr('to_text_logits.weight'), ldc=d)

@@ -284,6 +284,13 @@ def loss_weight_maps(P: PackedBatch):
     return tok_part, inst_part
 
 
+def flow_row_index(P: PackedBatch):
+    """per modality type present: (R_t, 2) int64 - for every latent row of the type, in the order of the type's rows (`row_inst`: instances in scan order,
+    each with its rows in order), the sample it belongs to and its instance's number within that sample (`inst_m`: 0 for the sample's first modality
+    part, whatever its type) - `TokenLosses.flow_index`.  Structure only."""
+    return {t: np.stack([P.inst_b[ri], P.inst_m[ri]], axis=1).astype(np.int64).reshape(-1, 2) for t, ri in P.row_inst.items()}
+
+
 def check_weight_tensors(src, on_device, seen=None):
     """refuse negative / non-finite loss weights given as tensors: ONE flag read back from the device for all of them (the values stay there).  `seen`: a
     dict the caller keeps - a tensor that passed is remembered by identity and version counter ({id: (weak reference, version)}), so a weight set that is

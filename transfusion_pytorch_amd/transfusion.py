@@ -22,7 +22,7 @@ from . import capi
 from . import engine as _engine            # (pull_form_ok is looked up there at call time)
 from .engine import Plan
 from .ode import check_odeint_kwargs
-from .packing import check_weight_tensors, fast_signature, is_int_tensor, lay_loss_weights, loss_weight_maps, scan_batch, scan_signature, token_maps, token_segments
+from .packing import check_weight_tensors, fast_signature, flow_row_index, is_int_tensor, lay_loss_weights, loss_weight_maps, scan_batch, scan_signature, token_maps, token_segments
 from .axial import ContinuousAxialPositionalEmbedding
 from .params import ModelDims, ParamStore
 
@@ -31,6 +31,13 @@ class TextLossTerms(NamedTuple):            # Transfusion.text_loss_terms()
     text: torch.Tensor
     ce: torch.Tensor
     lse_sq: torch.Tensor
+
+
+class TokenLosses(NamedTuple):              # the training calls under model.set_token_losses_()
+    text: torch.Tensor                       # (b, n) fp32: w r of predicting token j + 1 of packed row i; ignored positions exactly 0
+    text_weight: torch.Tensor                # (b, n) fp32: the weight that position added to the text loss' weight sum (0 where ignored)
+    flow: list                               # per modality type present, ascending: (R_t,) fp32, w_r sum_c err^2 of every real latent row
+    flow_index: list                         # per type: (R_t, 2) int64, (sample, the instance's number within its sample in scan order) of every row
 
 
 class LossBreakdown(NamedTuple):            # T:105-110
@@ -254,7 +261,9 @@ class _NativeLoss(torch.autograd.Function):
                        output (`pre_post_transformer_enc_dec`) or the axial positional embedding rows; their gradient is d loss / d x0 at those rows
       outputs        - the final-embedding rows of spec['out'] types, for the user's decoder; their incoming gradient seeds the backward next to the loss
                      - with spec['hid'] = (indices, raw): the hiddens of those indices (`_hiddens_out`); a gradient that reaches one of them is a
-                       hidden tap of this step's backward (engine.Plan.set_taps)"""
+                       hidden tap of this step's backward (engine.Plan.set_taps)
+                     - with spec['tl'] = (n, [(type, rows)]) (token-loss plans): the text row terms (b, n) and every native type's row sums; a gradient
+                       that reaches one of them enters the backward as a per-row factor (engine.Plan.set_token_loss_seeds)"""
 
     @staticmethod
     def forward(ctx, anchor, model, loss, spec, *rows):
@@ -267,24 +276,34 @@ class _NativeLoss(torch.autograd.Function):
             ctx.set_materialize_grads(False)              # a hidden nobody used is no tap
             ctx.n_true = model._live_n_true
             outs += model._hiddens_out(plan, ctx.n_true, *spec['hid'])
+        if spec.get('tl'):
+            ctx.set_materialize_grads(False)              # a row value nobody used costs nothing
+            outs += model._token_loss_rows(plan, *spec['tl'])
         return tuple(outs)
 
     @staticmethod
     def backward(ctx, grad_loss, *grad_rows):
         model, spec = ctx.model, ctx.spec
         plan = model._live[0]
+        if (spec.get('hid') or spec.get('tl')) and ctx.step_id != model._live[1]:
+            raise RuntimeError('backward() of a stale loss: the native engine keeps the activations of the latest forward only')
         for t, g in zip(spec['out'], grad_rows):
             if g is None:
                 plan.lat[t]['gemb'].zero_()
             else:
                 plan.lat[t]['gemb'].copy_(g)
+        n_hid = len(spec['hid'][0]) if spec.get('hid') else 0
         if spec.get('hid'):
-            if ctx.step_id != model._live[1]:
-                raise RuntimeError('backward() of a stale loss: the native engine keeps the activations of the latest forward only')
             taps = {k: g for k, g in zip(spec['hid'][0], grad_rows[len(spec['out']):]) if g is not None}
             plan.set_taps(taps, ctx.n_true)
-            if grad_loss is None:                         # only the hiddens were used: the loss seeds carry nothing
-                grad_loss = torch.zeros((), device=plan.dembed.device)
+        if spec.get('tl'):
+            n, types = spec['tl']
+            g_text, *g_rows = grad_rows[len(spec['out']) + n_hid:]
+            if g_text is not None:                        # onto the plan's (b, bucketed n) label grid
+                g_text = torch.nn.functional.pad(g_text.to(torch.float32), (0, plan.n - n)).reshape(-1)
+            model._tl_grads = (g_text, {t: g.to(torch.float32) for (t, _), g in zip(types, g_rows) if g is not None})
+        if grad_loss is None:                             # only hiddens / row values were used: the loss itself seeds nothing
+            grad_loss = torch.zeros((), device=plan.dembed.device)
         plan.rows_in = bool(spec['in'])                   # rows of d loss / d x_0 go back to PyTorch: the chain runs to x_0 whatever is frozen
         model._native_backward(grad_loss, ctx.step_id)
         back = [plan.dx0.index_select(0, plan.row_tok[t].long().clamp(min=0)).float() for _, t in spec['in']]
@@ -429,6 +448,8 @@ class Transfusion(nn.Module):
         self._chunk = None                   # rows per chunk of the text head (set_text_head_chunking_; None = off): part of the plan key
         self._text_terms = (0.0, 0.0)        # (z-loss weight, label smoothing) of the text loss (set_text_loss_terms_): part of the plan key
         self._text_terms_plan = None         # the plan of the last training step that ran with the terms on (text_loss_terms)
+        self._token_losses = False           # set_token_losses_: training calls also return the per-token losses (a TokenLosses)
+        self._tl_grads = None                # (d total / d text row terms, {type: d total / d row sums}) of the running backward (_NativeLoss -> _native_backward)
         self._lw_seen = {}                   # loss-weight tensors that passed the finite / non-negative check (packing.check_weight_tensors)
         self._struct_cache = {}
         self._decode_plans = {}              # decode plans of the cached forward calls and of the sampler (sampling.Sampler._decode_plan)
@@ -728,6 +749,17 @@ class Transfusion(nn.Module):
     def text_label_smoothing(self) -> float:
         return self._text_terms[1]
 
+    def set_token_losses_(self, on=True):
+        """PER-TOKEN LOSSES: with the switch on, every training call - `forward(batch, return_loss=True)`, `forward_text(text)`, `forward_modality(x)` -
+        appends a `TokenLosses(text, text_weight, flow, flow_index)` to its outputs (see `forward`), whose `text` and `flow[t]` are differentiable next to
+        `loss`.  A switch on the model, like `set_text_loss_terms_` and `set_text_head_chunking_`: the entry points keep their signatures.  It selects the
+        token-loss plans (engine.Plan(token_losses=True)); off - the default - nothing differs.  While it is on, calls that return no loss (inference,
+        decode, embed, pred flows, sampling) are refused: switch it off first.  Not copied by create_ema() / copy.deepcopy.  Returns self."""
+        if not isinstance(on, bool):
+            raise ValueError(f'set_token_losses_ takes a bool, got {on!r}')
+        self._token_losses = on
+        return self
+
     def set_text_loss_terms_(self, z_loss=0., label_smoothing=0.):
         """the two standard regularisers of the text head's cross entropy, formed inside the native loss kernels (include/tfx.h tfx_ce_reg_args): per
         valid text row, with lse = log sum_c exp(logit_c) over the V columns the loss runs over,
@@ -781,21 +813,23 @@ class Transfusion(nn.Module):
             self._rope = (cos.to(self.device).contiguous(), sin.to(self.device).contiguous())
         return self._rope
 
-    def _plan(self, b, n, I, R, training, text_loss=False, weighted=False):
+    def _plan(self, b, n, I, R, training, text_loss=False, weighted=False, token_losses=False):
         """`text_loss`: the call returns the text loss (forward, forward_text with return_loss) - the training plans set_text_head_chunking_ applies to;
-        `weighted`: the call carries loss weights (their presence is part of the key, their values never are)"""
+        `weighted`: the call carries loss weights (their presence is part of the key, their values never are); `token_losses`: the call returns the
+        per-token losses (a token-loss plan is a weighted one - all ones without `loss_weights` -, so the switch alone keys it; off, the key is what it was)"""
         dp_groups = getattr(self, '_dp_groups', 0) if training else 0
         ckpt = training and self._ckpt                              # inference, decode, sampling and hiddens-only plans never look at the switch
         chunk = self._chunk if (training and text_loss) else None   # ... nor at this one; forward_modality's training plans neither (no text loss)
         terms = self._text_terms if (training and text_loss and any(self._text_terms)) else None      # ... nor at the text loss terms
-        weighted = bool(weighted) and training
-        key = (b, n, I, tuple(sorted(R.items())), training, dp_groups, ckpt, chunk, terms, weighted)
+        token_losses = bool(token_losses) and training
+        weighted = bool(weighted) and training and not token_losses
+        key = (b, n, I, tuple(sorted(R.items())), training, dp_groups, ckpt, chunk, terms, weighted) + (('token_losses',) if token_losses else ())
         plan = self._plans.pop(key, None)
         if plan is None:
             while len(self._plans) >= 8:                             # least recently used plan goes first (dict order = use order)
                 self._plans.pop(next(iter(self._plans)))
             plan = Plan(self.store, b, n, I, R, training=training, dp_groups=dp_groups, ckpt=ckpt, **({'chunk_rows': chunk} if chunk else {}), **({'text_terms': terms} if terms else {}),
-                        **({'weighted': True} if weighted else {}))
+                        **({'weighted': True} if weighted else {}), **({'token_losses': True} if token_losses else {}))
             # a plan owns every activation of its step (tens of GB for a training plan at dim 1024 / depth 24): besides the count, the cache is
             # bounded by bytes - TFX_PLAN_BUDGET_GB, default 40 % of the device memory - oldest first, the new plan always stays
             budget = float(os.environ.get('TFX_PLAN_BUDGET_GB', 0)) * 2 ** 30 or 0.4 * torch.cuda.get_device_properties(self.device).total_memory
@@ -974,9 +1008,31 @@ class Transfusion(nn.Module):
         rows and to the tokens the packer inserts for it ([meta], shape characters, [som], [eom]); [sos] is never a label; [eos] takes the last weight of the
         sample's last part.  Every valid token adds (its weight) x (its own loss) / total_tokens to the loss - no new normaliser; `LossBreakdown.text` is the
         weighted mean sum w r / sum w, each flow / velocity entry sum w err^2 / (dim_latent sum_rows w) (0 where sum w is 0).  The weights run inside the
-        native loss kernels (include/tfx.h tfx_ce_w_args, tfx_mse_w_args) and never visit the host."""
+        native loss kernels (include/tfx.h tfx_ce_w_args, tfx_mse_w_args) and never visit the host.
+        PER-TOKEN LOSSES (`set_token_losses_()`, a switch on the model like the text loss terms: the signatures stay what they were) - a `TokenLosses` is
+        appended to the outputs of a training step (behind the loss, the breakdown, the
+        hiddens and the times): `text` (b, n) - element [i, j] is w r of predicting token j + 1 of packed row i (r: the row term of the text loss with the
+        model's text loss terms, w: the row's loss weight, 1 without `loss_weights`; ignored positions exactly 0; n: the batch's true label length) -,
+        `text_weight` (b, n), `flow` - per modality type present, ascending, (R_t,) with w_r sum_c err^2 of every real latent row - and `flow_index`,
+        (R_t, 2) int64 (sample, instance number within the sample).  loss == text_loss_weight text.sum() / total_tokens + sum_t flow_loss_weight
+        (flow[t].sum() / (R_t dim_latent_t)) w_t.  `text` and every `flow[t]` are outputs of the step's autograd node next to `loss`: any PyTorch function
+        of them (and of `loss` and hidden taps) goes through ONE backward(); their gradients enter the native backward as per-row factors, whatever
+        `text_loss_weight` is.  Under no_grad the same values come back without a graph (the reference-model pass of DPO).  Activations belong to the
+        latest forward of a model object: a DPO step is one policy forward over chosen + rejected in one batch."""
         # ---- dispatch and argument checks
         self._require_gpu()
+        return_token_losses = self._token_losses
+        if return_token_losses:
+            if torch.is_tensor(modalities):
+                raise NotImplementedError('token losses (set_token_losses_) with a tensor batch: call forward_text(text) / forward_modality(x) directly')
+            if self.has_recon_loss:
+                raise NotImplementedError('token losses (set_token_losses_) with reconstruction_loss_weight > 0: that term has no per-row report')
+            if velocity_consistency_ema_model is not None:
+                raise NotImplementedError('token losses (set_token_losses_) with a velocity_consistency_ema_model: the velocity term has no per-row report')
+            if (not return_loss or return_embed or return_only_pred_flows or return_kv_cache or cache is not None or decoding_text_or_modality is not None
+                    or (_hidden_request or {}).get('hiddens_only')):
+                raise ValueError('token losses (set_token_losses_) are the losses of a training step: the call needs return_loss = True and no cache / decode / '
+                                 'embed / pred-flow argument - switch them off first (set_token_losses_(False))')
         if loss_weights is not None:
             if torch.is_tensor(modalities):
                 raise NotImplementedError('loss_weights with a tensor batch: call forward_text(text, loss_weights=W) / forward_modality(x, loss_weights=w)')
@@ -1062,7 +1118,8 @@ class Transfusion(nn.Module):
             if 'w_maps' not in S:                             # (structure only: shared by every weight list on this structure)
                 S['w_maps'] = tuple(torch.from_numpy(a).to(dev) for a in loss_weight_maps(P))
             weights = lay_loss_weights(P, loss_weights, dev, S['w_maps'], self._lw_seen)
-        plan = self._step_plan(S, return_loss, hid_only, no_teacher=ema is None and not return_only_pred_flows, weighted=weights is not None)
+        plan = self._step_plan(S, return_loss, hid_only, no_teacher=ema is None and not return_only_pred_flows, weighted=weights is not None,
+                               token_losses=return_token_losses)
         if train_hiddens and not hid_only and torch.is_grad_enabled() and not (_engine.pull_form_ok(self.md) and plan.pull):
             raise NotImplementedError(f'return_hiddens next to the loss (hidden taps) needs the pull-form AttentionResidual backward: {_engine.PULL_LIMITS} '
                                       '(under torch.no_grad() the hiddens come back without a tap)')
@@ -1093,14 +1150,14 @@ class Transfusion(nn.Module):
         def teacher_flows():                                                               # T:3383-3418; called behind the student's forward
             with _teacher_pass(ema, flat_pred_flows=True):
                 return ema(velocity_modalities, times=orig_times + velocity_consistency_delta_time, return_only_pred_flows=True)
-        loss, breakdown, hid_out = self._losses(plan, S, ext_ctx, rows_in, teacher_flows if ema is not None else None, hid)
+        loss, breakdown, hid_out, tok = self._losses(plan, S, ext_ctx, rows_in, teacher_flows if ema is not None else None, hid)
         # T:3433-3450: loss[, breakdown], hiddens[, times]
         return _pack_outputs(loss, (return_breakdown, breakdown), (train_hiddens, self._hiddens_list(hid, hid_out)), (return_times, times),
-                             (_hidden_request is not None, (plan, S['n_true'])))
+                             (plan.token_losses, tok), (_hidden_request is not None, (plan, S['n_true'])))
 
-    def _step_plan(self, S, return_loss, hid_only, no_teacher, weighted=False):
+    def _step_plan(self, S, return_loss, hid_only, no_teacher, weighted=False, token_losses=False):
         """the plan of an interleaved `forward` step with the structure S loaded.  `no_teacher`: no EMA teacher and not a teacher's own `return_only_pred_flows` call.
-        `weighted`: the step carries loss weights."""
+        `weighted`: the step carries loss weights; `token_losses`: it returns the per-token losses."""
         md, I, R = self.md, S['I'], S['R']
         # Ragged corpora change the number of modality instances and of latent rows with every batch.  A training plan owns every activation of the
         # step and its launch lists (building one costs far more than a step), so in the plain training case the plan is built for both counts ROUNDED
@@ -1111,7 +1168,7 @@ class Transfusion(nn.Module):
                   and not md.model_output_clean and os.environ.get('TFX_PLAN_BUCKETS', '1') != '0')
         Ip = _bucket(I, 64) if (bucket and I > 0) else I
         Rp = {t: _bucket(r, 256) for t, r in R.items()} if bucket else R
-        plan = self._plan(S['b'], S['n'], Ip, Rp, training=return_loss and not hid_only, text_loss=True, weighted=weighted)
+        plan = self._plan(S['b'], S['n'], Ip, Rp, training=return_loss and not hid_only, text_loss=True, weighted=weighted, token_losses=token_losses)
         if return_loss and not hid_only:
             plan.clear_taps()                               # a tap lives for the step that set it
         if md.model_output_clean:
@@ -1143,6 +1200,9 @@ class Transfusion(nn.Module):
             plan.w_text.copy_(grid[:, 1:n + 1].reshape(-1))
             I = w_inst.numel()
             plan.w_inst[:I].copy_(w_inst); plan.w_inst[I:].zero_()
+        elif labels and plan.weighted:                        # a token-loss plan without loss weights: all ones (padding instances: 0)
+            I = S['I']
+            plan.w_text.fill_(1.); plan.w_inst[:I].fill_(1.); plan.w_inst[I:].zero_()
 
     def _load_latents(self, plan, S, latents, ext_ctx, return_loss):
         """latent rows and their noise onto the plan.  Returns the rows PyTorch hands to the engine: (kind, type, tensor with autograd history)"""
@@ -1195,7 +1255,7 @@ class Transfusion(nn.Module):
     def _losses(self, plan, S, ext_ctx, rows_in, teacher_flows, hid):
         """the training step from the loaded plan to the loss: forward, the native loss terms (text, then per ascending type flow, velocity
         consistency against `teacher_flows()`, reconstruction), the step's closing, then the terms of the types whose decoder is a user module.
-        Returns (loss, LossBreakdown, the hiddens of `hid` = (indices, raw) | [])."""
+        Returns (loss, LossBreakdown, the hiddens of `hid` = (indices, raw) | [], the TokenLosses of a token-loss plan | None)."""
         md, M, stream, acc = self.md, self.num_modalities, self._stream(), plan.acc
         P, tm, R = S['P'], S['tm'], S['R']
         # ---- loss seeds (the token-count normalisers cancel: d loss / d logit = w / total_tokens, T:3331)
@@ -1249,13 +1309,18 @@ class Transfusion(nn.Module):
                 loss = loss + self.reconstruction_loss_weight * recon_losses[t] * w[t]
 
         ext_out = sorted(plan.ext)
-        loss, outs = self._close_step(plan, loss, rows_in, ext_out, hid, S['n_true'])
+        tl = (S['n_true'], [(t, R[t]) for t in native]) if plan.token_losses else None
+        loss, outs = self._close_step(plan, loss, rows_in, ext_out, hid, S['n_true'], tl)
+        n_tl = 1 + len(native) if tl else 0
+        row_sums = dict(zip(native, outs[len(outs) - len(native):])) if tl else {}
         for t, rows in zip(ext_out, outs):                                                  # the user's decoders and their flow losses, in PyTorch
             preds = self._ext_decode(t, rows, ext_ctx[t])
             wi = None
             if plan.weighted:                              # the weights of the type's instances, in scan order (the order of `preds`)
                 wi = plan.w_inst[torch.from_numpy(np.flatnonzero(P.inst_type == t)).to(plan.w_inst.device)]
             fl, rec = self._ext_flow_loss(t, preds, ext_ctx[t], wi)
+            if tl:                                         # the type's row sums where its flow loss is formed: in PyTorch, with autograd's graph
+                row_sums[t] = self._ext_row_sums(t, preds, ext_ctx[t]['flow'], wi)
             if wi is not None:
                 fl, flow_losses[t] = fl
             else:
@@ -1273,24 +1338,48 @@ class Transfusion(nn.Module):
         by_type = lambda d: [d[t] for t in sorted(d)]
         breakdown = LossBreakdown(loss, text_loss, by_type(flow_losses), by_type(velocity_losses) if velocity_losses is not None else None,
                                   by_type(recon_losses) if self.has_recon_loss else None)
-        return loss, breakdown, outs[len(ext_out):]
+        tok = None
+        if tl:
+            if 'flow_index' not in S:                      # (structure only: cached with it)
+                S['flow_index'] = {t: torch.from_numpy(a).to(self.device) for t, a in flow_row_index(P).items()}
+            tok = TokenLosses(outs[len(outs) - n_tl], self._text_weight_out(plan, S['n_true']), by_type(row_sums), by_type(S['flow_index']))
+        return loss, breakdown, outs[len(ext_out):len(outs) - n_tl], tok
 
-    def _close_step(self, plan, loss, rows_in=(), out_types=(), hid=None, n_true=None):
+    def _close_step(self, plan, loss, rows_in=(), out_types=(), hid=None, n_true=None, tl=None):
         """close a training step: `plan` holds the live activations of step `_step_id`, and with gradients enabled the loss goes through `_NativeLoss`
         (`rows_in`: (kind, type, rows PyTorch produced), `out_types`: types whose embedding rows go out to a user decoder, `hid`: (indices, raw) of
-        the hiddens wanted, cut to `n_true` columns).  Returns (loss, [embedding rows per out type ..., hiddens ...]) - under no_grad the same tensors without a graph."""
+        the hiddens wanted, cut to `n_true` columns, `tl`: (label columns, [(native type, real rows)]) of a token-loss plan).  Returns (loss, [embedding
+        rows per out type ..., hiddens ..., text row terms, row sums per native type ...]) - under no_grad the same tensors without a graph."""
         self._step_id += 1
         self._live = (plan, self._step_id)
+        self._tl_grads = None
         if torch.is_grad_enabled():
             if self._anchor is None or self._anchor.device != self.device:
                 self._anchor = torch.zeros((), device=self.device, requires_grad=True)
             spec = {'in': [(k, t) for k, t, _ in rows_in], 'out': list(out_types)} if (rows_in or out_types) else _NO_ROWS
             if hid:
                 spec = dict(spec, hid=hid)
+            if tl:
+                spec = dict(spec, tl=tl)
             loss, *outs = _NativeLoss.apply(self._anchor, self, loss, spec, *[r for _, _, r in rows_in])
             return loss, outs
         outs = [plan.embed.index_select(0, plan.row_tok[t].long().clamp(min=0)).float() for t in out_types]
-        return loss, outs + (self._hiddens_out(plan, n_true, *hid) if hid else [])
+        return loss, outs + (self._hiddens_out(plan, n_true, *hid) if hid else []) + (self._token_loss_rows(plan, *tl) if tl else [])
+
+    @staticmethod
+    def _token_loss_rows(plan, n, types):
+        """the row values of a token-loss plan's latest forward: [text row terms (b, the n real label columns), row sums (real rows) per native type ...], copies"""
+        return [plan.row_loss.view(plan.b, plan.n)[:, :n].clone()] + [plan.lat[t]['row_sse'][:r].clone() for t, r in types]
+
+    @staticmethod
+    def _text_weight_out(plan, n):
+        """`TokenLosses.text_weight`: the weight every label position added to acc[1] - its loss weight where the label counts, 0 elsewhere"""
+        return torch.where(plan.labels >= 0, plan.w_text, torch.zeros_like(plan.w_text)).view(plan.b, plan.n)[:, :n].clone()
+
+    def _ext_row_sums(self, t, preds, targets, wi):
+        """row sums w_i sum_c err^2 of an `ext` type (its decoder is a user module: formed where its flow loss is, in PyTorch), instances in scan order"""
+        ch = 0 if self.channel_first_latent[t] else -1
+        return torch.cat([w * (p - f).square().sum(ch).reshape(-1) for p, f, w in zip(preds, targets, wi.to(torch.float32))])
 
     def _hiddens_list(self, hid, tensors):
         """the depth + 2 long list `return_hiddens` hands out: the tensors at the indices of `hid` = (indices, raw), None elsewhere"""
@@ -1526,8 +1615,14 @@ class Transfusion(nn.Module):
         text-only part of the vocabulary (`text_only_logits_mask`, T:1509, T:2653).  Inference calls also take / return the kv cache
         `(tensor, tokens_seen)` and the hiddens (T:2612-2645): with a cache, `text` holds the NEW tokens only (rotary positions from tokens_seen).
         `loss_weights`: a float tensor (b, n) aligned with `text` - column j weights the prediction of text[:, j], column 0 is unused; the loss is the weighted
-        mean sum w r / sum w (torch.nn.functional.cross_entropy's `weight` normalisation; with weights in {0, 1}: the loss with those labels ignored)."""
+        mean sum w r / sum w (torch.nn.functional.cross_entropy's `weight` normalisation; with weights in {0, 1}: the loss with those labels ignored).
+        With `set_token_losses_()`: returns (loss, TokenLosses(text, text_weight, [], [])) - `text` (b, n - 1): w r of predicting text[:, j + 1],
+        differentiable as in `forward`; loss == text.sum() / text_weight.sum()."""
         self._require_gpu()
+        return_token_losses = self._token_losses
+        if return_token_losses and (not return_loss or return_embed or cache is not None):
+            raise ValueError('token losses (set_token_losses_) are the losses of a training step: the call needs return_loss = True and no cache / embed '
+                             'argument - switch them off first (set_token_losses_(False))')
         if (cache is not None or return_hiddens or return_kv_cache) and return_loss:
             raise NotImplementedError('forward_text: kv cache / hiddens are returned by the inference call only (return_loss = False)')
         dev, stream = self.device, self._stream()
@@ -1553,7 +1648,7 @@ class Transfusion(nn.Module):
                         seg_start=D(seg_start), seg_len=D(seg_len))
         S = self._structure(('text', b, n), build)
         self.store.refresh_shadows(stream)
-        plan = self._plan(b, n, 0, {}, training=return_loss, text_loss=True, weighted=loss_weights is not None)
+        plan = self._plan(b, n, 0, {}, training=return_loss, text_loss=True, weighted=loss_weights is not None, token_losses=return_token_losses)
         if plan.loaded_structure is not S:
             plan.load_structure(S, self._rope_tables(n), S['tok_inst'], S['kv_end'], S['q_start'], S['rot_pos'], segments=(S['seg_start'], S['seg_len']))
         plan.text_ids.copy_(inp.masked_fill(inp == -1, 0).reshape(-1))                      # T:2608
@@ -1567,12 +1662,18 @@ class Transfusion(nn.Module):
         plan.set_loss_scales(1.0, {})                        # mean over the valid labels: the count lives on the device (see _bwd_scale)
         plan.set_ce_vocab(self.num_text_tokens)              # text_only_logits_mask (T:2653)
         if plan.weighted:
-            plan.w_text.copy_(loss_weights[:, 1:].reshape(-1))
+            if loss_weights is not None:
+                plan.w_text.copy_(loss_weights[:, 1:].reshape(-1))
+            else:                                            # (a token-loss plan without loss weights: all ones)
+                plan.w_text.fill_(1.)
         plan.zero_acc()
         Plan.run(plan.fwd, stream)
         cnt = _positive(plan.acc[1]) if plan.weighted else plan.acc[1].clamp(min=1.)      # (loss weights: the sum of the weights)
         loss = plan.acc[0] / cnt                             # T:2655-2659
         self._bwd_scale = (1. / cnt).detach()
+        if plan.token_losses:
+            loss, (rows,) = self._close_step(plan, loss, n_true=n, tl=(n, []))
+            return loss, TokenLosses(rows, self._text_weight_out(plan, n), [], [])
         return self._close_step(plan, loss)[0]
 
     def _forward_text_cached(self, text, cache, return_embed, return_kv_cache, return_hiddens):
@@ -1606,9 +1707,20 @@ class Transfusion(nn.Module):
         the sample's time, no attention mask, no rotary embedding; loss = MSE(pred flow, x - noise).  Encoders / EMA velocity
         consistency / reconstruction loss are outside the native path.
         `loss_weights`: one weight per batch entry (a float tensor (b,) or a list of numbers): the flow and velocity terms become
-        sum w err^2 / (dim_latent sum_rows w) - a zero-weight entry trains as if it were not in the batch."""
+        sum w err^2 / (dim_latent sum_rows w) - a zero-weight entry trains as if it were not in the batch.
+        With `set_token_losses_()`: a TokenLosses(empty text, empty text_weight, [row sums (b L,)], [(b L, 2) index: (batch entry, 0)]) is appended to the
+        outputs - w_r sum_c err^2 of every latent row, differentiable as in `forward`; the flow term is flow[0].sum() / (dim_latent sum_rows w)."""
         # ---- argument checks, frozen encoder, times
         self._require_gpu()
+        return_token_losses = self._token_losses
+        if return_token_losses:
+            if not return_loss:
+                raise ValueError('token losses (set_token_losses_) are the losses of a training step: the call needs return_loss = True - switch them off first '
+                                 '(set_token_losses_(False))')
+            if self.has_recon_loss:
+                raise NotImplementedError('token losses (set_token_losses_) with reconstruction_loss_weight > 0: that term has no per-row report')
+            if velocity_consistency_ema_model is not None:
+                raise NotImplementedError('token losses (set_token_losses_) with a velocity_consistency_ema_model: the velocity term has no per-row report')
         if loss_weights is not None:
             if not return_loss:
                 raise ValueError('loss_weights weight the loss of a training step: they need return_loss = True')
@@ -1663,7 +1775,7 @@ class Transfusion(nn.Module):
 
         # ---- structure, plan and its inputs
         # (a type whose maps are user modules forms its loss in PyTorch: its weights are applied there, on the unweighted plan)
-        plan = self._modality_plan(b, L, t, return_loss, weighted=loss_weights is not None and not ext)
+        plan = self._modality_plan(b, L, t, return_loss, weighted=loss_weights is not None and not ext, token_losses=return_token_losses and not ext)
         plan.inst_time.copy_(times)
         lt = plan.lat[t]
         rows_in = []
@@ -1701,8 +1813,12 @@ class Transfusion(nn.Module):
         plan.set_ce_vocab(md.vocab)
         self._bwd_scale = None
         if plan.weighted:                                    # weighted mean: the divisor dl x (sum of the row weights) lives on the device (as forward_text's count)
-            plan.w_inst.copy_(loss_weights)
-            wsum = _positive(loss_weights.sum() * L)
+            if loss_weights is not None:
+                plan.w_inst.copy_(loss_weights)
+                wsum = _positive(loss_weights.sum() * L)
+            else:                                            # (a token-loss plan without loss weights: all ones)
+                plan.w_inst.fill_(1.)
+                wsum = torch.full((), float(rows), device=dev)
             self._bwd_scale = 1. / wsum
         plan.zero_acc()
         Plan.run(plan.fwd, stream, graph='auto')
@@ -1721,7 +1837,8 @@ class Transfusion(nn.Module):
             if not ext:
                 recon_loss = self._modality_recon_loss(plan, t, x, times, orig_modalities)
                 loss = loss + self.reconstruction_loss_weight * recon_loss
-        loss, outs = self._close_step(plan, loss, rows_in, [t] if ext and torch.is_grad_enabled() else [])
+        loss, outs = self._close_step(plan, loss, rows_in, [t] if ext and torch.is_grad_enabled() else [], tl=(0, [(t, rows)]) if plan.token_losses else None)
+        row_sums = outs[-1] if plan.token_losses else None
         if ext:                                                                            # the user's decoder and the flow loss, in PyTorch (T:2806-2817)
             emb = outs[0] if outs else plan.embed.float()                                  # (no_grad: every row of the plan is one of the type's, in order)
             pred = self.model_to_latent_projs[t](emb.view(b, *axial, d))
@@ -1729,6 +1846,9 @@ class Transfusion(nn.Module):
                 pred = (pred - noised) / (1. - tt).clamp_min(md.clean_eps)
             flow_loss = torch.nn.functional.mse_loss(pred, flow_ext) if loss_weights is None else self._entry_weighted_mse(pred, flow_ext, loss_weights)
             loss = loss + flow_loss
+            if return_token_losses:                                                     # the row sums where the loss is formed: (b, *axial) -> rows
+                row_sums = (pred - flow_ext).square().sum(1 if cf else -1).reshape(b, -1)
+                row_sums = (row_sums if loss_weights is None else row_sums * loss_weights[:, None]).reshape(-1)
             if self.has_recon_loss:
                 rec = eps + pred * (1. - tt)
                 if dec is not None:
@@ -1737,12 +1857,15 @@ class Transfusion(nn.Module):
                         rec = dec(rec)
                 recon_loss = torch.nn.functional.mse_loss(rec, orig_modalities.float())
                 loss = loss + self.reconstruction_loss_weight * recon_loss
-        if not return_loss_breakdown:
-            return loss
+        tok = None
+        if return_token_losses:
+            index = torch.stack([torch.arange(b, device=dev).repeat_interleave(row_sums.numel() // b), torch.zeros(row_sums.numel(), dtype=torch.int64, device=dev)], dim=1)
+            tok = TokenLosses(torch.zeros(b, 0, device=dev), torch.zeros(b, 0, device=dev), [row_sums], [index])
         zero = torch.zeros((), device=dev)
-        return loss, (flow_loss.detach(), velocity_loss.detach() if velocity_loss is not None else zero, recon_loss.detach() if recon_loss is not None else zero)
+        breakdown = (flow_loss.detach(), velocity_loss.detach() if velocity_loss is not None else zero, recon_loss.detach() if recon_loss is not None else zero)
+        return _pack_outputs(loss, (return_loss_breakdown, breakdown), (return_token_losses, tok))
 
-    def _modality_plan(self, b, L, t, return_loss, weighted=False):
+    def _modality_plan(self, b, L, t, return_loss, weighted=False, token_losses=False):
         """the plan of a `forward_modality` call - b instances of type t, L tokens each, one per row - with its structure loaded"""
         dev, rows = self.device, b * L
 
@@ -1752,7 +1875,7 @@ class Transfusion(nn.Module):
                         row_tok=torch.arange(rows, dtype=torch.int32, device=dev), empty=torch.zeros(0, dtype=torch.int32, device=dev))
         S = self._structure(('modality', b, L, t), build)
         self.store.refresh_shadows(self._stream())
-        plan = self._plan(b, L, b, {t: rows}, training=return_loss, weighted=weighted)
+        plan = self._plan(b, L, b, {t: rows}, training=return_loss, weighted=weighted, token_losses=token_losses)
         if self.md.model_output_clean:
             plan.set_clean_mode('latent')                   # pure flow path: the latent-space conversion (T:2772-2810)
         if plan.loaded_structure is not S:
@@ -1862,11 +1985,18 @@ class Transfusion(nn.Module):
             go = go * self._bwd_scale                         # forward_text: 1 / #valid labels, known on the device only
         lib, stream = capi.lib(), self._stream()
         sp = ctypes.c_void_p(stream)
-        # fp32 scalar read on the device; exactly 1.0 (plain loss.backward()) skips the pass over the seeds
-        if plan.chunk:
-            plan.go_dev.copy_(go.reshape(1))                  # chunked text head: no d logits exist yet - tfx_ce_bwd reads the scalar as it forms each chunk's
-        for seed in ([] if plan.chunk else [plan.dlogits]) + [lt['dpred'] for lt in plan.lat.values() if 'dpred' in lt]:
-            capi.check(lib.tfx_scale_bf16_dev(seed.data_ptr(), seed.numel(), go.data_ptr(), sp), 'tfx_scale_bf16_dev')
+        if plan.token_losses:
+            # no seeds exist yet: the effective row weights w (go x d loss / d row value + d total / d row value handed out), then d logits (unless the
+            # head is chunked: its chunks form theirs inside the list) and d pred from them - rounded once
+            plan.set_token_loss_seeds(go, *(self._tl_grads or (None, None)))
+            self._tl_grads = None
+            Plan.run(plan.seed, stream)
+        else:
+            # fp32 scalar read on the device; exactly 1.0 (plain loss.backward()) skips the pass over the seeds
+            if plan.chunk:
+                plan.go_dev.copy_(go.reshape(1))              # chunked text head: no d logits exist yet - tfx_ce_bwd reads the scalar as it forms each chunk's
+            for seed in ([] if plan.chunk else [plan.dlogits]) + [lt['dpred'] for lt in plan.lat.values() if 'dpred' in lt]:
+                capi.check(lib.tfx_scale_bf16_dev(seed.data_ptr(), seed.numel(), go.data_ptr(), sp), 'tfx_scale_bf16_dev')
         plan.dtables.zero_()
         if self.md.model_output_clean and plan.clean_mode == 'model' and len(plan.clean_bwd):
             Plan.run(plan.clean_bwd, stream)                # gradient paths through q = W proj (engine._clean_model_space)
